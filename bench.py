@@ -22,6 +22,11 @@ ranks itself: N fresh child processes of this script, before anything here has t
 GPU, one per GPU, rank 0's JSON line relayed; a failing rank fails the run.  Launched by
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` it is a rank.
 
+A plain run sets up, warms up, times the --steps steps, writes the last timed step's records with --dump-outputs DIR and
+prints the line: the headline (`value`, `ms_per_step`), `config` and a `roofline` from the timed region's own launch
+times.  Everything else below -- the one-lane pass, `host_sinks`, `cpu_baseline`, `parity`, the single-stream latency,
+`other_configs` at N = 1 and `sharded_configs` at N > 1 -- runs after the headline with --full only.
+
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (stft_scan) at 8
 algorithmic bytes per IQ sample against the 8 TB/s HBM peak: `kernel_ms` / `achieved` /
 `frac` are the launch ALONE (one lane: one launch over all streams of the rank per step,
@@ -158,7 +163,23 @@ def parse():
     ap.add_argument("--other-steps", type=int, default=10, help="timed steps per configuration of --other-configs")
     ap.add_argument("--other-budget-s", type=float, default=240.0,
                     help="wall-clock budget of the whole --other-configs block: a configuration is only started while it is not spent")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: the CPU baseline and parity against the oracle, "
+                         "the one-lane pass that prices the scan launch alone, the host sinks, the single-stream latency and the "
+                         "--other-configs / --sharded-configs blocks.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step (all ranks', global stream numbers, ordered by "
+                         "stream, start, bin) as DIR/records_<field>.npy, one array per rt_record field (float64 for the integer fields, "
+                         "float32 for the float ones), at most 64 MB in all (a fixed seeded sample of the rows beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0 or args.settle < 0:
+        ap.error("--warmup and --settle cannot be negative")
+    for opt, val in (("--other-configs", args.other_configs), ("--sharded-configs", args.sharded_configs)):
+        if val == "on" and not args.full:
+            ap.error(f"{opt} on needs --full")
+    return args
 
 
 def resolve_workload(args, world):
@@ -571,6 +592,8 @@ def main():
         n_records_total, n_hot_total, fell_back = (int(v) for v in c)
     else:
         n_records_total, n_hot_total = n_records, n_hot
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rec, lo, rank, world, dist)
 
     # which GPU every rank ran on (ordinal, PCI address): a SCALE record shows N distinct devices without any collective library
     me = device_identity(torch, local_rank)
@@ -595,14 +618,14 @@ def main():
     n_dense_streams = int(info.n_dense_streams)
     traffic, traffic_note = pmc_traffic(default_workload, 1, int(getattr(info, "segs_per_chunk", 0)) or None)  # per launch over all 256 streams, like kernel_ms
 
-    # parity + CPU baseline (untimed).  N = 1: the oracle on the host cores over a bounded sample (the baseline) and the
+    # parity + CPU baseline (untimed, --full).  N = 1: the oracle on the host cores over a bounded sample (the baseline) and the
     # records of >= 16 sampled streams against it; N > 1: every rank checks the first and last stream of its shard.
     parity = base = None
-    if not args.no_cpu_baseline and u8:
+    if args.full and not args.no_cpu_baseline and u8:
         # the wire format: no CPU baseline (BASELINE's metric is quoted on complex64), but the sampled streams against the oracle
         if args.parity_streams > 0:
             _, parity = cpu_baseline(args, an, iq, rec, kw, blen, n_seg, nperseg, timed=False, spread=args.parity_streams)
-    elif not args.no_cpu_baseline:
+    elif args.full and not args.no_cpu_baseline:
         if world == 1:
             base, parity = cpu_baseline(args, an, iq, rec, kw, blen, n_seg, nperseg, timed=True)
         else:
@@ -615,7 +638,7 @@ def main():
     an_decoder = an.decoder
     # the scan launch alone: one lane, one launch per step, nothing running beside it
     iso_ms = None
-    if args.isolated_steps > 0:
+    if args.full and args.isolated_steps > 0:
         # (one lane and one call in flight: a handle without lanes runs its detection on a stream of its own, beside the next scan)
         an.close()
         del an
@@ -628,18 +651,18 @@ def main():
     # host sinks, outside the timed region (rank 0, one core): what the reference's path ends in -- Signal objects on the
     # queue (analyze.py:251, 280) -- and the vectorised record -> CSV route, next to the record rate the timed steps produced
     sinks = None
-    if rank == 0:
+    if args.full and rank == 0:
         sinks = host_sinks(an_decoder, rec, [str(i) for i in range(lo, hi)], n_records_total * args.steps / elapsed)
 
     # (d) as SURVEY wrote it: the drop-in class on config 1 from host memory, as a latency (N = 1, default command)
     latency = None
-    if rank == 0 and world == 1 and default_workload and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and default_workload and not args.no_cpu_baseline:
         latency = single_stream_latency(local_rank)
 
     # the other BASELINE configurations and the reference's defaults under a real noise floor, timed in this same run
     others = None
-    if world == 1 and (args.other_configs == "on" or (args.other_configs == "auto" and default_workload)):
-        if args.isolated_steps <= 0:
+    if args.full and world == 1 and (args.other_configs == "on" or (args.other_configs == "auto" and default_workload)):
+        if iso_ms is None:
             an.close()
             del an
         del iq, rec
@@ -648,9 +671,9 @@ def main():
 
     # north_star's curve in the driver's own multi-GPU run: configs 4 and 5 as one population each, sharded over these same ranks
     sharded = None
-    if args.sharded_configs == "on" or (args.sharded_configs == "auto" and world > 1 and default_workload):
+    if args.full and (args.sharded_configs == "on" or (args.sharded_configs == "auto" and world > 1 and default_workload)):
         if others is None:
-            if args.isolated_steps <= 0:
+            if iso_ms is None:
                 an.close()
                 del an
             del iq, rec
@@ -668,7 +691,8 @@ def main():
                        + "; a one-lane rocprofv3 --kernel-trace average of the same command reproduces it")
     else:
         kernel_ms, kernel_frac = k_ms, conc_frac
-        kernel_note = "isolated pass skipped (--isolated-steps 0): the concurrent per-launch figure stands in"
+        kernel_note = ("isolated pass skipped (" + ("--isolated-steps 0" if args.full else "it runs with --full")
+                       + "): the concurrent per-launch figure stands in")
     roofline = {
         "bound": "hbm",
         "kernel": "stft_scan",
@@ -758,6 +782,35 @@ def main():
             dist.destroy_process_group()
         except Exception:  # (a rank that failed inside the sharded block has left the others in a collective: the line is out already)
             pass
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, rec, first_stream, rank, world, dist):
+    """``--dump-outputs``: the records the timed path returned in its last step (what a caller of ``fetch_records`` receives),
+    every rank's with global stream numbers, in a canonical order (stream, start, bin, end), one ``records_<field>.npy`` per
+    rt_record field: the integer fields as float64 (exact), the float fields as the float32 the library computed.  Beyond
+    DUMP_LIMIT_BYTES a fixed seeded sample of the rows is written.  Collective at N > 1 (gloo, after the timed region)."""
+    import numpy as np
+
+    mine = rec.copy()
+    mine["stream"] += first_stream
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+        if rank != 0:
+            return
+        mine = np.concatenate(parts)
+    mine = mine[np.lexsort((mine["end"], mine["fi"], mine["start"], mine["stream"]))]
+    fields = [f for f in mine.dtype.names if f != "reserved"]
+    row_bytes = sum(8 if mine.dtype[f].kind in "iu" else 4 for f in fields)
+    if len(mine) * row_bytes > DUMP_LIMIT_BYTES:
+        mine = mine[np.sort(np.random.default_rng(0).choice(len(mine), DUMP_LIMIT_BYTES // row_bytes, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for f in fields:
+        col = mine[f]
+        np.save(os.path.join(path, f"records_{f}.npy"), col.astype(np.float64 if col.dtype.kind in "iu" else np.float32))
 
 
 def host_sinks(decoder, rec, device_names, records_per_s_produced):

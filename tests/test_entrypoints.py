@@ -155,3 +155,32 @@ def test_product_library_has_no_laboratory_hooks():
         assert bad.returncode != 0 and "laboratory switch" in bad.stderr, switch
         lab = subprocess.run(["g++", "-fsyntax-only", "-x", "c++", "-DRT_DIAG", switch, hdr], capture_output=True, text=True)
         assert lab.returncode == 0, lab.stderr
+
+
+def test_bench_dump_outputs_orders_records_and_keeps_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 array per rt_record field in (stream, start, bin, end) order with global stream
+    numbers; an output over the byte limit becomes a fixed seeded sample of its rows"""
+    import numpy as np
+
+    from pyradiotracking_amd import _native
+
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    rec = np.zeros(500, dtype=_native.RECORD_DTYPE)
+    for f, hi in (("stream", 8), ("fi", 256), ("start", 8000), ("end", 8000), ("shadowed", 2)):
+        rec[f] = rng.integers(0, hi, len(rec))
+    rec["max_p"] = rng.random(len(rec), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), rec, 40, 0, 1, None)
+    got = {f: np.load(tmp_path / "all" / f"records_{f}.npy") for f in _native.RECORD_DTYPE.names if f != "reserved"}
+    assert not (tmp_path / "all" / "records_reserved.npy").exists()
+    assert got["stream"].dtype == np.float64 and got["max_p"].dtype == np.float32
+    order = np.lexsort((rec["end"], rec["fi"], rec["start"], rec["stream"]))
+    assert np.array_equal(got["stream"], rec["stream"][order] + 40.0) and np.array_equal(got["max_p"], rec["max_p"][order])
+    assert all(np.array_equal(got[f], rec[f][order]) for f in ("fi", "start", "end", "shadowed"))
+    row_bytes = 5 * 8 + 4 * 4  # stream, fi, start, end, shadowed; max_p, mean_p, std_db, row_mean
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * row_bytes)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), rec, 0, 0, 1, None)
+    a, b = (np.load(tmp_path / run / "records_start.npy") for run in ("a", "b"))
+    assert len(a) == 100 and a.tobytes() == b.tobytes()
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) < 100 * row_bytes + 10 * 200  # (+ the .npy headers)

@@ -131,7 +131,7 @@ def _run_bench(n_gpus, extra, launcher=True):
     env = dict(os.environ, RT_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", str(n_gpus), "--steps", "3", "--warmup", "1", "--settle", "2", "--isolated-steps", "2", "--cpu-streams", "4",
+    args = ["--gpus", str(n_gpus), "--steps", "3", "--warmup", "1", "--settle", "2", "--full", "--isolated-steps", "2", "--cpu-streams", "4",
             "--parity-streams", "4"] + extra
     if n_gpus == 1 or not launcher:
         cmd = [sys.executable, os.path.join(REPO, "bench.py")] + args  # N > 1: bench.py starts its ranks itself
@@ -146,10 +146,13 @@ def _run_bench(n_gpus, extra, launcher=True):
     return json.loads(lines[0])
 
 
-def test_bench_two_ranks_share_one_gpu_weak():
-    """`bench.py --gpus 2` as the driver launches it (two ranks, here both on GPU 0): one JSON line, n_gpus 2"""
-    d = _run_bench(2, ["--streams", "32"])
+def test_bench_two_ranks_share_one_gpu_weak(tmp_path):
+    """`bench.py --gpus 2` as the driver launches it (two ranks, here both on GPU 0): one JSON line, n_gpus 2; --dump-outputs
+    writes both ranks' records with global stream numbers"""
+    d = _run_bench(2, ["--streams", "32", "--dump-outputs", str(tmp_path)])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["streams_total"] == 64
+    streams = np.load(tmp_path / "records_stream.npy")
+    assert len(streams) == d["config"]["records_per_step"] and streams.min() < 32 <= streams.max() < 64
     assert d["value"] > 0 and d["config"]["fallbacks"] == 0 and d["config"]["records_per_step"] > 0
     assert d["parity"]["streams_checked"] == 4 and d["parity"]["streams_mismatched"] == 0  # first + last of both shards
     assert "cpu_baseline" not in d  # rank 0 at N = 1 only
@@ -234,7 +237,7 @@ def test_bench_other_configs_block_is_timed_in_the_same_run(monkeypatch):
     env = dict(os.environ, RT_BENCH_OTHER_CONFIGS_JSON=env_cfg)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--settle", "2", "--isolated-steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--settle", "2", "--full", "--isolated-steps", "2",
                         "--streams", "32", "--cpu-streams", "4", "--parity-streams", "4", "--other-configs", "on", "--other-steps", "3"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -283,3 +286,34 @@ def test_bench_sharded_configs_block_carries_north_stars_curve():
     import bench
 
     assert [(n, sp["total"]) for n, sp in bench.SHARDED_CONFIGS] == [("config4", 32768), ("config5", 8192)]  # the real block: north_star's populations
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_steps_records(tmp_path):
+    """Without --full a run times exactly --steps steps and prints the headline alone (no parity, baseline, sinks or blocks);
+    --dump-outputs writes the last timed step's records, and two runs with the same arguments write the same arrays"""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--settle", "2",
+                            "--streams", "32", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-3000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "MSamples/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 32 * 8000 * 256 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * d["value"] + 0.1  # value and ms_per_step: one measurement
+        for key in ("parity", "cpu_baseline", "other_configs", "sharded_configs", "single_stream_latency_ms"):
+            assert key not in d, key
+        assert d["host_sinks"] is None
+        files = sorted(p.name for p in out.iterdir())
+        assert files == sorted(f"records_{f}.npy" for f in _native.RECORD_DTYPE.names if f != "reserved"), files
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert len({len(a) for a in arrs.values()}) == 1 and len(arrs["records_stream.npy"]) == d["config"]["records_per_step"] > 0
+        assert np.all(np.diff(arrs["records_stream.npy"]) >= 0) and arrs["records_stream.npy"].max() < 32
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert dumps[0][f].tobytes() == dumps[1][f].tobytes(), f
