@@ -290,6 +290,62 @@ int rt_get_call_info(rt_handle *h, rt_call_info *info);
 /* Message of the last error on this handle (or of the last failed rt_create if h == NULL). */
 const char *rt_last_error(rt_handle *h);
 
+/*
+ * ---- float64 handles (additive within ABI version 6) ----
+ * pyrtlsdr delivers complex128 buffers and the reference then runs the whole path in float64 (SciPy keeps the input
+ * dtype; thresholds and statistics are Python floats).  A handle made by rt_create_f64 does the same on the
+ * GPU: the dense map in double precision, thresholds and statistics in float64.  Its limits:
+ *   - dense path only: RT_MODE_AUTO means dense (rt_call_info.mode_used = RT_MODE_DENSE); RT_MODE_SPARSE,
+ *     RT_MODE_PREFILTER and RT_MODE_RUNFILTER are RT_E_UNSUPPORTED;
+ *   - nperseg 8 ... 4096, or a power of two up to 8192 (a segment's transform in LDS: Bluestein's padded length M <= 8192
+ *     complex doubles = 128 KiB); anything else is RT_E_UNSUPPORTED;
+ *   - cfg->lanes must be 0 or 1 (RT_E_UNSUPPORTED otherwise): one launch sequence per call;
+ *   - the native sinks of rt_format.h / rt_match.h take float32 rt_record arrays only.
+ * rt_process / rt_process_host take complex128 (interleaved float64 I,Q; 16-byte aligned) on such a handle;
+ * rt_process_u8 / rt_process_u8_host take the wire format and convert it as pyrtlsdr does, (double)b / 127.5 - 1.0.
+ * Every other rt_config field keeps its meaning (two calls in flight, record_capacity a starting size that grows,
+ * rt_reset / rt_reset_stream, hip_stream); the float32 fields window / scale / threshold / snr_threshold /
+ * calibration_db are replaced by rt_config_f64.  A float32 entry point that has a float64 twin (rt_fetch,
+ * rt_set_stream_params, rt_extract, rt_spectrogram), or rt_calibrate_read, on a float64 handle -- and each twin on a
+ * float32 handle -- is RT_E_INVALID, refused before anything is launched.
+ */
+typedef struct rt_config_f64 {
+    const double *window;   /* host pointer, nperseg float64 coefficients                         */
+    double scale;           /* 1/(fs*sum(w*w)) in float64 (_spectral_py.py:2087)                  */
+    double threshold;       /* signal_threshold, linear (analyze.py:115), never rounded to float32 */
+    double snr_threshold;   /* snr_threshold, linear (analyze.py:116)                             */
+    double calibration_db;  /* only used to order maxima in the shadow filter                     */
+} rt_config_f64;
+
+/* rt_record with float64 figures (56 bytes) */
+typedef struct rt_record_f64 {
+    int32_t stream, fi, start, end; /* as in rt_record                                     */
+    double max_p;                   /* max(data), linear                                   */
+    double mean_p;                  /* mean(data), linear                                  */
+    double std_db;                  /* std(10*log10(data)), population                     */
+    double row_mean;                /* mean of the bin's row over the whole buffer         */
+    int32_t shadowed;               /* 1 if filter_shadow_signals drops it                 */
+    int32_t reserved;
+} rt_record_f64;
+
+/* Create a float64 handle.  `cfg` as for rt_create except its float32 window / scale / thresholds / calibration, which
+ * `f64` replaces.  Arguments are checked before any device is touched; RT_E_NOMEM when the float64 map
+ * (n_streams * (max_samples / nperseg) * nperseg * 8 bytes) does not fit. */
+int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **out);
+
+/* rt_fetch of a float64 handle: the same contract, float64 records. */
+int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out);
+
+/* rt_set_stream_params of a float64 handle: HOST arrays of n_streams float64 (either may be NULL). */
+int rt_set_stream_params_f64(rt_handle *h, const double *threshold, const double *calibration_db);
+
+/* rt_extract of a float64 handle: `spec_dev` / `last_dev` are DEVICE pointers to [S][n_seg][n_bins] float64. */
+int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t n_bins, const double *last_dev,
+                   int32_t n_seg_last);
+
+/* rt_spectrogram of a float64 handle: complex128 `iq_dev` -> [S][T][nperseg] float64 at `spec_dev`.  Synchronous. */
+int rt_spectrogram_f64(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, double *spec_dev);
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

@@ -90,6 +90,37 @@ RECORD_DTYPE = np.dtype(
     ]
 )
 
+class RtConfigF64(C.Structure):
+    """``rt_config_f64``: the float64 window / scale / thresholds / calibration of a float64 handle (``rt_create_f64``)."""
+
+    _fields_ = [
+        ("window", C.POINTER(C.c_double)),
+        ("scale", C.c_double),
+        ("threshold", C.c_double),
+        ("snr_threshold", C.c_double),
+        ("calibration_db", C.c_double),
+    ]
+
+
+#: numpy view of ``rt_record_f64`` (56 bytes): a float64 handle's records
+RECORD_F64_DTYPE = np.dtype(
+    [
+        ("stream", "<i4"),
+        ("fi", "<i4"),
+        ("start", "<i4"),
+        ("end", "<i4"),
+        ("max_p", "<f8"),
+        ("mean_p", "<f8"),
+        ("std_db", "<f8"),
+        ("row_mean", "<f8"),
+        ("shadowed", "<i4"),
+        ("reserved", "<i4"),
+    ]
+)
+
+#: nperseg a float64 handle takes: 8 .. 4096 and the powers of two up to 8192
+SUPPORTED_NPERSEG_F64 = tuple(range(8, 4097)) + (8192,)
+
 #: every symbol include/rt_analyze.h declares
 ABI_SYMBOLS = (
     "rt_abi_version",
@@ -113,6 +144,11 @@ ABI_SYMBOLS = (
     "rt_dev_upload",
     "rt_dev_download",
     "rt_device_count",
+    "rt_create_f64",
+    "rt_fetch_f64",
+    "rt_set_stream_params_f64",
+    "rt_extract_f64",
+    "rt_spectrogram_f64",
 )
 
 _lib = None
@@ -168,6 +204,11 @@ def load_library(path: Optional[str] = None):
     lib.rt_dev_upload.argtypes = [C.c_int32, vp, vp, C.c_size_t]
     lib.rt_dev_download.argtypes = [C.c_int32, vp, vp, C.c_size_t]
     lib.rt_device_count.argtypes = [C.POINTER(C.c_int)]
+    lib.rt_create_f64.argtypes = [C.POINTER(RtConfig), C.POINTER(RtConfigF64), C.POINTER(vp)]
+    lib.rt_fetch_f64.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.rt_set_stream_params_f64.argtypes = [vp, vp, vp]
+    lib.rt_extract_f64.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int32]
+    lib.rt_spectrogram_f64.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -259,10 +300,17 @@ class NativeAnalyzer:
         subtract_first: bool = False,
         record_pool: int = 0,
         group_detect: Optional[bool] = None,
+        precision: str = "float32",
     ):
+        """``precision="float64"``: a float64 handle (``rt_create_f64``) -- ``window_f32`` then holds the float64 window and
+        ``scale`` / ``threshold`` / ``snr_threshold`` / ``calibration_db`` are passed on as float64, never rounded to float32;
+        the analysis takes complex128 (or uint8) IQ and the records are ``RECORD_F64_DTYPE``."""
+        if precision not in ("float32", "float64"):
+            raise ValueError(f"precision must be 'float32' or 'float64', not {precision!r}")
+        self.f64 = precision == "float64"
         self._lib = load_library()
         self._handle = C.c_void_p()
-        w = np.ascontiguousarray(window_f32, dtype=np.float32)
+        w = np.ascontiguousarray(window_f32, dtype=np.float64 if self.f64 else np.float32)
         if w.shape != (nperseg,):
             raise ValueError("window must have nperseg coefficients")
         cfg = RtConfig()
@@ -272,7 +320,7 @@ class NativeAnalyzer:
         cfg.mode = mode
         cfg.max_samples = max_samples
         cfg.sample_rate = float(sample_rate)
-        cfg.window = w.ctypes.data_as(C.POINTER(C.c_float))
+        cfg.window = w.ctypes.data_as(C.POINTER(C.c_float)) if not self.f64 else None
         cfg.scale = float(scale)
         cfg.threshold = float(threshold)
         cfg.snr_threshold = float(snr_threshold)
@@ -287,7 +335,16 @@ class NativeAnalyzer:
         cfg.hip_stream = hip_stream
         cfg.lanes = int(lanes)
         cfg.record_pool = int(record_pool)
-        rc = self._lib.rt_create(C.byref(cfg), C.byref(self._handle))
+        if self.f64:
+            c64 = RtConfigF64()
+            c64.window = w.ctypes.data_as(C.POINTER(C.c_double))
+            c64.scale = float(scale)
+            c64.threshold = float(threshold)
+            c64.snr_threshold = float(snr_threshold)
+            c64.calibration_db = float(calibration_db)
+            rc = self._lib.rt_create_f64(C.byref(cfg), C.byref(c64), C.byref(self._handle))
+        else:
+            rc = self._lib.rt_create(C.byref(cfg), C.byref(self._handle))
         if rc != RT_OK:
             self._handle = C.c_void_p()
             _raise(self._lib, None, rc)
@@ -319,19 +376,22 @@ class NativeAnalyzer:
         self._check(self._lib.rt_reset_stream(self._handle, int(stream)))
 
     def set_stream_params(self, threshold: Optional[np.ndarray], calibration_db: Optional[np.ndarray]):
-        """Per-stream linear thresholds / calibration (float32 ``[S]`` each, or None = the handle's value)."""
+        """Per-stream linear thresholds / calibration (float32 ``[S]`` each -- float64 on a float64 handle --, or None = the
+        handle's value)."""
+        dt = np.float64 if self.f64 else np.float32
 
         def arr(a):
             if a is None:
                 return None
-            a = np.ascontiguousarray(a, dtype=np.float32)
+            a = np.ascontiguousarray(a, dtype=dt)
             if a.shape != (self.n_streams,):
                 raise ValueError(f"expected {self.n_streams} values")
             return a
 
         t, c = arr(threshold), arr(calibration_db)
+        fn = self._lib.rt_set_stream_params_f64 if self.f64 else self._lib.rt_set_stream_params
         self._check(
-            self._lib.rt_set_stream_params(
+            fn(
                 self._handle, t.ctypes.data if t is not None else None, c.ctypes.data if c is not None else None
             )
         )
@@ -344,7 +404,8 @@ class NativeAnalyzer:
         self._check(self._lib.rt_process_u8(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
 
     def process_host(self, iq: np.ndarray):
-        a = np.ascontiguousarray(iq, dtype=np.complex64)
+        """``[S, B]`` complex IQ in host memory: complex64 (complex128 on a float64 handle, where complex64 is widened exactly)."""
+        a = np.ascontiguousarray(iq, dtype=np.complex128 if self.f64 else np.complex64)
         if a.ndim == 1:
             a = a[None, :]
         if a.shape[0] != self.n_streams:
@@ -369,12 +430,13 @@ class NativeAnalyzer:
         raises: an empty array would read as "no signals"."""
         n = C.c_size_t(0)
         self.last_truncated = False
-        rc = self._lib.rt_fetch(self._handle, None, 0, C.byref(n))  # size query: the call stays pending
+        fetch = self._lib.rt_fetch_f64 if self.f64 else self._lib.rt_fetch
+        rc = fetch(self._handle, None, 0, C.byref(n))  # size query: the call stays pending
         if rc != RT_OK and rc != RT_E_CAPACITY:
             self._check(rc)  # incl. RT_E_HOT_OVERFLOW: the library has dropped the call
-        out = np.zeros(n.value, dtype=RECORD_DTYPE)
+        out = np.zeros(n.value, dtype=RECORD_F64_DTYPE if self.f64 else RECORD_DTYPE)
         if n.value:
-            rc = self._lib.rt_fetch(self._handle, out.ctypes.data, n.value, C.byref(n))
+            rc = fetch(self._handle, out.ctypes.data, n.value, C.byref(n))
         if rc == RT_E_CAPACITY:
             self.last_truncated = True
         if rc != RT_OK and not (allow_truncated and rc == RT_E_CAPACITY):
@@ -382,10 +444,14 @@ class NativeAnalyzer:
         return out
 
     def extract_device(self, spec_ptr: int, n_seg: int, n_bins: int, last_ptr: Optional[int], n_seg_last: int):
-        self._check(self._lib.rt_extract(self._handle, spec_ptr, n_seg, n_bins, last_ptr, n_seg_last))
+        """``rt_extract`` (float32 maps), or ``rt_extract_f64`` (float64 maps) on a float64 handle."""
+        fn = self._lib.rt_extract_f64 if self.f64 else self._lib.rt_extract
+        self._check(fn(self._handle, spec_ptr, n_seg, n_bins, last_ptr, n_seg_last))
 
     def spectrogram_device(self, iq_ptr: int, n_samples: int, stream_stride: int, out_ptr: int):
-        self._check(self._lib.rt_spectrogram(self._handle, iq_ptr, n_samples, stream_stride, out_ptr))
+        """``rt_spectrogram`` (complex64 -> float32), or ``rt_spectrogram_f64`` (complex128 -> float64) on a float64 handle."""
+        fn = self._lib.rt_spectrogram_f64 if self.f64 else self._lib.rt_spectrogram
+        self._check(fn(self._handle, iq_ptr, n_samples, stream_stride, out_ptr))
 
     def calibrate_read(self, iq_ptr: int, n_samples: int, stream_stride: int):
         self._check(self._lib.rt_calibrate_read(self._handle, iq_ptr, n_samples, stream_stride))

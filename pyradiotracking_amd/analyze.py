@@ -61,6 +61,18 @@ def stft_constants(fft_window, nperseg: int, sample_rate):
     return np.ascontiguousarray(win.real, dtype=np.float32), np.float32(scale.real)
 
 
+def stft_constants_f64(fft_window, nperseg: int, sample_rate):
+    """float64 window and PSD scale as SciPy forms them for complex128 input (_spectral_py.py:2083-2087): the float64
+    window is kept (its result type with complex64 is already complex128) and ``scale = 1/(fs * sum(win*win))`` is a
+    float64 figure."""
+    win = np.asarray(window_coefficients(fft_window, nperseg), dtype=np.float64)
+    scale = 1.0 / (sample_rate * (win * win).sum())
+    return np.ascontiguousarray(win), float(scale)
+
+
+PRECISIONS = ("float32", "float64")
+
+
 class _Heartbeat:
     """Stand-in for the ``multiprocessing.Value("d")`` the reference's Runner hands to every analyzer."""
 
@@ -71,9 +83,11 @@ class _Heartbeat:
 class _RecordDecoder:
     """rt_record arrays -> Signal field columns (analyze.py:360, 420-449)."""
 
-    def __init__(self, nperseg: int, sample_rate, center_freq, calibration_db):
+    def __init__(self, nperseg: int, sample_rate, center_freq, calibration_db, f64: bool = False):
         """``calibration_db``: one value, or one per stream (the reference has one analyzer and one
-        calibration per SDR, __main__.py:140-141)."""
+        calibration per SDR, __main__.py:140-141).  ``f64``: the records are float64 (a float64 handle), and so are the
+        calibrations subtracted from them."""
+        self.f64 = f64
         self.nperseg = nperseg
         self.sample_rate = sample_rate
         self.center_freq = center_freq
@@ -99,7 +113,7 @@ class _RecordDecoder:
         if np.ndim(cal):
             # float32 dB figure minus a Python float is a float32 subtraction (NEP 50): the same bits as
             # subtracting the calibration rounded to float32
-            cal = np.asarray(cal, dtype=np.float32)[rec["stream"]]
+            cal = np.asarray(cal, dtype=np.float64 if self.f64 else np.float32)[rec["stream"]]
         with np.errstate(divide="ignore", invalid="ignore"):
             max_dbw = dB(rec["max_p"]) - cal  # float32, analyze.py:442
             avg_dbw = dB(rec["mean_p"]) - cal  # :444
@@ -254,9 +268,17 @@ class BatchSignalAnalyzer:
         subtract_first: bool = False,
         record_pool: int = 0,
         group_detect: Optional[bool] = None,
+        precision: str = "float32",
         **kwargs,
     ):
-        """``mode`` (``rt_config.mode``): ``"auto"`` (default) analyses on the fused sparse path and, when an input's noise
+        """``precision``: ``"float32"`` (default) analyses complex64; ``"float64"`` runs the reference's float64 arithmetic on
+        complex128 buffers (what pyrtlsdr delivers) -- float64 window, scale, thresholds, map and statistics
+        (``rt_create_f64``).  A float64 analyzer runs the dense path only (``mode`` ``"auto"`` or ``"dense"``), nperseg 8 ...
+        4096 or a power of two up to 8192, one lane; ``enqueue`` takes complex128 device tensors, host complex arrays
+        (complex64 widened exactly) and uint8 (converted as pyrtlsdr does, in float64); ``fetch_records`` returns
+        ``RECORD_F64_DTYPE``.
+
+        ``mode`` (``rt_config.mode``): ``"auto"`` (default) analyses on the fused sparse path and, when an input's noise
         crosses the thresholds, climbs by itself -- chunk-bit pre-filter, exact SNR-aware pre-filter, dense spectrogram; the
         records are the same on every level.  ``"sparse"``, ``"prefilter"``, ``"runfilter"`` and
         ``"dense"`` pin one level (the first three refuse an input they cannot hold with ``RT_E_HOT_OVERFLOW``).
@@ -283,6 +305,10 @@ class BatchSignalAnalyzer:
         ``calibration_db`` may be a sequence with one value per stream: every SDR of the reference has its own
         analyzer and calibration (``__main__.py:140-141``), and with it its own absolute threshold
         (``analyze.py:115``); the kernels then take the thresholds per stream (``rt_set_stream_params``)."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+        self.precision = precision
+        f64 = precision == "float64"
         self.devices = [str(d) for d in devices]
         per_stream_cal = None
         if np.ndim(calibration_db):
@@ -303,9 +329,12 @@ class BatchSignalAnalyzer:
         self.signal_threshold = from_dB(signal_threshold_dbw + calibration_db)  # :115
         self.snr_threshold = from_dB(snr_threshold_db)  # :116
 
-        win32, scale32 = stft_constants(fft_window, fft_nperseg, sample_rate)
+        if f64:
+            win32, scale32 = stft_constants_f64(fft_window, fft_nperseg, sample_rate)
+        else:
+            win32, scale32 = stft_constants(fft_window, fft_nperseg, sample_rate)
         if lanes == "auto":
-            lanes = 1 if hip_stream is not None else default_lanes(fft_nperseg, len(self.devices))
+            lanes = 1 if (hip_stream is not None or f64) else default_lanes(fft_nperseg, len(self.devices))
         if int(lanes) > 1 and hip_stream is not None:
             raise ValueError("lanes > 1 run on their own HIP streams: pass hip_stream=None")
         self._native = _native.NativeAnalyzer(
@@ -315,9 +344,9 @@ class BatchSignalAnalyzer:
             sample_rate=sample_rate,
             window_f32=win32,
             scale=float(scale32),
-            # thresholds are compared against float32 data in float32
-            threshold=float(np.float32(self.signal_threshold)),
-            snr_threshold=float(np.float32(self.snr_threshold)),
+            # thresholds are compared against float32 data in float32; a float64 handle keeps the Python floats
+            threshold=float(self.signal_threshold) if f64 else float(np.float32(self.signal_threshold)),
+            snr_threshold=float(self.snr_threshold) if f64 else float(np.float32(self.snr_threshold)),
             calibration_db=calibration_db,
             min_duration_s=self.signal_min_duration,
             max_duration_s=self.signal_max_duration,
@@ -333,14 +362,18 @@ class BatchSignalAnalyzer:
             subtract_first=bool(subtract_first),
             record_pool=int(record_pool),
             group_detect=group_detect,
+            precision=precision,
         )
         if per_stream_cal is not None:
             self.calibration_db = per_stream_cal
             self.signal_threshold = [from_dB(signal_threshold_dbw + c) for c in per_stream_cal]  # :115, per SDR
-            self._native.set_stream_params(
-                np.array(self.signal_threshold, dtype=np.float64).astype(np.float32), np.array(per_stream_cal, dtype=np.float32)
-            )
-        self._decoder = _RecordDecoder(fft_nperseg, sample_rate, center_freq, self.calibration_db)
+            if f64:
+                self._native.set_stream_params(np.array(self.signal_threshold, dtype=np.float64), np.array(per_stream_cal, dtype=np.float64))
+            else:
+                self._native.set_stream_params(
+                    np.array(self.signal_threshold, dtype=np.float64).astype(np.float32), np.array(per_stream_cal, dtype=np.float32)
+                )
+        self._decoder = _RecordDecoder(fft_nperseg, sample_rate, center_freq, self.calibration_db, f64=f64)
         self.decoder = self._decoder  # record -> field conversion, shared with pyradiotracking_amd.match
         self.gpu = gpu
         self._hip_stream = hip_stream
@@ -396,7 +429,7 @@ class BatchSignalAnalyzer:
         if isinstance(iq, int):
             if n_samples is None:
                 raise ValueError("n_samples is required with a raw device pointer")
-            self._process_device(iq, n_samples, stream_stride, 8, False)
+            self._process_device(iq, n_samples, stream_stride, 16 if self.precision == "float64" else 8, False)
             return
         if isinstance(iq, np.ndarray) and iq.dtype == np.uint8:
             self.enqueue_bytes(iq)
@@ -410,8 +443,9 @@ class BatchSignalAnalyzer:
         if not iq.is_cuda:
             self.enqueue(iq.numpy())
             return
-        if str(iq.dtype) != "torch.complex64":
-            raise TypeError("device IQ must be complex64")
+        want = "torch.complex128" if self.precision == "float64" else "torch.complex64"
+        if str(iq.dtype) != want:
+            raise TypeError(f"device IQ must be {want[6:]}" + (" on a float64 analyzer" if self.precision == "float64" else ""))
         if iq.shape[0] != len(self.devices) or iq.stride(1) != 1:
             raise ValueError("device IQ must be [S, B] with unit sample stride")
         self._hold(iq)
@@ -421,7 +455,7 @@ class BatchSignalAnalyzer:
             import torch
 
             torch.cuda.current_stream(iq.device).synchronize()
-        self._process_device(iq.data_ptr(), iq.shape[1], iq.stride(0) if iq.shape[0] > 1 else iq.shape[1], 8, False)
+        self._process_device(iq.data_ptr(), iq.shape[1], iq.stride(0) if iq.shape[0] > 1 else iq.shape[1], iq.element_size(), False)
 
     def enqueue_bytes(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None):
         """Same as :meth:`enqueue` for the RTL-SDR wire format: interleaved uint8 I, Q (what
@@ -522,9 +556,12 @@ class SignalAnalyzer:
         last_data_ts=None,
         gpu: int = 0,
         mode: str = "auto",
+        precision: str = "float32",
         **kwargs,
     ):
+        """``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer)."""
         self.device = device
+        self.precision = precision
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -572,6 +609,7 @@ class SignalAnalyzer:
             sdr_callback_length=sdr_callback_length,
             gpu=gpu,
             mode=mode,
+            precision=precision,
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
             **{k: kwargs[k] for k in ("record_capacity", "record_pool", "hot_capacity", "group_detect") if k in kwargs},
         )
@@ -617,7 +655,8 @@ class SignalAnalyzer:
     def process_samples(self, buffer: np.ndarray, context=None):
         """Analyse one buffer; state messages and detected signals go to ``signal_queue`` in the
         reference's order.  complex128 buffers (what pyrtlsdr delivers) are analysed in complex64 --
-        the GPU path is single precision.  The SIGALRM watchdog of the reference
+        unless the analyzer was made with ``precision="float64"``, which analyses them in float64 as the reference
+        does.  The SIGALRM watchdog of the reference
         (analyze.py:208) belongs to the process that owns the SDR and is not re-armed here."""
         ts_start = self._clock(len(buffer))
         filtered = self.analyze_buffer(buffer, ts_start)
@@ -643,7 +682,7 @@ class SignalAnalyzer:
     def analyze_buffer(self, buffer: np.ndarray, ts_start: datetime.datetime, filtered: bool = True) -> List[Signal]:
         """analyze.py:234-248 and :268 with an explicit ``ts_start``."""
         bench_start = time.time()
-        buf = np.ascontiguousarray(buffer, dtype=np.complex64).reshape(1, -1)
+        buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         out = self._batch.process_batch(buf, [ts_start], filtered=filtered, lazy=False)[0]  # (one stream: its Signal objects, as the reference returns them)
@@ -682,13 +721,14 @@ class SignalAnalyzer:
             if not np.isclose(times[1] - times[0], hop, rtol=1e-9, atol=0.0):
                 raise ValueError("times does not match fft_nperseg / sample_rate")
         nat = self._batch.native
-        seg_major = np.ascontiguousarray(spec.T, dtype=np.float32)
+        sdt = np.float64 if self.precision == "float64" else np.float32  # (a float64 analyzer: rt_extract_f64)
+        seg_major = np.ascontiguousarray(spec.T, dtype=sdt)
         d_spec = _native.DeviceBuffer(self._batch.gpu, max(4, seg_major.nbytes))
         d_spec.upload(seg_major)
         d_last = None
         n_last = 0
         if self._spectrogram_last is not None:
-            last = np.ascontiguousarray(np.asarray(self._spectrogram_last).T, dtype=np.float32)
+            last = np.ascontiguousarray(np.asarray(self._spectrogram_last).T, dtype=sdt)
             n_last = last.shape[0]
             d_last = _native.DeviceBuffer(self._batch.gpu, max(4, last.nbytes))
             d_last.upload(last)

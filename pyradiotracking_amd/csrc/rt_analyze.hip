@@ -29,6 +29,7 @@
 
 #include "rt_kernels.h"
 #include "rt_general.h"
+#include "rt_f64.h"
 
 using namespace rt;
 
@@ -116,6 +117,47 @@ struct Slot {
     unsigned long long *h_total = nullptr;                     // pinned: records allocated so far, uploaded before a partial re-run
     hipEvent_t ev_begin = nullptr, ev_first = nullptr, ev_scan = nullptr, ev_done = nullptr;  // first launch; end of the first scan; end of the scans; end of the call
     CallCtx call;
+};
+
+// A float64 handle (rt_create_f64; kernels: rt_f64.h).  Its own two call slots, three look-back tails in rotation as on the
+// float32 path, one float64 map shared by the calls (a call analysed again -- its records outgrew the capacity -- runs its
+// transform again from its IQ, which stays valid until the call is fetched).
+struct F64Slot {
+    bool pending = false;
+    uint64_t seq = 0;
+    bool is_extract = false, u8 = false, no_last = false;
+    const void *iq = nullptr;  // device IQ of the call (the caller's, or d_stage)
+    int64_t stream_stride = 0;
+    int n_seg = 0, n_seg_last = -1, tail_read = 0, tail_write = 0;
+    const double *ex_spec = nullptr, *ex_last = nullptr;  // rt_extract_f64
+    int ex_bins = 0, ex_last_cols = 0;
+    int rec_cap = 0;                                   // records per stream the slot's areas hold
+    rt_record_f64 *d_raw = nullptr;                    // [S][rec_cap]
+    int32_t *d_raw_count = nullptr;                    // [S]
+    int32_t *d_no_last = nullptr;                      // [S]
+    std::vector<int32_t> no_last_h;
+    rt_record_f64 *h_out = nullptr;                    // pinned, device-visible: [S * rec_cap] the call's records
+    int32_t *h_meta = nullptr;                         // pinned, device-visible: [S + 1] offsets + total, then [S] wanted
+    void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host
+    size_t stage_bytes = 0;
+    hipEvent_t ev_done = nullptr;
+};
+struct F64State {
+    rt_config_f64 c{};
+    int N = 0, M = 0, log2m = 0, SPB = 1, K = 1, stride = 1, max_seg = 0;
+    bool blu = false;
+    double *d_window = nullptr;
+    cd *d_cwin = nullptr, *d_bfilt = nullptr, *d_tw = nullptr;
+    double *d_map = nullptr;
+    double *d_tail[kTails] = {nullptr, nullptr, nullptr};
+    int tail_cur = 0, n_seg_last = -1;
+    double *d_thr_s = nullptr, *d_cal_s = nullptr;
+    std::vector<double> h_thr_s;
+    std::vector<uint8_t> reset_pending;
+    bool any_reset = false;
+    int rec_cap = 1024;
+    uint64_t n_calls = 0;
+    F64Slot slot[kSlots];
 };
 
 }  // namespace
@@ -208,6 +250,8 @@ struct rt_handle {
     // HIP stream) and forwards every call to them; kid k analyses streams [kid_base[k], kid_base[k + 1])
     std::vector<rt_handle *> kids;
     std::vector<int> kid_base;
+
+    F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
 };
 
 namespace {
@@ -1086,8 +1130,14 @@ int rt_device_count(int *count) {
 
 const char *rt_last_error(rt_handle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+static void destroy_f64(rt_handle *h);
+
 void rt_destroy(rt_handle *h) {
     if (!h) return;
+    if (h->f64) {
+        destroy_f64(h);
+        return;
+    }
     if (!h->kids.empty()) {
         for (rt_handle *k : h->kids) rt_destroy(k);
         delete h;
@@ -1688,6 +1738,12 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
 
 int rt_reset(rt_handle *h) {
     if (!h) return RT_E_INVALID;
+    if (h->f64) {
+        h->f64->n_seg_last = -1;
+        std::fill(h->f64->reset_pending.begin(), h->f64->reset_pending.end(), (uint8_t)0);
+        h->f64->any_reset = false;
+        return RT_OK;
+    }
     for (rt_handle *k : h->kids) rt_reset(k);
     h->n_seg_last = -1;
     std::fill(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)0);
@@ -1701,6 +1757,11 @@ int rt_reset_stream(rt_handle *h, int32_t stream) {
         h->err = "stream index out of range";
         return RT_E_INVALID;
     }
+    if (h->f64) {
+        h->f64->reset_pending[(size_t)stream] = 1;
+        h->f64->any_reset = true;
+        return RT_OK;
+    }
     if (!h->kids.empty()) {
         for (size_t k = 0; k < h->kids.size(); ++k)
             if (stream < h->kid_base[k + 1]) return rt_reset_stream(h->kids[k], stream - h->kid_base[k]);
@@ -1711,8 +1772,14 @@ int rt_reset_stream(rt_handle *h, int32_t stream) {
     return RT_OK;
 }
 
+static int refuse_on_f64(rt_handle *h, const char *what, const char *twin) {
+    h->err = std::string(what) + " on a float64 handle (rt_create_f64): " + (twin ? std::string("use ") + twin : std::string("not available"));
+    return RT_E_INVALID;
+}
+
 int rt_set_stream_params(rt_handle *h, const float *threshold, const float *calibration_db) {
     if (!h) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_set_stream_params", "rt_set_stream_params_f64");
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
             return rt_set_stream_params(k, threshold ? threshold + s0 : nullptr, calibration_db ? calibration_db + s0 : nullptr);
@@ -1765,8 +1832,11 @@ int rt_process_u8(rt_handle *h, const void *iq_u8_dev, int64_t n_samples, int64_
     return process_impl(h, iq_u8_dev, n_samples, stream_stride, true);
 }
 
+static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, bool u8, bool host);
+
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, bool u8) {
     if (!h) return RT_E_INVALID;
+    if (h->f64) return process_f64(h, iq_dev, n_samples, stream_stride, u8, false);
     if (!h->kids.empty()) {
         const int64_t bytes = u8 ? 2 : (int64_t)sizeof(cf);
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
@@ -1886,6 +1956,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
 
 static int process_host_impl(rt_handle *h, const void *iq_host, int64_t n_samples, int64_t stream_stride, bool u8) {
     if (!h) return RT_E_INVALID;
+    if (h->f64) return process_f64(h, iq_host, n_samples, stream_stride, u8, true);
     const size_t sample_bytes = u8 ? 2 : sizeof(cf);
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
@@ -1931,6 +2002,7 @@ int rt_process_u8_host(rt_handle *h, const void *iq_u8_host, int64_t n_samples, 
 int rt_extract(rt_handle *h, const float *spec_dev, int32_t n_seg, int32_t n_bins, const float *last_dev,
                int32_t n_seg_last) {
     if (!h) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_extract", "rt_extract_f64");
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
             const float *sp = spec_dev ? spec_dev + s0 * n_seg * n_bins : nullptr;
@@ -2289,6 +2361,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
 
 int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
     if (!h || !n_out) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_fetch", "rt_fetch_f64");
     if (h->kids.empty()) return fetch_one(h, out, cap, n_out, false);
     // lanes: size every lane first (a size query must leave all of them pending), then deliver in
     // stream order with the lane's first stream added to the records' stream index
@@ -2354,6 +2427,7 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
 
 int rt_spectrogram(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, float *spec_dev) {
     if (!h || !iq_dev || !spec_dev) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_spectrogram", "rt_spectrogram_f64");
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
             const int64_t T = n_samples / k->N;
@@ -2385,6 +2459,7 @@ int rt_spectrogram(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t 
 
 int rt_calibrate_read(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride) {
     if (!h || !iq_dev) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_calibrate_read", nullptr);
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
             return rt_calibrate_read(k, static_cast<const char *>(iq_dev) + s0 * stream_stride * (int64_t)sizeof(cf), n_samples,
@@ -2440,6 +2515,562 @@ int rt_dev_download(int32_t device, void *dst_host, const void *src_dev, size_t 
     if (hipSetDevice(device) != hipSuccess) return fail_create(RT_E_NO_DEVICE, "hipSetDevice failed");
     hipError_t e = hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost);
     return e == hipSuccess ? RT_OK : fail_create(RT_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+}
+
+}  // extern "C"
+
+// ---- float64 handles (include/rt_analyze.h: rt_create_f64; kernels: rt_f64.h) ----
+namespace {
+
+// W_M^j = exp(-2 pi i j / M), j < M / 2, and the chirp w[n] = exp(-i pi n^2 / N) with n^2 reduced mod 2 N in integers: sin / cos
+// in long double, rounded once to double
+constexpr long double kPiL = 3.141592653589793238462643383279502884L;
+cd f64_expi(long double a) { return cd{(double)cosl(a), (double)sinl(a)}; }
+
+// FFT_M in long double on the host (iterative radix-2): the transform of Bluestein's chirp filter
+void host_fft_ld(std::vector<long double> &re, std::vector<long double> &im) {
+    const size_t M = re.size();
+    for (size_t i = 1, j = 0; i < M; ++i) {
+        size_t bit = M >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) {
+            std::swap(re[i], re[j]);
+            std::swap(im[i], im[j]);
+        }
+    }
+    for (size_t len = 2; len <= M; len <<= 1)
+        for (size_t i = 0; i < M; i += len)
+            for (size_t k = 0; k < len / 2; ++k) {
+                const long double a = -2.0L * kPiL * (long double)k / (long double)len;
+                const long double wr = cosl(a), wi = sinl(a);
+                const size_t u = i + k, v = i + k + len / 2;
+                const long double xr = re[v] * wr - im[v] * wi, xi = re[v] * wi + im[v] * wr;
+                re[v] = re[u] - xr;
+                im[v] = im[u] - xi;
+                re[u] += xr;
+                im[u] += xi;
+            }
+}
+
+int f64_err(rt_handle *h, int code, const std::string &msg) {
+    h->err = msg;
+    return code;
+}
+
+F64Slot *f64_oldest(F64State *f) {
+    F64Slot *best = nullptr;
+    for (F64Slot &sl : f->slot)
+        if (sl.pending && (!best || sl.seq < best->seq)) best = &sl;
+    return best;
+}
+
+// a slot for the next call: a free one, else the older pending call is dropped (a third call without a fetch)
+F64Slot &f64_claim(F64State *f) {
+    for (F64Slot &sl : f->slot)
+        if (!sl.pending) return sl;
+    F64Slot *o = f64_oldest(f);
+    o->pending = false;
+    return *o;
+}
+
+// a slot's record areas for `cap` records per stream (a slot holds no call while this runs)
+int f64_slot_areas(rt_handle *h, F64Slot &sl, int cap) {
+    const size_t S = (size_t)h->cfg.n_streams;
+    if (h->s_scan) (void)hipStreamSynchronize(h->s_scan);  // (a dropped call of the slot may still be writing them)
+    (void)hipFree(sl.d_raw);
+    (void)hipHostFree(sl.h_out);
+    sl.d_raw = nullptr;
+    sl.h_out = nullptr;
+    sl.rec_cap = 0;
+    if (hipMalloc(&sl.d_raw, S * (size_t)cap * sizeof(rt_record_f64)) != hipSuccess ||
+        hipHostMalloc(&sl.h_out, S * (size_t)cap * sizeof(rt_record_f64)) != hipSuccess) {
+        (void)hipGetLastError();
+        return f64_err(h, RT_E_NOMEM, "float64 handle: no memory for " + std::to_string(cap) + " records per stream");
+    }
+    sl.rec_cap = cap;
+    return RT_OK;
+}
+
+F64DetectArgs f64_detect_args(rt_handle *h, F64Slot &sl) {
+    F64State *f = h->f64;
+    F64DetectArgs a{};
+    a.dp.n_seg = sl.n_seg;
+    a.dp.stride = f->stride;
+    a.dp.nperseg = f->N;
+    a.dp.thr = f->c.threshold;
+    a.dp.snr = f->c.snr_threshold;
+    a.dp.cal_db = f->c.calibration_db;
+    a.dp.fs = h->cfg.sample_rate;
+    a.dp.min_d = h->cfg.min_duration_s;
+    a.dp.max_d = h->cfg.max_duration_s;
+    a.n_streams = h->cfg.n_streams;
+    if (sl.is_extract) {
+        a.spec = sl.ex_spec;
+        a.n_bins = sl.ex_bins;
+        a.prev = sl.ex_last;
+        a.prev_cols = sl.ex_last_cols;
+        a.dp.n_seg_last = sl.ex_last ? sl.ex_last_cols : -1;
+        a.dp.tail_cols = sl.ex_last ? sl.ex_last_cols : 0;  // the whole previous spectrogram (the reference's unlimited look-back)
+    } else {
+        a.spec = f->d_map;
+        a.n_bins = f->N;
+        a.prev = f->d_tail[sl.tail_read];
+        a.prev_cols = f->K;
+        a.dp.n_seg_last = sl.n_seg_last;
+        a.dp.tail_cols = sl.n_seg_last < 0 ? 0 : std::min(f->K, sl.n_seg_last);
+        a.no_last = sl.no_last ? sl.d_no_last : nullptr;
+    }
+    a.thr_s = f->d_thr_s;
+    a.cal_s = f->d_cal_s;
+    a.raw = sl.d_raw;
+    a.raw_count = sl.d_raw_count;
+    a.rec_cap = sl.rec_cap;
+    a.out = sl.h_out;
+    a.out_off = sl.h_meta;
+    a.out_count = sl.h_meta + h->cfg.n_streams + 1;
+    return a;
+}
+
+// the call's kernels on the handle's stream: the transform (not for rt_extract_f64), detection, records, then the call's event
+int f64_enqueue(rt_handle *h, F64Slot &sl) {
+    F64State *f = h->f64;
+    const int S = h->cfg.n_streams;
+    hipStream_t st = h->s_scan;
+    if (!sl.is_extract && sl.n_seg > 0) {
+        F64StftParams p{};
+        p.iq = sl.iq;
+        p.stream_stride = sl.stream_stride;
+        p.n_streams = S;
+        p.n_seg = sl.n_seg;
+        p.nperseg = f->N;
+        p.m = f->M;
+        p.log2m = f->log2m;
+        p.segs_per_block = f->SPB;
+        p.tail_cols = f->K;
+        p.scale = f->c.scale;
+        p.window = f->d_window;
+        p.cwin = f->d_cwin;
+        p.bfilt = f->d_bfilt;
+        p.tw = f->d_tw;
+        p.spec = f->d_map;
+        p.tail = f->d_tail[sl.tail_write];
+        const int64_t grid = (int64_t)S * ((sl.n_seg + f->SPB - 1) / f->SPB);
+        const size_t lds = (size_t)f->SPB * f->M * sizeof(cd);
+        if (sl.u8) {
+            if (f->blu) stft_f64<true, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            else stft_f64<true, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+        } else {
+            if (f->blu) stft_f64<false, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            else stft_f64<false, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+        }
+        RT_HIP(h, hipGetLastError());
+    }
+    const F64DetectArgs a = f64_detect_args(h, sl);
+    const int64_t rows = (int64_t)S * a.n_bins;
+    detect_f64<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(a);
+    finalize_f64<<<(unsigned)S, 256, 0, st>>>(a);
+    clear_counts_f64<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(sl.d_raw_count, S);
+    RT_HIP(h, hipGetLastError());
+    RT_HIP(h, hipEventRecord(sl.ev_done, st));
+    return RT_OK;
+}
+
+int f64_start(rt_handle *h, F64Slot &sl) {
+    F64State *f = h->f64;
+    if (sl.rec_cap < f->rec_cap) {  // (another call grew the capacity since this slot's areas were made)
+        const int rc = f64_slot_areas(h, sl, f->rec_cap);
+        if (rc != RT_OK) return rc;
+    }
+    const int rc = f64_enqueue(h, sl);
+    if (rc != RT_OK) return rc;
+    sl.seq = ++f->n_calls;
+    sl.pending = true;
+    return RT_OK;
+}
+
+}  // namespace
+
+static void destroy_f64(rt_handle *h) {
+    F64State *f = h->f64;
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipDeviceSynchronize();
+    for (F64Slot &sl : f->slot) {
+        (void)hipFree(sl.d_raw);
+        (void)hipFree(sl.d_raw_count);
+        (void)hipFree(sl.d_no_last);
+        (void)hipFree(sl.d_stage);
+        (void)hipHostFree(sl.h_out);
+        (void)hipHostFree(sl.h_meta);
+        if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
+    }
+    (void)hipFree(f->d_window);
+    (void)hipFree(f->d_cwin);
+    (void)hipFree(f->d_bfilt);
+    (void)hipFree(f->d_tw);
+    (void)hipFree(f->d_map);
+    for (double *t : f->d_tail) (void)hipFree(t);
+    (void)hipFree(f->d_thr_s);
+    (void)hipFree(f->d_cal_s);
+    if (h->own_scan_stream && h->s_scan) (void)hipStreamDestroy(h->s_scan);
+    delete f;
+    h->f64 = nullptr;
+    delete h;
+}
+
+static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, bool u8, bool host) {
+    F64State *f = h->f64;
+    if (!iq && n_samples > 0) return f64_err(h, RT_E_INVALID, "null IQ pointer");
+    if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples)
+        return f64_err(h, RT_E_INVALID, "n_samples/stream_stride out of range for this handle");
+    if (!host && reinterpret_cast<uintptr_t>(iq) % (u8 ? 2u : 16u) != 0)
+        return f64_err(h, RT_E_INVALID, u8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)" : "IQ pointer must be 16-byte aligned (complex128 on a float64 handle)");
+    const int T = (int)(n_samples / f->N);
+    if (T == 1) return f64_err(h, RT_E_ONE_SEGMENT, "exactly one segment: the reference raises IndexError (times[1])");
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    const int S = h->cfg.n_streams;
+    F64Slot &sl = f64_claim(f);
+    sl.pending = false;
+    sl.is_extract = false;
+    sl.u8 = u8;
+    sl.stream_stride = stream_stride;
+    sl.n_seg = T;
+    sl.n_seg_last = f->n_seg_last;
+    sl.tail_read = f->tail_cur;
+    sl.tail_write = (f->tail_cur + 1) % kTails;
+    sl.iq = iq;
+    if (host && n_samples > 0) {
+        const size_t bytes = (size_t)S * (size_t)stream_stride * (u8 ? 2u : 16u);
+        if (sl.stage_bytes < bytes) {
+            RT_HIP(h, hipStreamSynchronize(h->s_scan));  // (the slot's last call may still read its staging buffer)
+            (void)hipFree(sl.d_stage);
+            sl.d_stage = nullptr;
+            sl.stage_bytes = 0;
+            if (hipMalloc(&sl.d_stage, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return f64_err(h, RT_E_NOMEM, "no device memory to stage the IQ");
+            }
+            sl.stage_bytes = bytes;
+        }
+        RT_HIP(h, hipMemcpyAsync(sl.d_stage, iq, bytes, hipMemcpyHostToDevice, h->s_scan));
+        RT_HIP(h, hipStreamSynchronize(h->s_scan));  // (blocking: the caller may reuse its buffer when this returns)
+        sl.iq = sl.d_stage;
+    }
+    sl.no_last = f->any_reset;
+    if (f->any_reset) {
+        sl.no_last_h.assign(f->reset_pending.begin(), f->reset_pending.end());
+        RT_HIP(h, hipMemcpyAsync(sl.d_no_last, sl.no_last_h.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
+        RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    }
+    const int rc = f64_start(h, sl);
+    if (rc != RT_OK) return rc;
+    if (f->any_reset) {
+        std::fill(f->reset_pending.begin(), f->reset_pending.end(), (uint8_t)0);
+        f->any_reset = false;
+    }
+    f->tail_cur = sl.tail_write;
+    f->n_seg_last = T;
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **out) {
+    if (!cfg || !f64 || !out) return fail_create(RT_E_INVALID, "null argument");
+    *out = nullptr;
+    if (cfg->n_streams < 1 || cfg->max_samples < 0 || !f64->window || !(cfg->sample_rate > 0))
+        return fail_create(RT_E_INVALID, "float64 handle: n_streams, max_samples, rt_config_f64.window and sample_rate must be set");
+    if (!(cfg->max_duration_s >= 0) || !(cfg->min_duration_s >= 0)) return fail_create(RT_E_INVALID, "durations must be non-negative");
+    const int n = cfg->nperseg;
+    const bool pow2 = n > 0 && (n & (n - 1)) == 0;
+    if (n < 8 || (pow2 && n > kF64MaxM) || (!pow2 && n > kF64MaxN))
+        return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(n) + " is not supported by a float64 handle: 8 ... 4096, or a power of two up to 8192");
+    if (cfg->mode < RT_MODE_AUTO || cfg->mode > RT_MODE_RUNFILTER) return fail_create(RT_E_INVALID, "bad mode");
+    if (cfg->mode != RT_MODE_AUTO && cfg->mode != RT_MODE_DENSE)
+        return fail_create(RT_E_UNSUPPORTED, "a float64 handle runs the dense path only: mode must be RT_MODE_AUTO or RT_MODE_DENSE");
+    if (cfg->lanes > 1) return fail_create(RT_E_UNSUPPORTED, "a float64 handle has one launch sequence per call: lanes must be 0 or 1");
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return fail_create(RT_E_NO_DEVICE, std::string("no HIP device: ") + (e != hipSuccess ? hipGetErrorString(e) : "count 0"));
+    if (cfg->device < 0 || cfg->device >= ndev) return fail_create(RT_E_INVALID, "device ordinal out of range");
+    e = hipSetDevice(cfg->device);
+    if (e != hipSuccess) return fail_create(RT_E_NO_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+
+    rt_handle *h = new (std::nothrow) rt_handle();
+    F64State *f = new (std::nothrow) F64State();
+    if (!h || !f) {
+        delete h;
+        delete f;
+        return fail_create(RT_E_NOMEM, "out of host memory");
+    }
+    h->f64 = f;
+    h->cfg = *cfg;
+    h->cfg.window = nullptr;
+    h->cfg.mode = RT_MODE_DENSE;
+    h->N = n;
+    f->c = *f64;
+    f->c.window = nullptr;
+    f->N = n;
+    f->blu = !pow2;
+    f->M = 1;
+    while (f->M < (pow2 ? n : 2 * n - 1)) f->M <<= 1;
+    while ((1 << f->log2m) < f->M) ++f->log2m;
+    f->SPB = std::max(1, std::min(64, 1024 / f->M));
+    f->stride = probe_stride(n, cfg->sample_rate, cfg->min_duration_s);
+    {
+        const double hop = seg_time(1, n, cfg->sample_rate) - seg_time(0, n, cfg->sample_rate);
+        const double k = std::floor(cfg->max_duration_s / hop) + 2.0;
+        f->K = (int)std::min(k, 1.0e6);
+        if (f->K < 1) f->K = 1;
+    }
+    f->max_seg = (int)(cfg->max_samples / n);
+    f->rec_cap = cfg->record_capacity > 0 ? cfg->record_capacity : 1024;
+    f->reset_pending.assign((size_t)cfg->n_streams, 0);
+    const size_t S = (size_t)cfg->n_streams;
+#define RT_F64_CREATE(expr)                                                               \
+    do {                                                                                  \
+        hipError_t e_ = (expr);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            const bool oom_ = e_ == hipErrorOutOfMemory;                                  \
+            const std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_);     \
+            (void)hipGetLastError();                                                      \
+            destroy_f64(h);                                                               \
+            return fail_create(oom_ ? RT_E_NOMEM : RT_E_NO_DEVICE, "float64 handle: " + m_); \
+        }                                                                                 \
+    } while (0)
+    if (cfg->hip_stream) {
+        h->s_scan = (hipStream_t)cfg->hip_stream;
+    } else {
+        RT_F64_CREATE(hipStreamCreateWithFlags(&h->s_scan, hipStreamNonBlocking));
+        h->own_scan_stream = true;
+    }
+    h->s_detect = h->s_scan;
+    // tables, made on the host so that every entry is rounded once to double
+    {
+        std::vector<cd> tw((size_t)f->M / 2);
+        for (int j = 0; j < f->M / 2; ++j) tw[(size_t)j] = f64_expi(-2.0L * kPiL * (long double)j / (long double)f->M);
+        RT_F64_CREATE(hipMalloc(&f->d_tw, tw.size() * sizeof(cd)));
+        RT_F64_CREATE(hipMemcpy(f->d_tw, tw.data(), tw.size() * sizeof(cd), hipMemcpyHostToDevice));
+        RT_F64_CREATE(hipMalloc(&f->d_window, (size_t)n * sizeof(double)));
+        RT_F64_CREATE(hipMemcpy(f->d_window, f64->window, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        if (f->blu) {
+            const int M = f->M;
+            std::vector<cd> cwin((size_t)n), chirp((size_t)n);
+            for (int k = 0; k < n; ++k) {
+                const long long r = ((long long)k * k) % (2LL * n);  // exp(-i pi k^2 / N) has period 2 N in k^2
+                chirp[(size_t)k] = f64_expi(-kPiL * (long double)r / (long double)n);
+                const long double w = (long double)f64->window[k];
+                const long double a = -kPiL * (long double)r / (long double)n;
+                cwin[(size_t)k] = cd{(double)(w * cosl(a)), (double)(w * sinl(a))};
+            }
+            std::vector<long double> re((size_t)M, 0.0L), im((size_t)M, 0.0L);
+            for (int k = 0; k < n; ++k) {  // the filter conj(w[m]) at m = k and m = M - k
+                const long long r = ((long long)k * k) % (2LL * n);
+                const long double a = kPiL * (long double)r / (long double)n;
+                re[(size_t)k] = cosl(a);
+                im[(size_t)k] = sinl(a);
+                if (k) {
+                    re[(size_t)(M - k)] = cosl(a);
+                    im[(size_t)(M - k)] = sinl(a);
+                }
+            }
+            host_fft_ld(re, im);
+            std::vector<cd> bf((size_t)M);
+            for (int i = 0; i < M; ++i) {  // bit-reversed order (the DIF transform's output order), divided by M
+                const unsigned rv = __builtin_bitreverse32((unsigned)i) >> (32 - f->log2m);
+                bf[(size_t)i] = cd{(double)(re[rv] / (long double)M), (double)(im[rv] / (long double)M)};
+            }
+            RT_F64_CREATE(hipMalloc(&f->d_cwin, (size_t)n * sizeof(cd)));
+            RT_F64_CREATE(hipMemcpy(f->d_cwin, cwin.data(), (size_t)n * sizeof(cd), hipMemcpyHostToDevice));
+            RT_F64_CREATE(hipMalloc(&f->d_bfilt, (size_t)M * sizeof(cd)));
+            RT_F64_CREATE(hipMemcpy(f->d_bfilt, bf.data(), (size_t)M * sizeof(cd), hipMemcpyHostToDevice));
+        }
+    }
+    const int lds = f->SPB * f->M * (int)sizeof(cd);
+    if (lds > 64 * 1024) {
+        const void *fns[] = {(const void *)stft_f64<false, false>, (const void *)stft_f64<false, true>,
+                             (const void *)stft_f64<true, false>, (const void *)stft_f64<true, true>};
+        for (const void *fn : fns) RT_F64_CREATE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
+    // the float64 map (S T N 8 bytes) and the look-back tails
+    RT_F64_CREATE(hipMalloc(&f->d_map, std::max<size_t>(8, S * (size_t)f->max_seg * (size_t)n * sizeof(double))));
+    for (double *&t : f->d_tail) {
+        RT_F64_CREATE(hipMalloc(&t, S * (size_t)f->K * (size_t)n * sizeof(double)));
+        RT_F64_CREATE(hipMemset(t, 0, S * (size_t)f->K * (size_t)n * sizeof(double)));
+    }
+    for (F64Slot &sl : f->slot) {
+        RT_F64_CREATE(hipMalloc(&sl.d_raw_count, S * sizeof(int32_t)));
+        RT_F64_CREATE(hipMemset(sl.d_raw_count, 0, S * sizeof(int32_t)));
+        RT_F64_CREATE(hipMalloc(&sl.d_no_last, S * sizeof(int32_t)));
+        RT_F64_CREATE(hipHostMalloc(&sl.h_meta, (2 * S + 1) * sizeof(int32_t)));
+        RT_F64_CREATE(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
+        if (f64_slot_areas(h, sl, f->rec_cap) != RT_OK) {
+            destroy_f64(h);
+            return fail_create(RT_E_NOMEM, "float64 handle: no memory for the record areas");
+        }
+    }
+#undef RT_F64_CREATE
+    *out = h;
+    return RT_OK;
+}
+
+int rt_set_stream_params_f64(rt_handle *h, const double *threshold, const double *calibration_db) {
+    if (!h) return RT_E_INVALID;
+    if (!h->f64) {
+        h->err = "rt_set_stream_params_f64 on a float32 handle: use rt_set_stream_params";
+        return RT_E_INVALID;
+    }
+    F64State *f = h->f64;
+    if (f64_oldest(f)) return f64_err(h, RT_E_INVALID, "rt_set_stream_params_f64 with unfetched calls pending: fetch them first");
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    const int S = h->cfg.n_streams;
+    const size_t bytes = (size_t)S * sizeof(double);
+    auto put = [&](double *&dst, const double *src) -> int {
+        if (!src) {
+            if (dst) (void)hipFree(dst);
+            dst = nullptr;
+            return RT_OK;
+        }
+        if (!dst) RT_HIP(h, hipMalloc(&dst, bytes));
+        RT_HIP(h, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return RT_OK;
+    };
+    // a stream whose threshold changes starts without look-back (a new analyzer in the reference, analyze.py:115)
+    for (int s = 0; s < S; ++s) {
+        const double was = f->h_thr_s.empty() ? f->c.threshold : f->h_thr_s[(size_t)s];
+        const double is = threshold ? threshold[s] : f->c.threshold;
+        if (!(was == is)) {
+            f->reset_pending[(size_t)s] = 1;
+            f->any_reset = true;
+        }
+    }
+    if (threshold) f->h_thr_s.assign(threshold, threshold + S); else f->h_thr_s.clear();
+    const int rc = put(f->d_thr_s, threshold);
+    if (rc != RT_OK) return rc;
+    return put(f->d_cal_s, calibration_db);
+}
+
+int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t n_bins, const double *last_dev, int32_t n_seg_last) {
+    if (!h) return RT_E_INVALID;
+    if (!h->f64) {
+        h->err = "rt_extract_f64 on a float32 handle: use rt_extract";
+        return RT_E_INVALID;
+    }
+    F64State *f = h->f64;
+    if (n_seg < 0 || n_bins < 1 || (n_seg > 0 && !spec_dev) || (last_dev && n_seg_last < 0))
+        return f64_err(h, RT_E_INVALID, "bad spectrogram arguments");
+    if (n_seg == 1) return f64_err(h, RT_E_ONE_SEGMENT, "exactly one segment: the reference raises IndexError (times[1])");
+    if (reinterpret_cast<uintptr_t>(spec_dev) % 8u != 0 || reinterpret_cast<uintptr_t>(last_dev) % 8u != 0)
+        return f64_err(h, RT_E_INVALID, "spectrogram pointers must be 8-byte aligned (float64)");
+    if ((int64_t)n_seg * n_bins > 0x7FFFFFFFll || (int64_t)h->cfg.n_streams * n_bins > 0x7FFFFFFFll)
+        return f64_err(h, RT_E_UNSUPPORTED, "spectrogram too large");
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    F64Slot &sl = f64_claim(f);
+    sl.pending = false;
+    sl.is_extract = true;
+    sl.n_seg = n_seg;
+    sl.ex_spec = spec_dev;
+    sl.ex_bins = n_bins;
+    sl.ex_last = last_dev;
+    sl.ex_last_cols = last_dev ? n_seg_last : 0;
+    sl.no_last = false;
+    return f64_start(h, sl);
+}
+
+int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
+    if (!h || !n_out) return RT_E_INVALID;
+    if (!h->f64) {
+        h->err = "rt_fetch_f64 on a float32 handle: use rt_fetch";
+        return RT_E_INVALID;
+    }
+    F64State *f = h->f64;
+    *n_out = 0;
+    F64Slot *slp = f64_oldest(f);
+    if (!slp) return f64_err(h, RT_E_INVALID, "rt_fetch_f64 without a preceding successful rt_process/rt_extract_f64");
+    F64Slot &sl = *slp;
+    const int S = h->cfg.n_streams;
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    RT_HIP(h, hipEventSynchronize(sl.ev_done));
+    bool truncated = false;
+    for (;;) {
+        int wanted = 0;
+        for (int s = 0; s < S; ++s) wanted = std::max(wanted, sl.h_meta[S + 1 + s]);
+        if (wanted <= sl.rec_cap) break;
+        if (sl.is_extract) {  // (the library does not keep the caller's spectrogram: the first records of each stream that fit)
+            truncated = true;
+            break;
+        }
+        // a stream found more records than the slot holds: grow the capacity and analyse the call again (its IQ is still valid)
+        int cap2 = sl.rec_cap;
+        while (cap2 < wanted) cap2 *= 2;
+        int rc = f64_slot_areas(h, sl, cap2);
+        if (rc != RT_OK) {
+            sl.pending = false;
+            return rc;
+        }
+        f->rec_cap = std::max(f->rec_cap, cap2);
+        rc = f64_enqueue(h, sl);
+        if (rc != RT_OK) {
+            sl.pending = false;
+            return rc;
+        }
+        RT_HIP(h, hipEventSynchronize(sl.ev_done));
+    }
+    const size_t total = (size_t)sl.h_meta[S];
+    *n_out = total;
+    h->info = rt_call_info{};
+    h->info.n_seg = sl.n_seg;
+    h->info.mode_used = RT_MODE_DENSE;
+    h->info.n_records = (int64_t)total;
+    if (total && (!out || !cap)) return truncated ? RT_E_CAPACITY : RT_OK;  // size query: the call stays pending
+    const size_t n = std::min(total, cap);
+    if (n) std::memcpy(out, sl.h_out, n * sizeof(rt_record_f64));
+    sl.pending = false;
+    if (truncated) return f64_err(h, RT_E_CAPACITY, "rt_extract_f64: a stream found more records than record_capacity");
+    if (n < total) return f64_err(h, RT_E_CAPACITY, "output buffer too small: records lost");
+    return RT_OK;
+}
+
+int rt_spectrogram_f64(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, double *spec_dev) {
+    if (!h || !iq_dev || !spec_dev) return RT_E_INVALID;
+    if (!h->f64) {
+        h->err = "rt_spectrogram_f64 on a float32 handle: use rt_spectrogram";
+        return RT_E_INVALID;
+    }
+    F64State *f = h->f64;
+    if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples || reinterpret_cast<uintptr_t>(iq_dev) % 16u != 0 ||
+        reinterpret_cast<uintptr_t>(spec_dev) % 8u != 0)
+        return f64_err(h, RT_E_INVALID, "n_samples/stream_stride out of range for this handle, or misaligned pointer");
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    const int T = (int)(n_samples / f->N);
+    if (T == 0) return RT_OK;
+    RT_HIP(h, hipDeviceSynchronize());
+    F64StftParams p{};
+    p.iq = iq_dev;
+    p.stream_stride = stream_stride;
+    p.n_streams = h->cfg.n_streams;
+    p.n_seg = T;
+    p.nperseg = f->N;
+    p.m = f->M;
+    p.log2m = f->log2m;
+    p.segs_per_block = f->SPB;
+    p.tail_cols = f->K;
+    p.scale = f->c.scale;
+    p.window = f->d_window;
+    p.cwin = f->d_cwin;
+    p.bfilt = f->d_bfilt;
+    p.tw = f->d_tw;
+    p.spec = spec_dev;
+    p.tail = nullptr;
+    const int64_t grid = (int64_t)h->cfg.n_streams * ((T + f->SPB - 1) / f->SPB);
+    const size_t lds = (size_t)f->SPB * f->M * sizeof(cd);
+    if (f->blu) stft_f64<false, true><<<(unsigned)grid, kF64Block, lds, h->s_scan>>>(p);
+    else stft_f64<false, false><<<(unsigned)grid, kF64Block, lds, h->s_scan>>>(p);
+    RT_HIP(h, hipGetLastError());
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    return RT_OK;
 }
 
 }  // extern "C"

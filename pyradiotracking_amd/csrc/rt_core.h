@@ -18,6 +18,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #if defined(__HIP__)  // HIP translation units only (hipcc also compiles the plain C++ ones)
 #define RT_HD __host__ __device__ __forceinline__
 #else
@@ -26,19 +29,27 @@
 
 namespace rt {
 
-// Geometry/thresholds of one detect pass (one spectrogram of T columns).
-struct DetectParams {
+// Geometry/thresholds of one detect pass (one spectrogram of T columns).  P is the power type of the map: float for
+// the complex64 path, double for a float64 handle (rt_create_f64), whose thresholds are the reference's Python floats.
+template <class P>
+struct DetectParamsT {
     int32_t n_seg;        // T: columns of the current spectrogram
     int32_t n_seg_last;   // columns of the previous one, or -1 if there is none
     int32_t tail_cols;    // K: how many trailing columns of the previous one are readable
     int32_t stride;       // probe stride max(1, int(min_d / hop))         (analyze.py:354, 364)
     int32_t nperseg;      // N (for the time axis only)
-    float thr;            // signal_threshold (linear)
-    float snr;            // snr_threshold (linear)
-    float cal_db;         // calibration (only to order maxima in the shadow filter)
+    P thr;                // signal_threshold (linear)
+    P snr;                // snr_threshold (linear)
+    P cal_db;             // calibration (only to order maxima in the shadow filter)
     double fs;
     double min_d;         // seconds
     double max_d;         // seconds
+};
+using DetectParams = DetectParamsT<float>;
+using DetectParams64 = DetectParamsT<double>;
+template <class T>
+struct same_t {  // (keeps an argument out of template deduction: the power type comes from the parameters)
+    using type = T;
 };
 
 // ---- RT_MODE_AUTO's levels (host-side bookkeeping of rt_analyze.hip; here so that the CPU suite can test it) ----
@@ -125,6 +136,12 @@ RT_HD bool cell_above(float p, float avg, float thr, float snr) {
     if (p / avg < snr) return false;
     return true;
 }
+// ... and in float64 (a float64 handle: the reference's comparisons on complex128 input)
+RT_HD bool cell_above(double p, double avg, double thr, double snr) {
+    if (p < thr) return false;
+    if (p / avg < snr) return false;
+    return true;
+}
 
 // A maximal run [b, e) of above-cells is visited by the strided probe iff it
 // contains a multiple of the stride (T9).  Returns that first probe or -1.
@@ -142,8 +159,8 @@ struct StartWalk {
 
 // `prev(d)` returns the power of the previous buffer's column n_seg_last-d
 // (d >= 1, d <= tail_cols) for the bin at hand.
-template <class PrevCell>
-RT_HD StartWalk walk_start(const DetectParams &p, int32_t b, int32_t ti0, float avg, PrevCell prev) {
+template <class P, class PrevCell>
+RT_HD StartWalk walk_start(const DetectParamsT<P> &p, int32_t b, int32_t ti0, typename same_t<P>::type avg, PrevCell prev) {
     StartWalk w;
     w.too_long = false;
     const int32_t start_min = (p.n_seg_last < 0) ? 0 : (1 - p.n_seg_last);
@@ -176,13 +193,16 @@ RT_HD StartWalk walk_start(const DetectParams &p, int32_t b, int32_t ti0, float 
 }
 
 // start_dt / duration in float64 exactly as analyze.py:420-427
-RT_HD double start_time(const DetectParams &p, int32_t start) {
+template <class P>
+RT_HD double start_time(const DetectParamsT<P> &p, int32_t start) {
     return start < 0 ? -seg_time(-start, p.nperseg, p.fs) : seg_time(start, p.nperseg, p.fs);
 }
-RT_HD double run_duration(const DetectParams &p, int32_t start, int32_t end) {
+template <class P>
+RT_HD double run_duration(const DetectParamsT<P> &p, int32_t start, int32_t end) {
     return seg_time(end, p.nperseg, p.fs) - start_time(p, start);
 }
-RT_HD bool duration_ok(const DetectParams &p, double dur) {
+template <class P>
+RT_HD bool duration_ok(const DetectParamsT<P> &p, double dur) {
     if (dur < p.min_d) return false;
     if (dur > p.max_d) return false;
     return true;
@@ -190,23 +210,28 @@ RT_HD bool duration_ok(const DetectParams &p, double dur) {
 
 // np.max / np.mean / np.std(dB(.)) over the cells of a plateau.  `cell(i)`,
 // i in [0, n), yields the i-th element of `data` (analyze.py:437-440).
-struct RunStats {
-    float max_p, mean_p, std_db;
+template <class P>
+struct RunStatsT {
+    P max_p, mean_p, std_db;
 };
+using RunStats = RunStatsT<float>;
 
 RT_HD float db10(float v) { return 10.0f * log10f(v); }
+RT_HD double db10(double v) { return 10.0 * log10(v); }
 
 // Canonical summation order (so the wave-cooperative device code, the dense
 // kernel and the host check agree bit for bit): 64 interleaved partial sums
 // (cell k goes to partial k mod 64, in k order), folded by halving
 // (p[l] += p[l + off], off = 32, 16, ... 1).  Sums run in float64 over the
-// float32 values np.mean / np.std see; np.max propagates NaN.
+// float32 values np.mean / np.std see; np.max propagates NaN.  The power type P is what `cell` yields (float64 maps:
+// the same order, every step in float64).
 constexpr int kStatLanes = 64;
 
 template <class Cell>
-RT_HD RunStats run_stats(int32_t n, Cell cell) {
+RT_HD RunStatsT<typename std::decay<decltype(std::declval<Cell>()(0))>::type> run_stats(int32_t n, Cell cell) {
+    using P = typename std::decay<decltype(cell(0))>::type;
     double ps[kStatLanes], pd[kStatLanes];
-    float pm[kStatLanes];
+    P pm[kStatLanes];
     bool any_nan = false;
     for (int l = 0; l < kStatLanes; ++l) {
         ps[l] = 0.0;
@@ -215,7 +240,7 @@ RT_HD RunStats run_stats(int32_t n, Cell cell) {
     }
     for (int32_t k = 0; k < n; ++k) {
         const int l = k & (kStatLanes - 1);
-        const float v = cell(k);
+        const P v = cell(k);
         ps[l] += (double)v;
         pd[l] += (double)db10(v);
         if (v != v) any_nan = true;
@@ -236,10 +261,10 @@ RT_HD RunStats run_stats(int32_t n, Cell cell) {
     }
     for (int off = kStatLanes / 2; off > 0; off >>= 1)
         for (int l = 0; l < off; ++l) pa[l] += pa[l + off];
-    RunStats r;
-    r.max_p = any_nan ? NAN : pm[0];
-    r.mean_p = (float)(ps[0] / (double)n);
-    r.std_db = (float)sqrt(pa[0] / (double)n);
+    RunStatsT<P> r;
+    r.max_p = any_nan ? (P)NAN : pm[0];
+    r.mean_p = (P)(ps[0] / (double)n);
+    r.std_db = (P)sqrt(pa[0] / (double)n);
     return r;
 }
 
@@ -269,8 +294,8 @@ RT_HD int64_t timedelta_us(double seconds) {
 // plateau (analyze.py:401-433 in run-based form): the
 // cheap decisions.  `prev(d)` reads the previous buffer's cell n_seg_last - d.
 // Returns true and the first cell of `data` if the run becomes a signal.
-template <class Prev>
-RT_HD bool gate_run(const DetectParams &p, int32_t b, int32_t e, float avg, Prev prev, int32_t *start_out) {
+template <class P, class Prev>
+RT_HD bool gate_run(const DetectParamsT<P> &p, int32_t b, int32_t e, typename same_t<P>::type avg, Prev prev, int32_t *start_out) {
     if (e == p.n_seg) return false;  // laps into the next buffer (analyze.py:415)
     const int32_t ti0 = first_probe_in_run(b, e, p.stride);
     if (ti0 < 0) return false;       // no strided probe lands in the run (T9)
@@ -283,11 +308,11 @@ RT_HD bool gate_run(const DetectParams &p, int32_t b, int32_t e, float avg, Prev
 
 // gate + statistics for one run, sequentially (host check; the kernels gate
 // per thread and compute the statistics wave-cooperatively in the same order)
-template <class Cur, class Prev, class Emit>
-RT_HD void finish_run(const DetectParams &p, int32_t b, int32_t e, float avg, Cur cur, Prev prev, Emit emit) {
+template <class P, class Cur, class Prev, class Emit>
+RT_HD void finish_run(const DetectParamsT<P> &p, int32_t b, int32_t e, typename same_t<P>::type avg, Cur cur, Prev prev, Emit emit) {
     int32_t start;
     if (!gate_run(p, b, e, avg, prev, &start)) return;
-    auto cell = [&](int32_t k) -> float {
+    auto cell = [&](int32_t k) -> P {
         const int32_t t = start + k;
         return t < 0 ? prev(-t) : cur(t);
     };
@@ -298,19 +323,23 @@ RT_HD void finish_run(const DetectParams &p, int32_t b, int32_t e, float avg, Cu
 // calls on_run(b, e, avg) for every maximal run of above-cells.  Returns false
 // when no cell reaches the absolute threshold (the row mean is then unused).
 // `row_sum` < 0 means "not known": the row is summed here.
-template <class Cur, class OnRun>
-RT_HD bool scan_dense_row(const DetectParams &p, Cur cur, double row_sum, float *avg_out, OnRun on_run) {
+// np.mean(row) (analyze.py:375) from the row's float64 sum: float32 rows as float32 (the sum rounded once), float64 rows in float64
+RT_HD float row_mean_of(double sum, int32_t T, float) { return (float)sum / (float)T; }
+RT_HD double row_mean_of(double sum, int32_t T, double) { return sum / (double)T; }
+
+template <class P, class Cur, class OnRun>
+RT_HD bool scan_dense_row(const DetectParamsT<P> &p, Cur cur, double row_sum, P *avg_out, OnRun on_run) {
     const int32_t T = p.n_seg;
     double sum = 0.0;
     bool any = false;
     for (int32_t t = 0; t < T; ++t) {
-        const float v = cur(t);
+        const P v = cur(t);
         sum += (double)v;
         any |= !(v < p.thr);
     }
     if (!any) return false;
     if (row_sum >= 0.0) sum = row_sum;
-    const float avg = (float)sum / (float)T;  // np.mean(row) (analyze.py:375)
+    const P avg = row_mean_of(sum, T, P());  // np.mean(row) (analyze.py:375)
     *avg_out = avg;
     int32_t b = -1;
     for (int32_t t = 0; t <= T; ++t) {
@@ -328,7 +357,8 @@ RT_HD bool scan_dense_row(const DetectParams &p, Cur cur, double row_sum, float 
 }
 
 // is_shadow_of (analyze.py:300-311) on microsecond offsets from ts_start.
-RT_HD bool shadowed_by(int64_t ts_i, int64_t dur_i, float max_i, int64_t ts_j, int64_t dur_j, float max_j) {
+template <class P>
+RT_HD bool shadowed_by(int64_t ts_i, int64_t dur_i, P max_i, int64_t ts_j, int64_t dur_j, P max_j) {
     if (ts_i > ts_j + dur_j) return false;
     if (ts_i + dur_i < ts_j) return false;
     return max_j > max_i;
@@ -336,16 +366,16 @@ RT_HD bool shadowed_by(int64_t ts_i, int64_t dur_i, float max_i, int64_t ts_j, i
 
 // Position of record i in (fi, start) order and its shadow verdict against
 // the unfiltered list (analyze.py:325).  max is compared as the reference's
-// float32 dBW figure (analyze.py:442).
-template <class Rec>
+// float32 dBW figure (analyze.py:442) -- float64 records (P = double) as the float64 one.
+template <class Rec, class P>
 RT_HD void rank_and_shadow(int32_t i, int32_t n, const Rec *rec, const long long *ts_us, const long long *dur_us,
-                           float cal_db, int32_t *rank_out, int32_t *shadow_out) {
+                           P cal_db, int32_t *rank_out, int32_t *shadow_out) {
     const int32_t fi = rec[i].fi, st = rec[i].start;
-    const float mx_i = db10(rec[i].max_p) - cal_db;
+    const P mx_i = db10(rec[i].max_p) - cal_db;
     int32_t rank = 0, shadow = 0;
     for (int32_t j = 0; j < n; ++j) {
         if (rec[j].fi < fi || (rec[j].fi == fi && rec[j].start < st)) ++rank;
-        const float mx_j = db10(rec[j].max_p) - cal_db;
+        const P mx_j = db10(rec[j].max_p) - cal_db;
         if (shadowed_by(ts_us[i], dur_us[i], mx_i, ts_us[j], dur_us[j], mx_j)) shadow = 1;
     }
     *rank_out = rank;

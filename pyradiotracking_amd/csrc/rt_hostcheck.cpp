@@ -132,3 +132,62 @@ int hc_plan_runs(const unsigned long long *hot, unsigned long long *need, int n_
 int hc_plan_tile_rows(int n_seg, int lg, int r) { return plan_tile_rows(n_seg, lg, r); }
 
 }  // extern "C"
+
+extern "C" {
+
+// hc_extract on a float64 map with float64 thresholds: the rt_core.h instantiations a float64 handle's kernels run
+// (rt_create_f64), records as rt_record_f64.
+int hc_extract_f64(const double *spec, int n_seg, int n_bins, const double *last, int n_seg_last, int tail_cols,
+                   int nperseg, double fs, double thr, double snr, double cal_db, double min_d, double max_d,
+                   rt_record_f64 *out, int cap) {
+    DetectParams64 p;
+    p.n_seg = n_seg;
+    p.n_seg_last = last ? n_seg_last : -1;
+    p.tail_cols = last ? tail_cols : 0;
+    p.stride = probe_stride(nperseg, fs, min_d);
+    p.nperseg = nperseg;
+    p.thr = thr;
+    p.snr = snr;
+    p.cal_db = cal_db;
+    p.fs = fs;
+    p.min_d = min_d;
+    p.max_d = max_d;
+    std::vector<rt_record_f64> rec;
+    std::vector<long long> ts, du;
+    for (int fi = 0; fi < n_bins; ++fi) {
+        auto cur = [&](int t) -> double { return spec[(size_t)t * n_bins + fi]; };
+        auto prev = [&](int d) -> double { return last[(size_t)(n_seg_last - d) * n_bins + fi]; };
+        double avg = 0.0;
+        auto emit = [&](int start, int end, const RunStatsT<double> &st) {
+            rt_record_f64 r;
+            std::memset(&r, 0, sizeof r);
+            r.fi = fi;
+            r.start = start;
+            r.end = end;
+            r.max_p = st.max_p;
+            r.mean_p = st.mean_p;
+            r.std_db = st.std_db;
+            r.row_mean = avg;
+            rec.push_back(r);
+            ts.push_back(timedelta_us(start_time(p, start)));
+            du.push_back(timedelta_us(run_duration(p, start, end)));
+        };
+        auto on_run = [&](int b, int e, double av) {
+            avg = av;
+            finish_run(p, b, e, av, cur, prev, emit);
+        };
+        scan_dense_row(p, cur, -1.0, &avg, on_run);
+    }
+    const int n = (int)rec.size();
+    std::vector<rt_record_f64> ordered(n);
+    for (int i = 0; i < n; ++i) {
+        int rank, shadow;
+        rank_and_shadow(i, n, rec.data(), ts.data(), du.data(), cal_db, &rank, &shadow);
+        ordered[rank] = rec[i];
+        ordered[rank].shadowed = shadow;
+    }
+    for (int i = 0; i < n && i < cap; ++i) out[i] = ordered[i];
+    return n;
+}
+
+}  // extern "C"

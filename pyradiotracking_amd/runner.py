@@ -203,7 +203,7 @@ class BatchRunner:
 
     # -- one step: one buffer per SDR ------------------------------------------------------------------
     def process(self, buffers, present: Optional[Sequence[bool]] = None, now: Optional[float] = None):
-        """The batched callback: ``buffers`` is ``[n_devices, B]`` complex64 (host array; rows in
+        """The batched callback: ``buffers`` is ``[n_devices, B]`` complex64 -- complex128 for float64 analyzers -- (host array; rows in
         ``--device`` order) or a dict ``gpu -> [S_gpu, B]`` device tensor; ``present[i]`` is False for an SDR
         that delivered nothing this step (its row is ignored).  Signals go to ``signal_queue`` per stream in
         the reference's order, after the shadow filter; returns their number."""
@@ -242,7 +242,9 @@ class BatchRunner:
                 if per_gpu is not None:
                     self.analyzers[gpu].enqueue(per_gpu[gpu])
                 else:
-                    chunk = np.ascontiguousarray(host[members], dtype=np.complex64)
+                    # (complex128 buffers stay complex128 for an analyzer made with precision="float64")
+                    cdt = np.complex128 if getattr(self.analyzers[gpu], "precision", "float32") == "float64" else np.complex64
+                    chunk = np.ascontiguousarray(host[members], dtype=cdt)
                     for k, i in enumerate(members):
                         if not active[i]:
                             chunk[k] = 0  # no samples: zero power, below every threshold
