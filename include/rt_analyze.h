@@ -135,6 +135,7 @@ typedef struct rt_config {
                                      average).  This flag: at any number of streams, whatever they hold.  Only where the fused kernels have
                                      the form (nperseg <= 256); ignored elsewhere */
 #define RT_FLAG_NO_GROUP_DETECT 8u /* ... never */
+#define RT_FLAG_ROW_MEANS 16u      /* keep each call's row means for rt_fetch_row_means[_f64] (rt_create and rt_create_f64) */
 
 /*
  * One extracted plateau, before it becomes a Signal (analyze.py:442-449).
@@ -345,6 +346,28 @@ int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t 
 
 /* rt_spectrogram of a float64 handle: complex128 `iq_dev` -> [S][T][nperseg] float64 at `spec_dev`.  Synchronous. */
 int rt_spectrogram_f64(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, double *spec_dev);
+
+/*
+ * ---- row means: every bin's noise level (additive within ABI version 6) ----
+ * The reference computes one noise figure per bin and buffer, `freq_avg = np.mean(row)` (analyze.py:373-375), and prints it
+ * only as the `noise` of a Signal (analyze.py:446).  A handle created with RT_FLAG_ROW_MEANS (rt_create or rt_create_f64)
+ * keeps that figure for EVERY bin of every stream; without the flag nothing is allocated or launched for it.
+ *   - `out`: HOST memory, n == n_streams * nperseg entries, [stream][fi], fi in fftfreq order (the index of rt_record.fi).
+ *   - the row means of the call the last rt_fetch / rt_fetch_f64 delivered (with RT_OK, or RT_E_CAPACITY).  Valid until the
+ *     next rt_process*, rt_extract* or rt_reset on the handle; with two calls in flight: process k, process k + 1, fetch k,
+ *     then the row means of k.
+ *   - each entry is np.mean of the bin's row over the call's T segments in the handle's arithmetic (float32: the float64 sum
+ *     of the partial row sums, rounded once and divided by T in float32; float64: the float64 sum divided by T).  For every
+ *     record r of the call, out[r.stream * nperseg + r.fi] == r.row_mean bit for bit, in every mode and lane split, after
+ *     AUTO's re-runs and after a re-analysis on record growth.
+ *   - T == 0 (a buffer shorter than nperseg): every entry is NaN, as np.mean of an empty row.
+ *   - RT_E_INVALID: null handle or `out`, a handle without the flag, a wrong n, no delivered call (or its row means are no
+ *     longer valid, see above), a delivered call that was an rt_extract (the caller holds that map), and the float32 entry on
+ *     a float64 handle or the reverse.
+ * A laned handle gathers its lanes' row means in stream order.
+ */
+int rt_fetch_row_means(rt_handle *h, float *out, size_t n);       /* float32 handle */
+int rt_fetch_row_means_f64(rt_handle *h, double *out, size_t n);  /* float64 handle */
 
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */

@@ -29,6 +29,7 @@ RT_FLAG_TIMING = 1
 RT_FLAG_NO_LIN_DETREND = 2  # subtract the segment mean before windowing even for hamming / hann / boxcar windows
 RT_FLAG_GROUP_DETECT = 4  # sparse detection by groups of candidate lists at any number of streams (default: from 1 024 streams per handle)
 RT_FLAG_NO_GROUP_DETECT = 8  # ... never
+RT_FLAG_ROW_MEANS = 16  # keep each call's row means (every bin's noise level) for rt_fetch_row_means[_f64]
 
 SUPPORTED_NPERSEG = tuple(range(8, 8193)) + (16384,)  # 8 .. 8192 and 16384 (32 .. 4096 powers of two: the fused scans; everything else: general transforms, dense path)
 FUSED_NPERSEG = (256, 512, 1024, 2048, 4096)
@@ -149,6 +150,8 @@ ABI_SYMBOLS = (
     "rt_set_stream_params_f64",
     "rt_extract_f64",
     "rt_spectrogram_f64",
+    "rt_fetch_row_means",
+    "rt_fetch_row_means_f64",
 )
 
 _lib = None
@@ -209,6 +212,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_set_stream_params_f64.argtypes = [vp, vp, vp]
     lib.rt_extract_f64.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int32]
     lib.rt_spectrogram_f64.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
+    lib.rt_fetch_row_means.argtypes = [vp, vp, C.c_size_t]
+    lib.rt_fetch_row_means_f64.argtypes = [vp, vp, C.c_size_t]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -301,10 +306,12 @@ class NativeAnalyzer:
         record_pool: int = 0,
         group_detect: Optional[bool] = None,
         precision: str = "float32",
+        row_means: bool = False,
     ):
         """``precision="float64"``: a float64 handle (``rt_create_f64``) -- ``window_f32`` then holds the float64 window and
         ``scale`` / ``threshold`` / ``snr_threshold`` / ``calibration_db`` are passed on as float64, never rounded to float32;
-        the analysis takes complex128 (or uint8) IQ and the records are ``RECORD_F64_DTYPE``."""
+        the analysis takes complex128 (or uint8) IQ and the records are ``RECORD_F64_DTYPE``.  ``row_means``:
+        ``RT_FLAG_ROW_MEANS`` (``fetch_row_means``)."""
         if precision not in ("float32", "float64"):
             raise ValueError(f"precision must be 'float32' or 'float64', not {precision!r}")
         self.f64 = precision == "float64"
@@ -331,7 +338,8 @@ class NativeAnalyzer:
         cfg.record_capacity = record_capacity
         cfg.segs_per_chunk = segs_per_chunk
         cfg.flags = ((RT_FLAG_TIMING if timing else 0) | (RT_FLAG_NO_LIN_DETREND if subtract_first else 0)
-                     | (0 if group_detect is None else RT_FLAG_GROUP_DETECT if group_detect else RT_FLAG_NO_GROUP_DETECT))
+                     | (0 if group_detect is None else RT_FLAG_GROUP_DETECT if group_detect else RT_FLAG_NO_GROUP_DETECT)
+                     | (RT_FLAG_ROW_MEANS if row_means else 0))
         cfg.hip_stream = hip_stream
         cfg.lanes = int(lanes)
         cfg.record_pool = int(record_pool)
@@ -441,6 +449,14 @@ class NativeAnalyzer:
             self.last_truncated = True
         if rc != RT_OK and not (allow_truncated and rc == RT_E_CAPACITY):
             self._check(rc)
+        return out
+
+    def fetch_row_means(self) -> np.ndarray:
+        """``rt_fetch_row_means`` (``rt_fetch_row_means_f64`` on a float64 handle): ``[S, nperseg]`` float32 (float64), the
+        mean of every bin's row over the segments of the call ``fetch`` delivered last, bins in fftfreq order."""
+        out = np.empty((self.n_streams, self.nperseg), dtype=np.float64 if self.f64 else np.float32)
+        fn = self._lib.rt_fetch_row_means_f64 if self.f64 else self._lib.rt_fetch_row_means
+        self._check(fn(self._handle, out.ctypes.data, out.size))
         return out
 
     def extract_device(self, spec_ptr: int, n_seg: int, n_bins: int, last_ptr: Optional[int], n_seg_last: int):

@@ -98,6 +98,12 @@ class _RecordDecoder:
         # element k of  arange(N/2, B - N/2 + 1, N) / float(fs)   (_spectral_py.py:2136)
         return (self.nperseg / 2 + np.asarray(k, dtype=np.float64) * self.nperseg) / float(self.sample_rate)
 
+    @staticmethod
+    def noise_dbw(row_mean):
+        """``Signal.noise`` from a row mean: ``dB(freq_avg)``, uncalibrated as in the reference (analyze.py:446)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return dB(row_mean)
+
     def decode(self, rec: np.ndarray, freqs: Optional[np.ndarray] = None, times: bool = True):
         """Signal field columns of ``rec``; ``freqs`` replaces the analyzer's own frequency axis (caller-supplied
         spectrograms may have any number of bins, ``extract_signals``).  ``times=False``: without start time and duration
@@ -117,7 +123,7 @@ class _RecordDecoder:
         with np.errstate(divide="ignore", invalid="ignore"):
             max_dbw = dB(rec["max_p"]) - cal  # float32, analyze.py:442
             avg_dbw = dB(rec["mean_p"]) - cal  # :444
-            noise_dbw = dB(rec["row_mean"])  # :446
+            noise_dbw = self.noise_dbw(rec["row_mean"])  # :446
             snr_db = dB(rec["mean_p"] / rec["row_mean"])  # :447
         frequency = (self.freqs if freqs is None else np.asarray(freqs))[rec["fi"]] + self.center_freq  # :360
         return t_start, duration_s, frequency, max_dbw, avg_dbw, rec["std_db"], noise_dbw, snr_db
@@ -269,9 +275,13 @@ class BatchSignalAnalyzer:
         record_pool: int = 0,
         group_detect: Optional[bool] = None,
         precision: str = "float32",
+        row_means: bool = False,
         **kwargs,
     ):
-        """``precision``: ``"float32"`` (default) analyses complex64; ``"float64"`` runs the reference's float64 arithmetic on
+        """``row_means`` (``RT_FLAG_ROW_MEANS``): keep every bin's noise level, the reference's ``freq_avg = np.mean(row)``
+        (analyze.py:373-375), of each call for :meth:`fetch_row_means` -- not only of the bins a signal was found in.
+
+        ``precision``: ``"float32"`` (default) analyses complex64; ``"float64"`` runs the reference's float64 arithmetic on
         complex128 buffers (what pyrtlsdr delivers) -- float64 window, scale, thresholds, map and statistics
         (``rt_create_f64``).  A float64 analyzer runs the dense path only (``mode`` ``"auto"`` or ``"dense"``), nperseg 8 ...
         4096 or a power of two up to 8192, one lane; ``enqueue`` takes complex128 device tensors, host complex arrays
@@ -363,6 +373,7 @@ class BatchSignalAnalyzer:
             record_pool=int(record_pool),
             group_detect=group_detect,
             precision=precision,
+            row_means=bool(row_means),
         )
         if per_stream_cal is not None:
             self.calibration_db = per_stream_cal
@@ -498,6 +509,16 @@ class BatchSignalAnalyzer:
         spectrogram can be cut off: that raises unless ``allow_truncated`` (then ``native.last_truncated`` tells)."""
         return self._native.fetch(allow_truncated)
 
+    def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
+        """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
+        reference's noise figure (analyze.py:373-375) -- over the buffer of the call :meth:`fetch_records` (or
+        :meth:`process_batch`) returned last, bins in fftfreq order; NaN for a buffer shorter than ``fft_nperseg``.  A record's
+        ``row_mean`` equals its bin's entry bit for bit.  ``dbw=True``: in dBW as ``Signal.noise`` (uncalibrated, analyze.py:446).
+        Needs ``row_means=True``; raises ``NativeError`` (``RT_E_INVALID``) once another buffer was enqueued or the analyzer
+        reset, and after an ``extract_signals`` call."""
+        out = self._native.fetch_row_means()
+        return self._decoder.noise_dbw(out) if dbw else out
+
     def process_batch(self, iq, ts_starts: Union[datetime.datetime, Sequence[datetime.datetime]], filtered: bool = True, lazy: bool = True):
         """One buffer per stream -> per stream a sequence of ``Signal``.
 
@@ -557,11 +578,16 @@ class SignalAnalyzer:
         gpu: int = 0,
         mode: str = "auto",
         precision: str = "float32",
+        row_means: bool = False,
         **kwargs,
     ):
-        """``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer)."""
+        """``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer).
+        ``row_means=True``: after every buffer ``noise_dbw`` holds the noise level of every bin (``[fft_nperseg]``, dBW, fftfreq
+        order) -- what the reference prints as the ``noise`` of a Signal (analyze.py:446), for all bins."""
         self.device = device
         self.precision = precision
+        self.row_means = bool(row_means)
+        self.noise_dbw: Optional[np.ndarray] = None
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -610,6 +636,7 @@ class SignalAnalyzer:
             gpu=gpu,
             mode=mode,
             precision=precision,
+            row_means=self.row_means,
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
             **{k: kwargs[k] for k in ("record_capacity", "record_pool", "hot_capacity", "group_detect") if k in kwargs},
         )
@@ -673,8 +700,10 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
+        self.noise_dbw = None
         self._batch.enqueue_bytes(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
+        self._keep_noise()
         rec = rec[rec["shadowed"] == 0]
         [self.consume_signal(s) for s in self._decoder.signals(rec, [self.device], [ts_start])]
         return None
@@ -685,12 +714,18 @@ class SignalAnalyzer:
         buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
+        self.noise_dbw = None
         out = self._batch.process_batch(buf, [ts_start], filtered=filtered, lazy=False)[0]  # (one stream: its Signal objects, as the reference returns them)
+        self._keep_noise()
         logger.info(
             f"SDR {self.device} recv {len(buffer)}, {len(out)} signals, "
             f"compute: {(time.time() - bench_start) * 1000:.1f} ms"
         )
         return out
+
+    def _keep_noise(self):
+        if self.row_means:
+            self.noise_dbw = self._batch.fetch_row_means(dbw=True)[0]
 
     def reset(self):
         self._batch.reset()
@@ -712,6 +747,7 @@ class SignalAnalyzer:
         dense detect kernel (``rt_extract``).  The time axis must be the one
         SciPy produces for ``fft_nperseg`` / ``sample_rate`` (hop = nperseg/fs);
         ``freqs`` is used as given."""
+        self.noise_dbw = None  # (the caller holds this map: no row means of it)
         spec = np.asarray(spectrogram)
         n_bins, n_seg = spec.shape
         if n_seg == 0:

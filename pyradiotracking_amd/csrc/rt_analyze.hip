@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 #include <vector>
@@ -82,6 +83,8 @@ struct CallCtx {
     int prev_tail_cur = 0, prev_n_seg_last = -1, prev_dense_sticky = 0, prev_minsum_slot = -1;
 };
 
+constexpr int kRowMeansNone = -1, kRowMeansExtract = -2;  // rt_handle::rm_slot / F64State::rm_slot without valid row means
+
 struct Slot {
     uint2 *d_hot = nullptr;
     uint32_t *d_hot_count = nullptr;
@@ -115,6 +118,7 @@ struct Slot {
     int32_t *h_dc_flag = nullptr;                              // pinned, [S]: set by a LIN scan for a stream whose constant offset is too large for that form (StftParams::dc_flag)
     int32_t *h_list = nullptr;                                 // pinned, [kMaxPartial]: the streams of a partial dense re-run (read by the kernels)
     unsigned long long *h_total = nullptr;                     // pinned: records allocated so far, uploaded before a partial re-run
+    float *d_row_means = nullptr;                              // [S][N] the call's row means (RT_FLAG_ROW_MEANS only; rt_fetch_row_means copies them)
     hipEvent_t ev_begin = nullptr, ev_first = nullptr, ev_scan = nullptr, ev_done = nullptr;  // first launch; end of the first scan; end of the scans; end of the call
     CallCtx call;
 };
@@ -137,6 +141,7 @@ struct F64Slot {
     int32_t *d_no_last = nullptr;                      // [S]
     std::vector<int32_t> no_last_h;
     rt_record_f64 *h_out = nullptr;                    // pinned, device-visible: [S * rec_cap] the call's records
+    double *d_row_means = nullptr;                     // [S][N] the call's row means (RT_FLAG_ROW_MEANS only; rt_fetch_row_means_f64 copies them)
     int32_t *h_meta = nullptr;                         // pinned, device-visible: [S + 1] offsets + total, then [S] wanted
     void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host
     size_t stage_bytes = 0;
@@ -158,6 +163,7 @@ struct F64State {
     int rec_cap = 1024;
     uint64_t n_calls = 0;
     F64Slot slot[kSlots];
+    int rm_slot = -1;  // the slot of the call rt_fetch_f64 delivered last, while its row means are valid (kRowMeansNone / kRowMeansExtract)
 };
 
 }  // namespace
@@ -250,6 +256,10 @@ struct rt_handle {
     // HIP stream) and forwards every call to them; kid k analyses streams [kid_base[k], kid_base[k + 1])
     std::vector<rt_handle *> kids;
     std::vector<int> kid_base;
+
+    // RT_FLAG_ROW_MEANS: the slot of the call rt_fetch delivered last, while its row means are valid (rt_fetch_row_means) --
+    // or kRowMeansNone (none delivered, or an rt_process* / rt_extract / rt_reset since), or kRowMeansExtract
+    int rm_slot = -1;
 
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
 };
@@ -639,6 +649,20 @@ void launch_detect_dense(rt_handle *h, int grid, hipStream_t st, const DetectArg
     }
 }
 
+// RT_FLAG_ROW_MEANS: every row's mean of the call (row_means_from_partials) into the slot's device buffer, on the stream of the
+// call's ev_done behind its detection, which read the same partial sums: behind the last writer of d_psum on every level -- the
+// first scan (MODE 0 / 1 / 4 / 6, and the subtract-first launch over the streams the detrend guard marked), row_sums_dense on the
+// general path, the dense scan of a partial re-run; the selective second scans of the pre-filter levels (MODE 5 / 7) write none.
+// Every analysis of a call rewrites all S rows, so the buffer holds those of the analysis whose records are delivered.
+int enqueue_row_means(rt_handle *h, Slot &sl, int chunks, int n_seg, hipStream_t st) {
+    if (!sl.d_row_means) return RT_OK;
+    const int64_t cells = (int64_t)h->cfg.n_streams * h->N;
+    hipLaunchKernelGGL(row_means_from_partials, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, sl.d_psum, chunks, h->cfg.n_streams, h->N,
+                       n_seg, sl.d_row_means);
+    RT_HIP(h, hipGetLastError());
+    return RT_OK;
+}
+
 int ensure_dense_spec(rt_handle *h) {
     if (h->d_spec) return RT_OK;
     const size_t bytes = (size_t)h->cfg.n_streams * (size_t)h->max_seg * (size_t)h->N * sizeof(float);
@@ -700,6 +724,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         a.chunks = 1;
         launch_detect_dense(h, h->cfg.n_streams, h->s_scan, a);
         RT_HIP(h, hipGetLastError());
+        { const int rc2 = enqueue_row_means(h, sl, 1, c.n_seg, h->s_scan); if (rc2 != RT_OK) return rc2; }
         RT_HIP(h, hipEventRecord(sl.ev_done, h->s_scan));
         return RT_OK;
     }
@@ -918,6 +943,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         hipLaunchKernelGGL(finalize_records, dim3(S), dim3(256), 0, sd, a);
     }
     RT_HIP(h, hipGetLastError());
+    { const int rc = enqueue_row_means(h, sl, sp.blocks_per_stream, c.n_seg, sd); if (rc != RT_OK) return rc; }
     // no readback: the call's last workgroup wrote the counter words to pinned host memory
     RT_HIP(h, hipEventRecord(sl.ev_done, sd));
     return RT_OK;
@@ -955,6 +981,8 @@ int enqueue_partial_dense(rt_handle *h, Slot &sl, int n_list, unsigned long long
     a.stream_list = sl.h_list;
     launch_detect_dense(h, n_list, h->s_scan, a);
     RT_HIP(h, hipGetLastError());
+    // (the dense scan rewrote the listed streams' partial sums -- the same chunks --, the others stand: all S rows again)
+    { const int rc = enqueue_row_means(h, sl, sp.blocks_per_stream, c.n_seg, h->s_scan); if (rc != RT_OK) return rc; }
     RT_HIP(h, hipEventRecord(sl.ev_done, h->s_scan));
     return RT_OK;
 }
@@ -1063,6 +1091,16 @@ Slot *oldest_pending(rt_handle *h) {
     for (auto &sl : h->slot)
         if (sl.call.pending && (!best || sl.call.seq < best->call.seq)) best = &sl;
     return best;
+}
+
+// rt_fetch_row_means: the row means of the call just delivered are the ones to hand out (an rt_extract has none) ...
+void keep_row_means(rt_handle *h, const Slot &sl) { h->rm_slot = sl.call.is_extract ? kRowMeansExtract : (int)(&sl - h->slot); }
+
+// ... until the next rt_process*, rt_extract or rt_reset (in every lane: a lane that fails to enqueue leaves none behind either)
+void forget_row_means(rt_handle *h) {
+    h->rm_slot = kRowMeansNone;
+    if (h->f64) h->f64->rm_slot = kRowMeansNone;
+    for (rt_handle *k : h->kids) forget_row_means(k);
 }
 
 // forward one call to every lane; `call(kid, first stream of the kid)`; the first failure is reported.
@@ -1191,6 +1229,7 @@ void rt_destroy(rt_handle *h) {
         (void)hipHostFree(sl.h_dc_flag);
         (void)hipHostFree(sl.h_list);
         (void)hipHostFree(sl.h_total);
+        (void)hipFree(sl.d_row_means);
         if (sl.ev_begin) (void)hipEventDestroy(sl.ev_begin);
         if (sl.ev_first) (void)hipEventDestroy(sl.ev_first);
         if (sl.ev_scan) (void)hipEventDestroy(sl.ev_scan);
@@ -1709,6 +1748,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         std::memset(sl.h_dc_flag, 0, (size_t)S * sizeof(int32_t));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_list, (size_t)kMaxPartial * sizeof(int32_t)));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_total, sizeof(unsigned long long)));
+        if (cfg->flags & RT_FLAG_ROW_MEANS) RT_CREATE_HIP(hipMalloc(&sl.d_row_means, (size_t)S * N * sizeof(float)));
         RT_CREATE_HIP(hipEventCreate(&sl.ev_begin));
         RT_CREATE_HIP(hipEventCreateWithFlags(&sl.ev_first, hipEventDisableTiming));
         RT_CREATE_HIP(hipEventCreate(&sl.ev_scan));
@@ -1738,6 +1778,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
 
 int rt_reset(rt_handle *h) {
     if (!h) return RT_E_INVALID;
+    forget_row_means(h);
     if (h->f64) {
         h->f64->n_seg_last = -1;
         std::fill(h->f64->reset_pending.begin(), h->f64->reset_pending.end(), (uint8_t)0);
@@ -1836,6 +1877,7 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
 
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, bool u8) {
     if (!h) return RT_E_INVALID;
+    forget_row_means(h);
     if (h->f64) return process_f64(h, iq_dev, n_samples, stream_stride, u8, false);
     if (!h->kids.empty()) {
         const int64_t bytes = u8 ? 2 : (int64_t)sizeof(cf);
@@ -1956,6 +1998,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
 
 static int process_host_impl(rt_handle *h, const void *iq_host, int64_t n_samples, int64_t stream_stride, bool u8) {
     if (!h) return RT_E_INVALID;
+    forget_row_means(h);
     if (h->f64) return process_f64(h, iq_host, n_samples, stream_stride, u8, true);
     const size_t sample_bytes = u8 ? 2 : sizeof(cf);
     if (!h->kids.empty())
@@ -2002,6 +2045,7 @@ int rt_process_u8_host(rt_handle *h, const void *iq_u8_host, int64_t n_samples, 
 int rt_extract(rt_handle *h, const float *spec_dev, int32_t n_seg, int32_t n_bins, const float *last_dev,
                int32_t n_seg_last) {
     if (!h) return RT_E_INVALID;
+    forget_row_means(h);
     if (h->f64) return refuse_on_f64(h, "rt_extract", "rt_extract_f64");
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
@@ -2351,6 +2395,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
     } else if (total == 0) {
         c.pending = false;  // nothing to deliver
     }
+    if (!peek && !c.pending) keep_row_means(h, sl);
     // (out == NULL / cap == 0 with records available is a size query: the call stays pending)
     if (flags & kFlagRecOverflow) {
         h->err = "record capacity exceeded (record_capacity per stream, or the record pool could not grow); results truncated";
@@ -2394,6 +2439,7 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
         if (deliver && total && cap <= w) {
             // the caller's buffer is full: this lane's records are lost, but the call is consumed here as in the
             // lanes before it -- otherwise the lanes would be out of step from the next rt_fetch on
+            if (const Slot *o = oldest_pending(k)) keep_row_means(k, *o);  // (delivered, if not in full: its row means stand)
             discard_oldest(k);
         } else if (deliver) {
             size_t n = 0;
@@ -2481,6 +2527,57 @@ int rt_calibrate_read(rt_handle *h, const void *iq_dev, int64_t n_samples, int64
     launch_stft<3>(h, sp, h->cfg.n_streams * sp.blocks_per_stream, h->s_scan);
     RT_HIP(h, hipGetLastError());
     RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    return RT_OK;
+}
+
+// rt_fetch_row_means / _f64 (include/rt_analyze.h): the checks both make; `rm_slot` is the lane-less handle's (or the float64 state's)
+static int row_means_refused(rt_handle *h, const void *out, size_t n, int rm_slot) {
+    const char *why = nullptr;
+    if (!out) why = "null output";
+    else if (!(h->cfg.flags & RT_FLAG_ROW_MEANS)) why = "the handle was created without RT_FLAG_ROW_MEANS";
+    else if (n != (size_t)h->cfg.n_streams * (size_t)h->cfg.nperseg) why = "n must be n_streams * nperseg";
+    else if (rm_slot == kRowMeansExtract) why = "the call fetched last was an rt_extract: the caller holds its spectrogram";
+    else if (rm_slot < 0) why = "no row means: no call delivered by rt_fetch since the last rt_process*, rt_extract or rt_reset";
+    if (!why) return RT_OK;
+    h->err = std::string("rt_fetch_row_means: ") + why;
+    return RT_E_INVALID;
+}
+
+int rt_fetch_row_means(rt_handle *h, float *out, size_t n) {
+    if (!h) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_fetch_row_means", "rt_fetch_row_means_f64");
+    if (!h->kids.empty()) {
+        // every lane holds the row means of its streams: all of them are checked before anything is written
+        int rc = row_means_refused(h, out, n, 0);
+        for (size_t k = 0; k < h->kids.size() && rc == RT_OK; ++k) {
+            rt_handle *kid = h->kids[k];
+            rc = row_means_refused(kid, out, (size_t)kid->cfg.n_streams * (size_t)kid->cfg.nperseg, kid->rm_slot);
+            if (rc != RT_OK) h->err = kid->err;
+        }
+        if (rc != RT_OK) return rc;
+        for (size_t k = 0; k < h->kids.size(); ++k) {
+            rt_handle *kid = h->kids[k];
+            rc = rt_fetch_row_means(kid, out + (size_t)h->kid_base[k] * (size_t)h->cfg.nperseg, (size_t)kid->cfg.n_streams * (size_t)kid->cfg.nperseg);
+            if (rc != RT_OK) {
+                h->err = kid->err;
+                return rc;
+            }
+        }
+        return RT_OK;
+    }
+    const int rc = row_means_refused(h, out, n, h->rm_slot);
+    if (rc != RT_OK) return rc;
+    const Slot &sl = h->slot[h->rm_slot];
+    if (sl.call.n_seg == 0) {
+        std::fill(out, out + n, std::numeric_limits<float>::quiet_NaN());  // np.mean of an empty row
+        return RT_OK;
+    }
+    // The kernel wrote the slot's buffer before the call's ev_done, which the delivering rt_fetch waited for.  A copy on the null
+    // stream, which does not wait for the handle's (non-blocking) streams: the next call's kernels run on.  (Written into pinned
+    // host memory by the kernel instead, like the records, the row means cost 2.6 % at the reference's defaults and 8 % at
+    // config 5's share: 4 / 16 MB a call over the host link, behind the call's detection -- DESIGN.md section 4.10.)
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    RT_HIP(h, hipMemcpy(out, sl.d_row_means, n * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -2666,9 +2763,14 @@ int f64_enqueue(rt_handle *h, F64Slot &sl) {
         }
         RT_HIP(h, hipGetLastError());
     }
-    const F64DetectArgs a = f64_detect_args(h, sl);
+    F64DetectArgs a = f64_detect_args(h, sl);
     const int64_t rows = (int64_t)S * a.n_bins;
-    detect_f64<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(a);
+    if (sl.d_row_means && !sl.is_extract) {  // RT_FLAG_ROW_MEANS: every row's mean as well
+        a.row_means = sl.d_row_means;
+        detect_f64<true><<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(a);
+    } else {
+        detect_f64<false><<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(a);
+    }
     finalize_f64<<<(unsigned)S, 256, 0, st>>>(a);
     clear_counts_f64<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(sl.d_raw_count, S);
     RT_HIP(h, hipGetLastError());
@@ -2702,6 +2804,7 @@ static void destroy_f64(rt_handle *h) {
         (void)hipFree(sl.d_stage);
         (void)hipHostFree(sl.h_out);
         (void)hipHostFree(sl.h_meta);
+        (void)hipFree(sl.d_row_means);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     }
     (void)hipFree(f->d_window);
@@ -2904,6 +3007,7 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
         RT_F64_CREATE(hipMemset(sl.d_raw_count, 0, S * sizeof(int32_t)));
         RT_F64_CREATE(hipMalloc(&sl.d_no_last, S * sizeof(int32_t)));
         RT_F64_CREATE(hipHostMalloc(&sl.h_meta, (2 * S + 1) * sizeof(int32_t)));
+        if (cfg->flags & RT_FLAG_ROW_MEANS) RT_F64_CREATE(hipMalloc(&sl.d_row_means, S * (size_t)n * sizeof(double)));
         RT_F64_CREATE(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
         if (f64_slot_areas(h, sl, f->rec_cap) != RT_OK) {
             destroy_f64(h);
@@ -2954,6 +3058,7 @@ int rt_set_stream_params_f64(rt_handle *h, const double *threshold, const double
 
 int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t n_bins, const double *last_dev, int32_t n_seg_last) {
     if (!h) return RT_E_INVALID;
+    forget_row_means(h);
     if (!h->f64) {
         h->err = "rt_extract_f64 on a float32 handle: use rt_extract";
         return RT_E_INVALID;
@@ -3028,8 +3133,23 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     const size_t n = std::min(total, cap);
     if (n) std::memcpy(out, sl.h_out, n * sizeof(rt_record_f64));
     sl.pending = false;
+    f->rm_slot = sl.is_extract ? kRowMeansExtract : (int)(&sl - f->slot);
     if (truncated) return f64_err(h, RT_E_CAPACITY, "rt_extract_f64: a stream found more records than record_capacity");
     if (n < total) return f64_err(h, RT_E_CAPACITY, "output buffer too small: records lost");
+    return RT_OK;
+}
+
+int rt_fetch_row_means_f64(rt_handle *h, double *out, size_t n) {
+    if (!h) return RT_E_INVALID;
+    if (!h->f64) {
+        h->err = "rt_fetch_row_means_f64 on a float32 handle: use rt_fetch_row_means";
+        return RT_E_INVALID;
+    }
+    const int rc = row_means_refused(h, out, n, h->f64->rm_slot);
+    if (rc != RT_OK) return rc;
+    // (T == 0: detect_f64<true> divided an empty sum by zero -- NaN, as np.mean of an empty row; the copy as in rt_fetch_row_means)
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    RT_HIP(h, hipMemcpy(out, h->f64->slot[h->f64->rm_slot].d_row_means, n * sizeof(double), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -322,13 +322,14 @@ RT_HD void finish_run(const DetectParamsT<P> &p, int32_t b, int32_t e, typename 
 // Sequential scan of one bin's row of a dense spectrogram (analyze.py:357-450):
 // calls on_run(b, e, avg) for every maximal run of above-cells.  Returns false
 // when no cell reaches the absolute threshold (the row mean is then unused).
-// `row_sum` < 0 means "not known": the row is summed here.
+// `row_sum` < 0 means "not known": the row is summed here.  `sum_out` (or null): that sum, whatever the row holds
+// (RT_FLAG_ROW_MEANS: the float64 handle keeps every row's mean).
 // np.mean(row) (analyze.py:375) from the row's float64 sum: float32 rows as float32 (the sum rounded once), float64 rows in float64
 RT_HD float row_mean_of(double sum, int32_t T, float) { return (float)sum / (float)T; }
 RT_HD double row_mean_of(double sum, int32_t T, double) { return sum / (double)T; }
 
 template <class P, class Cur, class OnRun>
-RT_HD bool scan_dense_row(const DetectParamsT<P> &p, Cur cur, double row_sum, P *avg_out, OnRun on_run) {
+RT_HD bool scan_dense_row(const DetectParamsT<P> &p, Cur cur, double row_sum, P *avg_out, OnRun on_run, double *sum_out = nullptr) {
     const int32_t T = p.n_seg;
     double sum = 0.0;
     bool any = false;
@@ -337,6 +338,7 @@ RT_HD bool scan_dense_row(const DetectParamsT<P> &p, Cur cur, double row_sum, P 
         sum += (double)v;
         any |= !(v < p.thr);
     }
+    if (sum_out) *sum_out = row_sum >= 0.0 ? row_sum : sum;
     if (!any) return false;
     if (row_sum >= 0.0) sum = row_sum;
     const P avg = row_mean_of(sum, T, P());  // np.mean(row) (analyze.py:375)

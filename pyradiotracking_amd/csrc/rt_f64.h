@@ -183,6 +183,7 @@ struct F64DetectArgs {
     rt_record_f64 *out;         // the call's records, ordered by (stream, fi, start): stream s from out_off[s]
     int32_t *out_off;           // [S + 1] each stream's first record in `out`, and the total
     int32_t *out_count;         // [S] records each stream wanted (copied to the host behind the call)
+    double *row_means;          // RT_FLAG_ROW_MEANS: [S][F] every row's mean (the call slot's device buffer), written by detect_f64<true> only
 };
 
 __device__ __forceinline__ DetectParams64 f64_stream_params(const F64DetectArgs &a, int s) {
@@ -204,6 +205,8 @@ struct F64Prev {
 
 // One thread per (stream, bin): rt::scan_dense_row on float64 cells (neighbouring threads read neighbouring bins: whole lines),
 // each run through rt::gate_run; a plateau goes to the stream's raw area with its start, end and the row mean.
+// ROW_MEANS (RT_FLAG_ROW_MEANS): every row's mean -- from the sum scan_dense_row forms anyway -- to a.row_means as well.
+template <bool ROW_MEANS>
 __global__ __launch_bounds__(256) void detect_f64(const F64DetectArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)a.n_streams * a.n_bins) return;
@@ -227,7 +230,13 @@ __global__ __launch_bounds__(256) void detect_f64(const F64DetectArgs a) {
         r.row_mean = av;
         a.raw[(int64_t)s * a.rec_cap + k] = r;
     };
-    scan_dense_row(dp, cur, -1.0, &avg, on_run);
+    if constexpr (ROW_MEANS) {
+        double sum = 0.0;
+        scan_dense_row(dp, cur, -1.0, &avg, on_run, &sum);
+        a.row_means[i] = row_mean_of(sum, dp.n_seg, double());  // (the record's row_mean: the same expression on the same sum)
+    } else {
+        scan_dense_row(dp, cur, -1.0, &avg, on_run);
+    }
 }
 
 // np.max / np.mean / np.std(dB(.)) of one plateau by one wave: rt::run_stats' 64 interleaved partials and halving fold, in float64

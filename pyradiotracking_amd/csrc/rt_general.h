@@ -381,5 +381,16 @@ __global__ __launch_bounds__(256) void row_sums_dense(const float *spec, float *
     psum[i] = (float)acc;
 }
 
+// RT_FLAG_ROW_MEANS: np.mean of every (stream, bin) row of a call (analyze.py:375) from its partial row sums, the detectors'
+// own expression (row_sum_from_partials, rounded once, / T in float32) -- so every record's row_mean is its entry bit for bit.
+// A thread per (stream, bin), neighbouring threads on neighbouring bins: each partial row is read in whole lines.  `out` is the
+// call slot's device buffer [S][N] (include/rt_analyze.h: rt_fetch_row_means copies it).
+__global__ __launch_bounds__(256) void row_means_from_partials(const float *psum, int chunks, int n_streams, int n_bins, int n_seg, float *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)n_streams * n_bins) return;
+    const int s = (int)(i / n_bins), bin = (int)(i % n_bins);
+    out[i] = (float)row_sum_from_partials(psum + (int64_t)s * chunks * n_bins + bin, chunks, n_bins) / (float)n_seg;
+}
+
 }  // namespace rt
 #endif
