@@ -136,6 +136,7 @@ typedef struct rt_config {
                                      the form (nperseg <= 256); ignored elsewhere */
 #define RT_FLAG_NO_GROUP_DETECT 8u /* ... never */
 #define RT_FLAG_ROW_MEANS 16u      /* keep each call's row means for rt_fetch_row_means[_f64] (rt_create and rt_create_f64) */
+#define RT_FLAG_RECORD_CELLS 32u   /* keep the cells of every record of a call for rt_fetch_record_cells[_f64] (rt_create and rt_create_f64) */
 
 /*
  * One extracted plateau, before it becomes a Signal (analyze.py:442-449).
@@ -368,6 +369,36 @@ int rt_spectrogram_f64(rt_handle *h, const void *iq_dev, int64_t n_samples, int6
  */
 int rt_fetch_row_means(rt_handle *h, float *out, size_t n);       /* float32 handle */
 int rt_fetch_row_means_f64(rt_handle *h, double *out, size_t n);  /* float64 handle */
+
+/*
+ * ---- record cells: the spectrogram cells behind every record (additive within ABI version 6) ----
+ * For every plateau it reports the reference forms `data`, the cells the plateau consists of (analyze.py:437-440:
+ * `fft[start:end]`, or `concatenate((_spectrogram_last[fi][start:], fft[:end]))` when it reaches back into the previous
+ * buffer), reduces it to max / mean / std (analyze.py:442-445) and drops it.  A handle created with RT_FLAG_RECORD_CELLS
+ * (rt_create or rt_create_f64) keeps those cells for every record of a call; without the flag nothing is allocated and no
+ * launch is added, removed or changed.
+ *   - the call concerned is the one the last rt_fetch / rt_fetch_f64 delivered IN FULL (RT_OK, cap >= *n_out).  Record i below
+ *     is the i-th record that fetch wrote: all of them, shadowed ones included, in (stream, fi, start) order, over all lanes.
+ *   - `offsets`: HOST memory, n_offsets == n_records + 1 entries (or NULL: not wanted); offsets[0] == 0,
+ *     offsets[i + 1] - offsets[i] == end_i - start_i, *n_cells == offsets[n_records].
+ *   - `cells`: HOST memory, `cap` entries.  Cell k of record i -- cells[offsets[i] + k] -- is the spectrogram cell of bin fi_i at
+ *     segment start_i + k; a negative segment counts back from the end of the stream's previous buffer, exactly as
+ *     rt_record.start does (analyze.py:383-388, 438).  Linear power, uncalibrated, in the handle's arithmetic.
+ *   - each cell is bit for bit the value the detection used for the record's decision and statistics -- gathered from the map,
+ *     the candidate lists and the look-back columns the detection read, not computed again.  Hence for every record
+ *     max(cells) == max_p exactly (NaN as np.max propagates it), and mean_p, std_db are the canonical statistics (64 interleaved
+ *     float64 partials, cell k to partial k mod 64, folded by halving) of them.
+ *   - cells == NULL or cap == 0: a size query (*n_cells and, if given, the offsets); nothing is consumed.  The data stay valid
+ *     until the next rt_process*, rt_extract* or rt_reset on the handle; with two calls in flight: process k, process k + 1,
+ *     fetch k, then the cells of k.  cap < *n_cells with a buffer: RT_E_CAPACITY, nothing written to `cells`.
+ *   - a call without records: offsets[0] = 0, *n_cells = 0, RT_OK.
+ *   - RT_E_INVALID: null handle or `n_cells`, a wrong n_offsets, a handle without the flag, no delivered call (or one no longer
+ *     valid, see above), a call delivered truncated (RT_E_CAPACITY from the fetch), a delivered rt_extract* call (the caller
+ *     holds that map), and the float32 entry on a float64 handle or the reverse.  Refused before anything is launched or copied.
+ *   - RT_E_NOMEM: the device could not hold the call's cells (the pool grows on demand, inside rt_fetch, like the record pool).
+ */
+int rt_fetch_record_cells(rt_handle *h, int64_t *offsets, size_t n_offsets, float *cells, size_t cap, size_t *n_cells);       /* float32 handle */
+int rt_fetch_record_cells_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, double *cells, size_t cap, size_t *n_cells);  /* float64 handle */
 
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */

@@ -30,6 +30,7 @@ RT_FLAG_NO_LIN_DETREND = 2  # subtract the segment mean before windowing even fo
 RT_FLAG_GROUP_DETECT = 4  # sparse detection by groups of candidate lists at any number of streams (default: from 1 024 streams per handle)
 RT_FLAG_NO_GROUP_DETECT = 8  # ... never
 RT_FLAG_ROW_MEANS = 16  # keep each call's row means (every bin's noise level) for rt_fetch_row_means[_f64]
+RT_FLAG_RECORD_CELLS = 32  # keep the spectrogram cells of every record of a call (the reference's ``data``) for rt_fetch_record_cells[_f64]
 
 SUPPORTED_NPERSEG = tuple(range(8, 8193)) + (16384,)  # 8 .. 8192 and 16384 (32 .. 4096 powers of two: the fused scans; everything else: general transforms, dense path)
 FUSED_NPERSEG = (256, 512, 1024, 2048, 4096)
@@ -152,6 +153,8 @@ ABI_SYMBOLS = (
     "rt_spectrogram_f64",
     "rt_fetch_row_means",
     "rt_fetch_row_means_f64",
+    "rt_fetch_record_cells",
+    "rt_fetch_record_cells_f64",
 )
 
 _lib = None
@@ -214,6 +217,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_spectrogram_f64.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
     lib.rt_fetch_row_means.argtypes = [vp, vp, C.c_size_t]
     lib.rt_fetch_row_means_f64.argtypes = [vp, vp, C.c_size_t]
+    lib.rt_fetch_record_cells.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.rt_fetch_record_cells_f64.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -307,11 +312,12 @@ class NativeAnalyzer:
         group_detect: Optional[bool] = None,
         precision: str = "float32",
         row_means: bool = False,
+        record_cells: bool = False,
     ):
         """``precision="float64"``: a float64 handle (``rt_create_f64``) -- ``window_f32`` then holds the float64 window and
         ``scale`` / ``threshold`` / ``snr_threshold`` / ``calibration_db`` are passed on as float64, never rounded to float32;
         the analysis takes complex128 (or uint8) IQ and the records are ``RECORD_F64_DTYPE``.  ``row_means``:
-        ``RT_FLAG_ROW_MEANS`` (``fetch_row_means``)."""
+        ``RT_FLAG_ROW_MEANS`` (``fetch_row_means``); ``record_cells``: ``RT_FLAG_RECORD_CELLS`` (``fetch_record_cells``)."""
         if precision not in ("float32", "float64"):
             raise ValueError(f"precision must be 'float32' or 'float64', not {precision!r}")
         self.f64 = precision == "float64"
@@ -339,7 +345,8 @@ class NativeAnalyzer:
         cfg.segs_per_chunk = segs_per_chunk
         cfg.flags = ((RT_FLAG_TIMING if timing else 0) | (RT_FLAG_NO_LIN_DETREND if subtract_first else 0)
                      | (0 if group_detect is None else RT_FLAG_GROUP_DETECT if group_detect else RT_FLAG_NO_GROUP_DETECT)
-                     | (RT_FLAG_ROW_MEANS if row_means else 0))
+                     | (RT_FLAG_ROW_MEANS if row_means else 0)
+                     | (RT_FLAG_RECORD_CELLS if record_cells else 0))
         cfg.hip_stream = hip_stream
         cfg.lanes = int(lanes)
         cfg.record_pool = int(record_pool)
@@ -449,7 +456,21 @@ class NativeAnalyzer:
             self.last_truncated = True
         if rc != RT_OK and not (allow_truncated and rc == RT_E_CAPACITY):
             self._check(rc)
+        self._n_fetched = len(out)
         return out
+
+    def fetch_record_cells(self):
+        """``rt_fetch_record_cells`` (``rt_fetch_record_cells_f64`` on a float64 handle): ``(offsets, cells)`` of the call
+        ``fetch`` delivered last (in full) -- ``offsets`` int64 ``[n_records + 1]``, ``cells`` float32 (float64); the cells of
+        record ``i``, the reference's ``data`` of that plateau (analyze.py:437-440), are ``cells[offsets[i]:offsets[i + 1]]``."""
+        fn = self._lib.rt_fetch_record_cells_f64 if self.f64 else self._lib.rt_fetch_record_cells
+        offsets = np.zeros(getattr(self, "_n_fetched", 0) + 1, dtype=np.int64)
+        n = C.c_size_t(0)
+        self._check(fn(self._handle, offsets.ctypes.data, offsets.size, None, 0, C.byref(n)))  # size query
+        cells = np.empty(n.value, dtype=np.float64 if self.f64 else np.float32)
+        if n.value:
+            self._check(fn(self._handle, offsets.ctypes.data, offsets.size, cells.ctypes.data, cells.size, C.byref(n)))
+        return offsets, cells
 
     def fetch_row_means(self) -> np.ndarray:
         """``rt_fetch_row_means`` (``rt_fetch_row_means_f64`` on a float64 handle): ``[S, nperseg]`` float32 (float64), the

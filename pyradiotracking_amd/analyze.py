@@ -276,9 +276,14 @@ class BatchSignalAnalyzer:
         group_detect: Optional[bool] = None,
         precision: str = "float32",
         row_means: bool = False,
+        record_cells: bool = False,
         **kwargs,
     ):
-        """``row_means`` (``RT_FLAG_ROW_MEANS``): keep every bin's noise level, the reference's ``freq_avg = np.mean(row)``
+        """``record_cells`` (``RT_FLAG_RECORD_CELLS``): keep the spectrogram cells every record of a call consists of -- the
+        reference's ``data`` (analyze.py:437-440), which it reduces to max / mean / std and drops -- for
+        :meth:`fetch_record_cells`.
+
+        ``row_means`` (``RT_FLAG_ROW_MEANS``): keep every bin's noise level, the reference's ``freq_avg = np.mean(row)``
         (analyze.py:373-375), of each call for :meth:`fetch_row_means` -- not only of the bins a signal was found in.
 
         ``precision``: ``"float32"`` (default) analyses complex64; ``"float64"`` runs the reference's float64 arithmetic on
@@ -374,6 +379,7 @@ class BatchSignalAnalyzer:
             group_detect=group_detect,
             precision=precision,
             row_means=bool(row_means),
+            record_cells=bool(record_cells),
         )
         if per_stream_cal is not None:
             self.calibration_db = per_stream_cal
@@ -509,6 +515,16 @@ class BatchSignalAnalyzer:
         spectrogram can be cut off: that raises unless ``allow_truncated`` (then ``native.last_truncated`` tells)."""
         return self._native.fetch(allow_truncated)
 
+    def fetch_record_cells(self):
+        """``(offsets, cells)``: the spectrogram cells behind every record of the call :meth:`fetch_records` (or
+        :meth:`process_batch`) returned last -- all records, shadowed ones included, in the order they were returned.
+        ``cells[offsets[i]:offsets[i + 1]]`` (float32, float64 with ``precision="float64"``) is the reference's ``data`` of
+        record ``i`` (analyze.py:437-440): bin ``fi`` at segments ``start .. end - 1``, negative segments from the end of the
+        stream's previous buffer; linear power, uncalibrated, bit for bit what the detection used (``max(data) == max_p``).
+        Needs ``record_cells=True``; raises ``NativeError`` (``RT_E_INVALID``) once another buffer was enqueued or the analyzer
+        reset, after an ``extract_signals`` call and after a truncated fetch."""
+        return self._native.fetch_record_cells()
+
     def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
         """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
         reference's noise figure (analyze.py:373-375) -- over the buffer of the call :meth:`fetch_records` (or
@@ -579,15 +595,21 @@ class SignalAnalyzer:
         mode: str = "auto",
         precision: str = "float32",
         row_means: bool = False,
+        record_cells: bool = False,
         **kwargs,
     ):
-        """``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer).
+        """``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
+        queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
+
+        ``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer).
         ``row_means=True``: after every buffer ``noise_dbw`` holds the noise level of every bin (``[fft_nperseg]``, dBW, fftfreq
         order) -- what the reference prints as the ``noise`` of a Signal (analyze.py:446), for all bins."""
         self.device = device
         self.precision = precision
         self.row_means = bool(row_means)
         self.noise_dbw: Optional[np.ndarray] = None
+        self.record_cells = bool(record_cells)
+        self.signal_data: Optional[List[np.ndarray]] = None
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -637,6 +659,7 @@ class SignalAnalyzer:
             mode=mode,
             precision=precision,
             row_means=self.row_means,
+            record_cells=self.record_cells,
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
             **{k: kwargs[k] for k in ("record_capacity", "record_pool", "hot_capacity", "group_detect") if k in kwargs},
         )
@@ -700,10 +723,11 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = None
+        self.noise_dbw = self.signal_data = None
         self._batch.enqueue_bytes(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
+        self._keep_cells(rec["shadowed"] == 0)
         rec = rec[rec["shadowed"] == 0]
         [self.consume_signal(s) for s in self._decoder.signals(rec, [self.device], [ts_start])]
         return None
@@ -714,8 +738,15 @@ class SignalAnalyzer:
         buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = None
-        out = self._batch.process_batch(buf, [ts_start], filtered=filtered, lazy=False)[0]  # (one stream: its Signal objects, as the reference returns them)
+        self.noise_dbw = self.signal_data = None
+        if self.record_cells:  # (process_batch, with the records kept for the cells' shadow flags)
+            self._batch.enqueue(buf)
+            rec = self._batch.fetch_records()
+            keep = rec["shadowed"] == 0 if filtered else np.ones(len(rec), dtype=bool)
+            out = self._decoder.signals(rec[keep], [self.device], [ts_start])
+            self._keep_cells(keep)
+        else:
+            out = self._batch.process_batch(buf, [ts_start], filtered=filtered, lazy=False)[0]  # (one stream: its Signal objects, as the reference returns them)
         self._keep_noise()
         logger.info(
             f"SDR {self.device} recv {len(buffer)}, {len(out)} signals, "
@@ -726,6 +757,12 @@ class SignalAnalyzer:
     def _keep_noise(self):
         if self.row_means:
             self.noise_dbw = self._batch.fetch_row_means(dbw=True)[0]
+
+    def _keep_cells(self, keep):
+        """``signal_data``: the cells of the records ``keep`` selects (those whose signals go to the queue), in their order."""
+        if self.record_cells:
+            offsets, cells = self._batch.fetch_record_cells()
+            self.signal_data = [cells[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
 
     def reset(self):
         self._batch.reset()
@@ -747,7 +784,7 @@ class SignalAnalyzer:
         dense detect kernel (``rt_extract``).  The time axis must be the one
         SciPy produces for ``fft_nperseg`` / ``sample_rate`` (hop = nperseg/fs);
         ``freqs`` is used as given."""
-        self.noise_dbw = None  # (the caller holds this map: no row means of it)
+        self.noise_dbw = self.signal_data = None  # (the caller holds this map: no row means, no cells of it)
         spec = np.asarray(spectrogram)
         n_bins, n_seg = spec.shape
         if n_seg == 0:

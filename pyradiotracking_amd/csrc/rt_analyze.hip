@@ -31,6 +31,7 @@
 #include "rt_kernels.h"
 #include "rt_general.h"
 #include "rt_f64.h"
+#include "rt_cells.h"
 
 using namespace rt;
 
@@ -54,6 +55,8 @@ constexpr int kTails = 3;
 constexpr int64_t kInitialPoolRecords = 4 << 20;  // pinned record pool per slot at rt_create unless rt_config.record_pool says otherwise
                                                   // (4 Mi records = 160 MiB); a call that needs more grows it (grow_pool), up to what
                                                   // n_streams * record_capacity can ever deliver
+constexpr int64_t kInitialPoolCells = 4 << 20;    // RT_FLAG_RECORD_CELLS: device cell pool per slot at rt_create (or 16 cells per record of the record pool,
+                                                  // if that is less); a call that needs more grows it (grow_cells) and is analysed again
 constexpr int kMaxPartial = 32;  // AUTO: up to this many overflowing streams of a batch are re-run dense on their own
 
 struct CallCtx {
@@ -79,6 +82,7 @@ struct CallCtx {
     bool level_settled = false;  // AUTO's level bookkeeping for this call is done (fetch_one passes over a call twice: size query / peek, then delivery)
     bool ran_lin = false;     // its scans detrended by linearity (fetch_one: analysed again if the guard marks a stream)
     uint64_t sub_epoch = 0;   // rt_handle::sub_epoch when its kernels were enqueued
+    int cells_grown = 0;      // times the slot's cell pool was enlarged for this call and the call analysed again (RT_FLAG_RECORD_CELLS)
     // handle state before this call (restored when the call is rolled back: a later lane failed to enqueue)
     int prev_tail_cur = 0, prev_n_seg_last = -1, prev_dense_sticky = 0, prev_minsum_slot = -1;
 };
@@ -119,6 +123,12 @@ struct Slot {
     int32_t *h_list = nullptr;                                 // pinned, [kMaxPartial]: the streams of a partial dense re-run (read by the kernels)
     unsigned long long *h_total = nullptr;                     // pinned: records allocated so far, uploaded before a partial re-run
     float *d_row_means = nullptr;                              // [S][N] the call's row means (RT_FLAG_ROW_MEANS only; rt_fetch_row_means copies them)
+    // RT_FLAG_RECORD_CELLS only (rt_cells.h; rt_fetch_record_cells copies the cells):
+    float *d_cells = nullptr;                                  // the cells of the call's records, in delivery order
+    int64_t cell_cap = 0;                                      // cells the pool holds (grows on demand, grow_cells)
+    uint32_t *d_hot_kept = nullptr;                            // [S][kBuckets] the candidate counters as they were in front of finalize_records
+    long long *d_stream_cells = nullptr, *d_stream_base = nullptr;  // [S] cells of each stream's records / its first cell in the pool
+    unsigned long long *h_cells_info = nullptr;                // pinned: [0] cells the call wants, [1] a record's cells were not all found
     hipEvent_t ev_begin = nullptr, ev_first = nullptr, ev_scan = nullptr, ev_done = nullptr;  // first launch; end of the first scan; end of the scans; end of the call
     CallCtx call;
 };
@@ -145,6 +155,11 @@ struct F64Slot {
     int32_t *h_meta = nullptr;                         // pinned, device-visible: [S + 1] offsets + total, then [S] wanted
     void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host
     size_t stage_bytes = 0;
+    // RT_FLAG_RECORD_CELLS only, as in Slot:
+    double *d_cells = nullptr;
+    int64_t cell_cap = 0;
+    long long *d_stream_cells = nullptr, *d_stream_base = nullptr;
+    unsigned long long *h_cells_info = nullptr;
     hipEvent_t ev_done = nullptr;
 };
 struct F64State {
@@ -164,6 +179,8 @@ struct F64State {
     uint64_t n_calls = 0;
     F64Slot slot[kSlots];
     int rm_slot = -1;  // the slot of the call rt_fetch_f64 delivered last, while its row means are valid (kRowMeansNone / kRowMeansExtract)
+    bool cells_full = false;  // ... and that call was delivered in full (rt_fetch_record_cells_f64)
+    int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
 };
 
 }  // namespace
@@ -260,6 +277,8 @@ struct rt_handle {
     // RT_FLAG_ROW_MEANS: the slot of the call rt_fetch delivered last, while its row means are valid (rt_fetch_row_means) --
     // or kRowMeansNone (none delivered, or an rt_process* / rt_extract / rt_reset since), or kRowMeansExtract
     int rm_slot = -1;
+    bool cells_full = false;  // RT_FLAG_RECORD_CELLS: ... and that call was delivered in full: its cells can be fetched (rt_fetch_record_cells)
+    int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
 
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
 };
@@ -663,6 +682,72 @@ int enqueue_row_means(rt_handle *h, Slot &sl, int chunks, int n_seg, hipStream_t
     return RT_OK;
 }
 
+// RT_FLAG_RECORD_CELLS: the cells of the call's final records (rt_cells.h) into the slot's pool -- where enqueue_row_means is
+// called, on the same stream behind the call's detection: the dense map is one per handle and belongs to the next call as soon
+// as this one's kernels are through, so the gather is never left to fetch time.  `spec`: the dense map the detection read
+// (`stream_list` / `n_list`: the streams a partial re-run's map holds, the others keep their candidate lists), or null on the
+// sparse levels.  Every analysis of a call gathers all its records again, so the pool follows the analysis that is delivered.
+template <class P, class Rec>
+void launch_record_cells(const CellsArgs<P, Rec> &a, hipStream_t st) {
+    hipLaunchKernelGGL((cells_stream_totals<P, Rec>), dim3(a.n_streams), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(cells_stream_bases, dim3(1), dim3(kCellsScanBlock), 0, st, a.stream_cells, a.stream_base, a.n_streams, a.info);
+    hipLaunchKernelGGL((cells_gather<P, Rec>), dim3(a.n_streams), dim3(256), 0, st, a);
+}
+
+int enqueue_record_cells(rt_handle *h, Slot &sl, const float *spec, const int32_t *stream_list, int n_list, hipStream_t st) {
+    if (!sl.d_cells) return RT_OK;
+    const CallCtx &c = sl.call;
+    CellsArgs<float, rt_record> a{};
+    a.records = sl.h_records;
+    a.rec_off = sl.h_rec_offset;
+    a.rec_cnt = sl.h_rec_count;
+    a.stage = sl.d_raw;
+    a.rec_cap = h->rec_cap;
+    a.n_streams = h->cfg.n_streams;
+    a.n_bins = h->N;
+    a.n_seg = c.n_seg;
+    a.spec = spec;
+    a.stream_list = stream_list;
+    a.n_list = n_list;
+    a.prev = h->d_tail[c.tail_read];
+    a.prev_cols = h->K;
+    a.hot = sl.d_hot;
+    a.hot_count = sl.d_hot_kept;
+    a.hot_cap = h->hot_cap;
+    a.tbits = key_tbits(c.n_seg);
+    a.stream_cells = sl.d_stream_cells;
+    a.stream_base = sl.d_stream_base;
+    a.cells = sl.d_cells;
+    a.cell_cap = sl.cell_cap;
+    a.info = sl.h_cells_info;
+    launch_record_cells(a, st);
+    RT_HIP(h, hipGetLastError());
+    return RT_OK;
+}
+
+// A call's records hold more cells than the slot's pool: a larger one (nothing to keep: the call is analysed again).  Only
+// while none of the slot's kernels is in flight.  Failure leaves the old pool in place.
+template <class P>
+int grow_cells(rt_handle *h, P *&pool, int64_t &cap, int64_t want) {
+    if (want <= cap) return RT_OK;
+    P *p = nullptr;
+    int64_t n = want + want / 4;
+    hipError_t e = hipMalloc(&p, (size_t)n * sizeof(P));
+    if (e != hipSuccess) {
+        n = want;
+        e = hipMalloc(&p, (size_t)n * sizeof(P));
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = "cell pool of " + std::to_string(n) + " cells: " + hipGetErrorString(e);
+        return RT_E_NOMEM;
+    }
+    (void)hipFree(pool);
+    pool = p;
+    cap = n;
+    return RT_OK;
+}
+
 int ensure_dense_spec(rt_handle *h) {
     if (h->d_spec) return RT_OK;
     const size_t bytes = (size_t)h->cfg.n_streams * (size_t)h->max_seg * (size_t)h->N * sizeof(float);
@@ -725,6 +810,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         launch_detect_dense(h, h->cfg.n_streams, h->s_scan, a);
         RT_HIP(h, hipGetLastError());
         { const int rc2 = enqueue_row_means(h, sl, 1, c.n_seg, h->s_scan); if (rc2 != RT_OK) return rc2; }
+        { const int rc2 = enqueue_record_cells(h, sl, h->d_spec, nullptr, 0, h->s_scan); if (rc2 != RT_OK) return rc2; }
         RT_HIP(h, hipEventRecord(sl.ev_done, h->s_scan));
         return RT_OK;
     }
@@ -940,10 +1026,13 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         // (the large instantiation returns at once for a stream without a bucket over kSmallBucket cells; the per-bucket counters
         // are put back to zero by finalize_records)
         hipLaunchKernelGGL(detect_bucket<true>, dim3(S), dim3(256), h->lds_large, sd, a);  // one workgroup per stream: its 16 buckets in turn
+        // (RT_FLAG_RECORD_CELLS: the gather needs the lists' lengths, which finalize_records puts back to zero)
+        if (sl.d_cells) hipLaunchKernelGGL(cells_keep_counts, dim3((S * kBuckets + 255) / 256), dim3(256), 0, sd, sl.d_hot_count, sl.d_hot_kept, S * kBuckets);
         hipLaunchKernelGGL(finalize_records, dim3(S), dim3(256), 0, sd, a);
     }
     RT_HIP(h, hipGetLastError());
     { const int rc = enqueue_row_means(h, sl, sp.blocks_per_stream, c.n_seg, sd); if (rc != RT_OK) return rc; }
+    { const int rc = enqueue_record_cells(h, sl, dense ? h->d_spec : nullptr, nullptr, 0, sd); if (rc != RT_OK) return rc; }
     // no readback: the call's last workgroup wrote the counter words to pinned host memory
     RT_HIP(h, hipEventRecord(sl.ev_done, sd));
     return RT_OK;
@@ -983,6 +1072,8 @@ int enqueue_partial_dense(rt_handle *h, Slot &sl, int n_list, unsigned long long
     RT_HIP(h, hipGetLastError());
     // (the dense scan rewrote the listed streams' partial sums -- the same chunks --, the others stand: all S rows again)
     { const int rc = enqueue_row_means(h, sl, sp.blocks_per_stream, c.n_seg, h->s_scan); if (rc != RT_OK) return rc; }
+    // (the listed streams' cells from this map, the others' from their candidate lists, whose kept counters stand)
+    { const int rc = enqueue_record_cells(h, sl, h->d_spec_part, sl.h_list, n_list, h->s_scan); if (rc != RT_OK) return rc; }
     RT_HIP(h, hipEventRecord(sl.ev_done, h->s_scan));
     return RT_OK;
 }
@@ -1052,6 +1143,9 @@ int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
     if (sl.pool_cap < h->pool_want && !sl.call.pending) {
         // the other slot's pool had to grow: this one follows before its next call needs it (best effort)
         if (sl.call.seq == 0 || hipEventSynchronize(sl.ev_done) == hipSuccess) (void)grow_pool(h, sl, h->pool_want);
+    }
+    if (sl.d_cells && sl.cell_cap < h->cells_want && !sl.call.pending) {  // (the cell pool likewise)
+        if (sl.call.seq == 0 || hipEventSynchronize(sl.ev_done) == hipSuccess) (void)grow_cells(h, sl.d_cells, sl.cell_cap, h->cells_want);
     }
     *saved = sl.call;  // put back if the new call fails before it has launched anything
     sl.call = CallCtx{};
@@ -1230,6 +1324,11 @@ void rt_destroy(rt_handle *h) {
         (void)hipHostFree(sl.h_list);
         (void)hipHostFree(sl.h_total);
         (void)hipFree(sl.d_row_means);
+        (void)hipFree(sl.d_cells);
+        (void)hipFree(sl.d_hot_kept);
+        (void)hipFree(sl.d_stream_cells);
+        (void)hipFree(sl.d_stream_base);
+        (void)hipHostFree(sl.h_cells_info);
         if (sl.ev_begin) (void)hipEventDestroy(sl.ev_begin);
         if (sl.ev_first) (void)hipEventDestroy(sl.ev_first);
         if (sl.ev_scan) (void)hipEventDestroy(sl.ev_scan);
@@ -1749,6 +1848,16 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         RT_CREATE_HIP(hipHostMalloc(&sl.h_list, (size_t)kMaxPartial * sizeof(int32_t)));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_total, sizeof(unsigned long long)));
         if (cfg->flags & RT_FLAG_ROW_MEANS) RT_CREATE_HIP(hipMalloc(&sl.d_row_means, (size_t)S * N * sizeof(float)));
+        if (cfg->flags & RT_FLAG_RECORD_CELLS) {
+            sl.cell_cap = std::max<int64_t>(64, std::min<int64_t>(kInitialPoolCells, 16 * sl.pool_cap));
+            RT_CREATE_HIP(hipMalloc(&sl.d_cells, (size_t)sl.cell_cap * sizeof(float)));
+            RT_CREATE_HIP(hipMalloc(&sl.d_hot_kept, (size_t)S * kBuckets * sizeof(uint32_t)));
+            RT_CREATE_HIP(hipMemset(sl.d_hot_kept, 0, (size_t)S * kBuckets * sizeof(uint32_t)));
+            RT_CREATE_HIP(hipMalloc(&sl.d_stream_cells, (size_t)S * sizeof(long long)));
+            RT_CREATE_HIP(hipMalloc(&sl.d_stream_base, (size_t)S * sizeof(long long)));
+            RT_CREATE_HIP(hipHostMalloc(&sl.h_cells_info, 2 * sizeof(unsigned long long)));
+            sl.h_cells_info[0] = sl.h_cells_info[1] = 0ull;
+        }
         RT_CREATE_HIP(hipEventCreate(&sl.ev_begin));
         RT_CREATE_HIP(hipEventCreateWithFlags(&sl.ev_first, hipEventDisableTiming));
         RT_CREATE_HIP(hipEventCreate(&sl.ev_scan));
@@ -2319,6 +2428,23 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
             continue;
         }
     }
+    // RT_FLAG_RECORD_CELLS: the call's records hold more cells than the slot's pool (word 0 of the gather's words): the pool grows
+    // and the call is analysed again, like a call that outgrew the record pool -- the gather reads a map that is gone by now.
+    if (sl.d_cells && !c.is_extract && c.n_seg > 0 && sl.h_cells_info[0] > (unsigned long long)sl.cell_cap && c.cells_grown < 3) {
+        if (grow_cells(h, sl.d_cells, sl.cell_cap, (int64_t)sl.h_cells_info[0]) == RT_OK) {
+            RT_TRACE_FETCH(h, sl, "cell pool grown");
+            ++c.cells_grown;
+            h->cells_want = std::max(h->cells_want, sl.cell_cap);
+            for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
+            c.n_dense_streams = 0;
+            int rc = before_rerun(h, sl);
+            if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used);
+            if (rc != RT_OK) return rc;
+            RT_HIP(h, hipEventSynchronize(sl.ev_done));
+            flags = sl.h_counters[2];
+            continue;
+        }
+    }
     break;
   }
     RT_TRACE_FETCH(h, sl, "settled");
@@ -2395,7 +2521,10 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
     } else if (total == 0) {
         c.pending = false;  // nothing to deliver
     }
-    if (!peek && !c.pending) keep_row_means(h, sl);
+    if (!peek && !c.pending) {
+        keep_row_means(h, sl);
+        h->cells_full = cap >= total && !(flags & kFlagRecOverflow);  // (rt_fetch_record_cells: only of a call delivered in full)
+    }
     // (out == NULL / cap == 0 with records available is a size query: the call stays pending)
     if (flags & kFlagRecOverflow) {
         h->err = "record capacity exceeded (record_capacity per stream, or the record pool could not grow); results truncated";
@@ -2440,6 +2569,7 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
             // the caller's buffer is full: this lane's records are lost, but the call is consumed here as in the
             // lanes before it -- otherwise the lanes would be out of step from the next rt_fetch on
             if (const Slot *o = oldest_pending(k)) keep_row_means(k, *o);  // (delivered, if not in full: its row means stand)
+            k->cells_full = false;
             discard_oldest(k);
         } else if (deliver) {
             size_t n = 0;
@@ -2578,6 +2708,116 @@ int rt_fetch_row_means(rt_handle *h, float *out, size_t n) {
     // config 5's share: 4 / 16 MB a call over the host link, behind the call's detection -- DESIGN.md section 4.10.)
     RT_HIP(h, hipSetDevice(h->cfg.device));
     RT_HIP(h, hipMemcpy(out, sl.d_row_means, n * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// ---- rt_fetch_record_cells / _f64 (include/rt_analyze.h) ----
+// the checks both entries make on a lane-less handle (or a lane); `rm_slot` / `full`: the handle's, or the float64 state's
+static int record_cells_refused(rt_handle *h, int rm_slot, bool full) {
+    const char *why = nullptr;
+    if (!(h->cfg.flags & RT_FLAG_RECORD_CELLS)) why = "the handle was created without RT_FLAG_RECORD_CELLS";
+    else if (rm_slot == kRowMeansExtract) why = "the call fetched last was an rt_extract: the caller holds its spectrogram";
+    else if (rm_slot < 0) why = "no cells: no call delivered by rt_fetch since the last rt_process*, rt_extract or rt_reset";
+    else if (!full) why = "the call fetched last was delivered truncated";
+    if (!why) return RT_OK;
+    h->err = std::string("rt_fetch_record_cells: ") + why;
+    return RT_E_INVALID;
+}
+
+// what the gather left for a delivered call of `total` cells: the pool could not grow, or a record's cells were not on its list
+static int record_cells_state(rt_handle *h, const unsigned long long *info, int64_t cell_cap, size_t total) {
+    if (total == 0) return RT_OK;
+    if (info[0] > (unsigned long long)cell_cap) {
+        h->err = "rt_fetch_record_cells: the cell pool could not grow to " + std::to_string(info[0]) + " cells";
+        return RT_E_NOMEM;
+    }
+    if (info[1] != 0ull || info[0] != (unsigned long long)total) {
+        h->err = "internal: a record's cells are not all on its candidate list";
+        return RT_E_HIP;
+    }
+    return RT_OK;
+}
+
+// records / cells of the call a lane-less float32 handle delivered last (its slot's result arrays stand until the slot's next call)
+static void record_cells_count(const Slot &sl, int S, size_t *n_rec, size_t *n_cells) {
+    size_t nr = 0, nc = 0;
+    for (int s = 0; s < S; ++s) {
+        const rt_record *r = sl.h_records + sl.h_rec_offset[s];
+        for (int i = 0; i < sl.h_rec_count[s]; ++i) nc += (size_t)(r[i].end - r[i].start);
+        nr += (size_t)sl.h_rec_count[s];
+    }
+    *n_rec = nr;
+    *n_cells = nc;
+}
+
+// ... its offsets behind `base` cells (offsets[0] is the caller's), and its cells
+static int record_cells_deliver(rt_handle *h, int64_t *offsets, int64_t base, float *cells, size_t n_cells) {
+    const Slot &sl = h->slot[h->rm_slot];
+    if (offsets) {
+        size_t w = 0;
+        for (int s = 0; s < h->cfg.n_streams; ++s) {
+            const rt_record *r = sl.h_records + sl.h_rec_offset[s];
+            for (int i = 0; i < sl.h_rec_count[s]; ++i) {
+                base += r[i].end - r[i].start;
+                offsets[++w] = base;
+            }
+        }
+    }
+    if (cells && n_cells) {
+        // (the gather ran before the call's ev_done, which the delivering rt_fetch waited for; a copy on the null stream, as
+        // rt_fetch_row_means copies: the next call's kernels run on)
+        RT_HIP(h, hipSetDevice(h->cfg.device));
+        RT_HIP(h, hipMemcpy(cells, sl.d_cells, n_cells * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
+int rt_fetch_record_cells(rt_handle *h, int64_t *offsets, size_t n_offsets, float *cells, size_t cap, size_t *n_cells) {
+    if (!h || !n_cells) return RT_E_INVALID;
+    *n_cells = 0;
+    if (h->f64) return refuse_on_f64(h, "rt_fetch_record_cells", "rt_fetch_record_cells_f64");
+    std::vector<rt_handle *> one{h};
+    const std::vector<rt_handle *> &lanes = h->kids.empty() ? one : h->kids;
+    if (!(h->cfg.flags & RT_FLAG_RECORD_CELLS)) return record_cells_refused(h, 0, true);
+    // every lane holds the cells of its streams: all of them are checked and counted before anything is written
+    std::vector<size_t> n_rec(lanes.size()), n_cell(lanes.size());
+    size_t records = 0, total = 0;
+    for (size_t k = 0; k < lanes.size(); ++k) {
+        rt_handle *l = lanes[k];
+        int rc = record_cells_refused(l, l->rm_slot, l->cells_full);
+        if (rc == RT_OK) {
+            const Slot &sl = l->slot[l->rm_slot];
+            record_cells_count(sl, l->cfg.n_streams, &n_rec[k], &n_cell[k]);
+            rc = record_cells_state(l, sl.h_cells_info, sl.cell_cap, n_cell[k]);
+        }
+        if (rc != RT_OK) {
+            h->err = l->err;
+            return rc;
+        }
+        records += n_rec[k];
+        total += n_cell[k];
+    }
+    if (offsets && n_offsets != records + 1) {
+        h->err = "rt_fetch_record_cells: n_offsets must be the number of records the last rt_fetch delivered, plus one";
+        return RT_E_INVALID;
+    }
+    *n_cells = total;
+    const bool query = !cells || cap == 0;
+    if (!query && cap < total) {
+        h->err = "rt_fetch_record_cells: output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    if (offsets) offsets[0] = 0;
+    size_t r0 = 0, c0 = 0;
+    for (size_t k = 0; k < lanes.size(); ++k) {
+        const int rc = record_cells_deliver(lanes[k], offsets ? offsets + r0 : nullptr, (int64_t)c0, query ? nullptr : cells + c0, n_cell[k]);
+        if (rc != RT_OK) {
+            h->err = lanes[k]->err;
+            return rc;
+        }
+        r0 += n_rec[k];
+        c0 += n_cell[k];
+    }
     return RT_OK;
 }
 
@@ -2773,6 +3013,26 @@ int f64_enqueue(rt_handle *h, F64Slot &sl) {
     }
     finalize_f64<<<(unsigned)S, 256, 0, st>>>(a);
     clear_counts_f64<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(sl.d_raw_count, S);
+    if (sl.d_cells && !sl.is_extract && sl.n_seg > 0) {
+        // RT_FLAG_RECORD_CELLS: the cells finalize_f64 has just read, behind it on the call's stream (the map is the next call's after that)
+        CellsArgs<double, rt_record_f64> ca{};
+        ca.records = sl.h_out;
+        ca.rec_off = sl.h_meta;  // [S + 1], packed
+        ca.stage = sl.d_raw;
+        ca.rec_cap = sl.rec_cap;
+        ca.n_streams = S;
+        ca.n_bins = a.n_bins;
+        ca.n_seg = sl.n_seg;
+        ca.spec = a.spec;
+        ca.prev = a.prev;
+        ca.prev_cols = a.prev_cols;
+        ca.stream_cells = sl.d_stream_cells;
+        ca.stream_base = sl.d_stream_base;
+        ca.cells = sl.d_cells;
+        ca.cell_cap = sl.cell_cap;
+        ca.info = sl.h_cells_info;
+        launch_record_cells(ca, st);
+    }
     RT_HIP(h, hipGetLastError());
     RT_HIP(h, hipEventRecord(sl.ev_done, st));
     return RT_OK;
@@ -2783,6 +3043,10 @@ int f64_start(rt_handle *h, F64Slot &sl) {
     if (sl.rec_cap < f->rec_cap) {  // (another call grew the capacity since this slot's areas were made)
         const int rc = f64_slot_areas(h, sl, f->rec_cap);
         if (rc != RT_OK) return rc;
+    }
+    if (sl.d_cells && sl.cell_cap < f->cells_want) {  // (... or the cell pool; best effort)
+        if (h->s_scan) (void)hipStreamSynchronize(h->s_scan);
+        (void)grow_cells(h, sl.d_cells, sl.cell_cap, f->cells_want);
     }
     const int rc = f64_enqueue(h, sl);
     if (rc != RT_OK) return rc;
@@ -2805,6 +3069,10 @@ static void destroy_f64(rt_handle *h) {
         (void)hipHostFree(sl.h_out);
         (void)hipHostFree(sl.h_meta);
         (void)hipFree(sl.d_row_means);
+        (void)hipFree(sl.d_cells);
+        (void)hipFree(sl.d_stream_cells);
+        (void)hipFree(sl.d_stream_base);
+        (void)hipHostFree(sl.h_cells_info);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     }
     (void)hipFree(f->d_window);
@@ -3008,6 +3276,14 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
         RT_F64_CREATE(hipMalloc(&sl.d_no_last, S * sizeof(int32_t)));
         RT_F64_CREATE(hipHostMalloc(&sl.h_meta, (2 * S + 1) * sizeof(int32_t)));
         if (cfg->flags & RT_FLAG_ROW_MEANS) RT_F64_CREATE(hipMalloc(&sl.d_row_means, S * (size_t)n * sizeof(double)));
+        if (cfg->flags & RT_FLAG_RECORD_CELLS) {
+            sl.cell_cap = std::max<int64_t>(64, std::min<int64_t>(kInitialPoolCells, 16 * (int64_t)S * f->rec_cap));
+            RT_F64_CREATE(hipMalloc(&sl.d_cells, (size_t)sl.cell_cap * sizeof(double)));
+            RT_F64_CREATE(hipMalloc(&sl.d_stream_cells, S * sizeof(long long)));
+            RT_F64_CREATE(hipMalloc(&sl.d_stream_base, S * sizeof(long long)));
+            RT_F64_CREATE(hipHostMalloc(&sl.h_cells_info, 2 * sizeof(unsigned long long)));
+            sl.h_cells_info[0] = sl.h_cells_info[1] = 0ull;
+        }
         RT_F64_CREATE(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
         if (f64_slot_areas(h, sl, f->rec_cap) != RT_OK) {
             destroy_f64(h);
@@ -3102,7 +3378,21 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     for (;;) {
         int wanted = 0;
         for (int s = 0; s < S; ++s) wanted = std::max(wanted, sl.h_meta[S + 1 + s]);
-        if (wanted <= sl.rec_cap) break;
+        if (wanted <= sl.rec_cap) {
+            // RT_FLAG_RECORD_CELLS: more cells than the slot's pool holds -- a larger pool, and the call analysed again (the map may be the next call's by now)
+            if (sl.d_cells && !sl.is_extract && sl.n_seg > 0 && sl.h_cells_info[0] > (unsigned long long)sl.cell_cap &&
+                grow_cells(h, sl.d_cells, sl.cell_cap, (int64_t)sl.h_cells_info[0]) == RT_OK) {
+                f->cells_want = std::max(f->cells_want, sl.cell_cap);
+                const int rc = f64_enqueue(h, sl);
+                if (rc != RT_OK) {
+                    sl.pending = false;
+                    return rc;
+                }
+                RT_HIP(h, hipEventSynchronize(sl.ev_done));
+                continue;
+            }
+            break;
+        }
         if (sl.is_extract) {  // (the library does not keep the caller's spectrogram: the first records of each stream that fit)
             truncated = true;
             break;
@@ -3134,6 +3424,7 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     if (n) std::memcpy(out, sl.h_out, n * sizeof(rt_record_f64));
     sl.pending = false;
     f->rm_slot = sl.is_extract ? kRowMeansExtract : (int)(&sl - f->slot);
+    f->cells_full = !truncated && n == total;
     if (truncated) return f64_err(h, RT_E_CAPACITY, "rt_extract_f64: a stream found more records than record_capacity");
     if (n < total) return f64_err(h, RT_E_CAPACITY, "output buffer too small: records lost");
     return RT_OK;
@@ -3150,6 +3441,43 @@ int rt_fetch_row_means_f64(rt_handle *h, double *out, size_t n) {
     // (T == 0: detect_f64<true> divided an empty sum by zero -- NaN, as np.mean of an empty row; the copy as in rt_fetch_row_means)
     RT_HIP(h, hipSetDevice(h->cfg.device));
     RT_HIP(h, hipMemcpy(out, h->f64->slot[h->f64->rm_slot].d_row_means, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_fetch_record_cells_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, double *cells, size_t cap, size_t *n_cells) {
+    if (!h || !n_cells) return RT_E_INVALID;
+    *n_cells = 0;
+    if (!h->f64) {
+        h->err = "rt_fetch_record_cells_f64 on a float32 handle: use rt_fetch_record_cells";
+        return RT_E_INVALID;
+    }
+    F64State *f = h->f64;
+    int rc = record_cells_refused(h, f->rm_slot, f->cells_full);
+    if (rc != RT_OK) return rc;
+    const F64Slot &sl = f->slot[f->rm_slot];
+    const size_t records = (size_t)sl.h_meta[h->cfg.n_streams];  // (delivered in full: all of the packed output)
+    size_t total = 0;
+    for (size_t i = 0; i < records; ++i) total += (size_t)(sl.h_out[i].end - sl.h_out[i].start);
+    rc = record_cells_state(h, sl.h_cells_info, sl.cell_cap, total);
+    if (rc != RT_OK) return rc;
+    if (offsets && n_offsets != records + 1) {
+        h->err = "rt_fetch_record_cells: n_offsets must be the number of records the last rt_fetch_f64 delivered, plus one";
+        return RT_E_INVALID;
+    }
+    *n_cells = total;
+    const bool query = !cells || cap == 0;
+    if (!query && cap < total) {
+        h->err = "rt_fetch_record_cells: output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    if (offsets) {
+        offsets[0] = 0;
+        for (size_t i = 0; i < records; ++i) offsets[i + 1] = offsets[i] + (sl.h_out[i].end - sl.h_out[i].start);
+    }
+    if (!query && total) {
+        RT_HIP(h, hipSetDevice(h->cfg.device));
+        RT_HIP(h, hipMemcpy(cells, sl.d_cells, total * sizeof(double), hipMemcpyDeviceToHost));
+    }
     return RT_OK;
 }
 

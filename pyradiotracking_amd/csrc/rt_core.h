@@ -306,6 +306,15 @@ RT_HD bool gate_run(const DetectParamsT<P> &p, int32_t b, int32_t e, typename sa
     return true;
 }
 
+// Cell `t` of a plateau's `data` (analyze.py:437-440) for bin `fi`: segment t >= 0 of the buffer's map `map` ([T][F], this
+// stream's), t < 0 counted back from the end of the previous buffer (analyze.py:438: `_spectrogram_last[fi][start:]`), of which
+// `prev` holds the last `prev_cols` columns ([prev_cols][F], this stream's: a whole previous map, or the look-back tail).  The
+// one indexing rule of the dense detectors' statistics, the record-cells gather (rt_cells.h) and the host check.
+template <class P>
+RT_HD P record_cell(const P *map, const P *prev, int32_t prev_cols, int32_t F, int32_t fi, int32_t t) {
+    return t < 0 ? prev[((int64_t)prev_cols + t) * F + fi] : map[(int64_t)t * F + fi];
+}
+
 // gate + statistics for one run, sequentially (host check; the kernels gate
 // per thread and compute the statistics wave-cooperatively in the same order)
 template <class P, class Cur, class Prev, class Emit>

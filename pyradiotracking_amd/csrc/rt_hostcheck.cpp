@@ -191,3 +191,31 @@ int hc_extract_f64(const double *spec, int n_seg, int n_bins, const double *last
 }
 
 }  // extern "C"
+
+// The record-cells convention (include/rt_analyze.h: rt_fetch_record_cells) on an explicit map + previous map for ONE stream:
+// rt::record_cell -- the indexing the gather kernels use (rt_cells.h) -- for the n records `rec` (hc_extract's).
+// offsets[n + 1], cells[cap]; returns the number of cells (nothing is written to `cells` if cap is too small).
+namespace {
+template <class P, class Rec>
+long long record_cells_host(const P *spec, int n_bins, const P *last, int n_seg_last, const Rec *rec, int n, long long *offsets, P *cells, long long cap) {
+    long long total = 0;
+    offsets[0] = 0;
+    for (int i = 0; i < n; ++i) offsets[i + 1] = (total += rec[i].end - rec[i].start);
+    if (total > cap) return total;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < rec[i].end - rec[i].start; ++k)
+            cells[offsets[i] + k] = record_cell(spec, last, last ? n_seg_last : 0, n_bins, rec[i].fi, rec[i].start + k);
+    return total;
+}
+}  // namespace
+
+extern "C" {
+long long hc_record_cells(const float *spec, int n_bins, const float *last, int n_seg_last, const rt_record *rec, int n, long long *offsets,
+                          float *cells, long long cap) {
+    return record_cells_host(spec, n_bins, last, n_seg_last, rec, n, offsets, cells, cap);
+}
+long long hc_record_cells_f64(const double *spec, int n_bins, const double *last, int n_seg_last, const rt_record_f64 *rec, int n,
+                              long long *offsets, double *cells, long long cap) {
+    return record_cells_host(spec, n_bins, last, n_seg_last, rec, n, offsets, cells, cap);
+}
+}  // extern "C"
