@@ -400,6 +400,32 @@ int rt_fetch_row_means_f64(rt_handle *h, double *out, size_t n);  /* float64 han
 int rt_fetch_record_cells(rt_handle *h, int64_t *offsets, size_t n_offsets, float *cells, size_t cap, size_t *n_cells);       /* float32 handle */
 int rt_fetch_record_cells_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, double *cells, size_t cap, size_t *n_cells);  /* float64 handle */
 
+/*
+ * ---- per-stream detection settings (additive within ABI version 6) ----
+ * In the reference every SDR is a SignalAnalyzer of its own, built from its own snr_threshold_db, signal_min_duration_ms and
+ * signal_max_duration_ms (analyze.py:113-116) beside the threshold and calibration of rt_set_stream_params.  These entries give
+ * every stream of a handle its own values: HOST arrays of n_streams entries (linear SNR threshold; durations in seconds), each
+ * of which may be NULL = rt_config's value for every stream.  All three NULL puts the handle back to rt_config's values.
+ *   - rt_config.min_duration_s / max_duration_s are the handle's ENVELOPE: every stream's minimum must be >= the handle's, every
+ *     maximum <= the handle's (RT_E_INVALID otherwise, the message names the stream).  The look-back depth, the availability of
+ *     RT_MODE_PREFILTER and the run length of RT_MODE_RUNFILTER stay derived from the envelope -- supersets for every stream --
+ *     while the detection applies each stream's own probe stride (analyze.py:354, 364) and duration gates (:427-433), and
+ *     RT_MODE_RUNFILTER's per-bin thresholds take each stream's own SNR threshold.
+ *   - RT_E_INVALID as well: a snr_threshold that is <= 0 or not finite, a duration that is not finite, unfetched calls pending
+ *     (as rt_set_stream_params: AUTO may still re-run them with the settings they were enqueued with), the float32 entry on a
+ *     float64 handle or the reverse.  min > max is accepted, as the reference accepts it: such a stream finds nothing.  Every
+ *     refusal happens before anything is copied or launched; the handle then analyses on as if the call had not been made.
+ *   - a stream whose settings CHANGE starts its next buffer without look-back, as after rt_reset_stream (a new setting is a new
+ *     analyzer in the reference, analyze.py:128); streams whose values stay keep theirs.
+ *   - applies to rt_process* and rt_extract* calls enqueued afterwards; with cfg.lanes > 1 every lane takes its slice.
+ *   - a handle on which the entry was never called launches exactly what it launched before: no kernel, copy or allocation.
+ * sample_rate, nperseg and the window stay per handle: they set the scan's geometry and scale.
+ */
+int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const double *min_duration_s,
+                           const double *max_duration_s);      /* float32 handle */
+int rt_set_stream_settings_f64(rt_handle *h, const double *snr_threshold, const double *min_duration_s,
+                               const double *max_duration_s);  /* float64 handle */
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

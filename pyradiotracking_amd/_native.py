@@ -155,6 +155,8 @@ ABI_SYMBOLS = (
     "rt_fetch_row_means_f64",
     "rt_fetch_record_cells",
     "rt_fetch_record_cells_f64",
+    "rt_set_stream_settings",
+    "rt_set_stream_settings_f64",
 )
 
 _lib = None
@@ -219,6 +221,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_fetch_row_means_f64.argtypes = [vp, vp, C.c_size_t]
     lib.rt_fetch_record_cells.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
     lib.rt_fetch_record_cells_f64.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.rt_set_stream_settings.argtypes = [vp, vp, vp, vp]
+    lib.rt_set_stream_settings_f64.argtypes = [vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -410,6 +414,25 @@ class NativeAnalyzer:
                 self._handle, t.ctypes.data if t is not None else None, c.ctypes.data if c is not None else None
             )
         )
+
+    def set_stream_settings(self, snr_threshold: Optional[np.ndarray], min_duration_s: Optional[np.ndarray],
+                            max_duration_s: Optional[np.ndarray]):
+        """``rt_set_stream_settings`` (``rt_set_stream_settings_f64`` on a float64 handle): per-stream linear SNR thresholds
+        (float32 ``[S]``, float64 on a float64 handle) and duration gates in seconds (float64 ``[S]``), each or None = the
+        handle's value.  The durations must lie inside the handle's ``min_duration_s`` / ``max_duration_s``."""
+
+        def arr(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != (self.n_streams,):
+                raise ValueError(f"expected {self.n_streams} values")
+            return a
+
+        s = arr(snr_threshold, np.float64 if self.f64 else np.float32)
+        lo, hi = arr(min_duration_s, np.float64), arr(max_duration_s, np.float64)
+        fn = self._lib.rt_set_stream_settings_f64 if self.f64 else self._lib.rt_set_stream_settings
+        self._check(fn(self._handle, *(a.ctypes.data if a is not None else None for a in (s, lo, hi))))
 
     # -- analysis ---------------------------------------------------------
     def process_device(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):

@@ -84,8 +84,8 @@ class _RecordDecoder:
     """rt_record arrays -> Signal field columns (analyze.py:360, 420-449)."""
 
     def __init__(self, nperseg: int, sample_rate, center_freq, calibration_db, f64: bool = False):
-        """``calibration_db``: one value, or one per stream (the reference has one analyzer and one
-        calibration per SDR, __main__.py:140-141).  ``f64``: the records are float64 (a float64 handle), and so are the
+        """``calibration_db`` and ``center_freq``: one value, or one per stream (the reference has one analyzer, one
+        calibration and one centre frequency per SDR, __main__.py:140-141, analyze.py:360).  ``f64``: the records are float64 (a float64 handle), and so are the
         calibrations subtracted from them."""
         self.f64 = f64
         self.nperseg = nperseg
@@ -125,7 +125,10 @@ class _RecordDecoder:
             avg_dbw = dB(rec["mean_p"]) - cal  # :444
             noise_dbw = self.noise_dbw(rec["row_mean"])  # :446
             snr_db = dB(rec["mean_p"] / rec["row_mean"])  # :447
-        frequency = (self.freqs if freqs is None else np.asarray(freqs))[rec["fi"]] + self.center_freq  # :360
+        center = self.center_freq
+        if np.ndim(center):
+            center = np.asarray(center)[rec["stream"]]  # every stream's SDR is tuned on its own
+        frequency = (self.freqs if freqs is None else np.asarray(freqs))[rec["fi"]] + center  # :360
         return t_start, duration_s, frequency, max_dbw, avg_dbw, rec["std_db"], noise_dbw, snr_db
 
     def signal_columns(self, rec: np.ndarray, device_names: Sequence[str], ts_starts: Sequence[datetime.datetime]):
@@ -241,8 +244,21 @@ def default_lanes(fft_nperseg: int, n_streams: int) -> int:
     return 3 if (fft_nperseg <= 512 and 3 <= n_streams < 16384) else 1
 
 
+def _per_stream(name: str, value, devices: Sequence[str]):
+    """A keyword that may be given per stream: ``None`` for a scalar, else its values as a list (one per device)."""
+    if not np.ndim(value):
+        return None
+    values = list(value)
+    if len(values) != len(devices):
+        raise ValueError(f"{name} values {values} do not match devices {list(devices)}")
+    return values
+
+
 class BatchSignalAnalyzer:
-    """``S`` independent analyzers sharing one configuration, one GPU.
+    """``S`` independent analyzers on one GPU, one per device as in the reference (``__main__.py:140-141``).  They share the
+    STFT -- ``sample_rate``, ``fft_nperseg`` and ``fft_window`` set the scan's geometry and scale and stay per handle -- while
+    every detection setting may differ per stream: ``calibration_db``, ``signal_threshold_dbw``, ``snr_threshold_db``,
+    ``signal_min_duration_ms``, ``signal_max_duration_ms`` and ``center_freq`` each take one value, or one per device.
 
     ``process_batch`` is the batched body of the reference callback
     (analyze.py:231-251, 268) for one buffer of every stream.  Per-stream
@@ -319,12 +335,25 @@ class BatchSignalAnalyzer:
 
         ``calibration_db`` may be a sequence with one value per stream: every SDR of the reference has its own
         analyzer and calibration (``__main__.py:140-141``), and with it its own absolute threshold
-        (``analyze.py:115``); the kernels then take the thresholds per stream (``rt_set_stream_params``)."""
+        (``analyze.py:115``); the kernels then take the thresholds per stream (``rt_set_stream_params``).
+
+        ``signal_threshold_dbw``, ``snr_threshold_db``, ``signal_min_duration_ms``, ``signal_max_duration_ms`` and
+        ``center_freq`` may be sequences as well, one value per device (``analyze.py:113-116``, ``:360``): the attributes
+        (``signal_threshold``, ``snr_threshold``, ``signal_min_duration``, ...) are then lists.  The handle is created with the
+        envelope of the durations -- the smallest minimum, the largest maximum: look-back depth and pre-filters derive from it
+        -- and every stream is gated by its own values (``rt_set_stream_settings``); :meth:`set_stream_settings` changes them
+        later, inside that envelope."""
+        self.devices = [str(d) for d in devices]
+        # (a sequence of the wrong length is refused before anything native is touched)
+        per_thr = _per_stream("signal_threshold_dbw", signal_threshold_dbw, self.devices)
+        per_snr = _per_stream("snr_threshold_db", snr_threshold_db, self.devices)
+        per_min = _per_stream("signal_min_duration_ms", signal_min_duration_ms, self.devices)
+        per_max = _per_stream("signal_max_duration_ms", signal_max_duration_ms, self.devices)
+        per_center = _per_stream("center_freq", center_freq, self.devices)
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
         self.precision = precision
         f64 = precision == "float64"
-        self.devices = [str(d) for d in devices]
         per_stream_cal = None
         if np.ndim(calibration_db):
             per_stream_cal = [float(c) for c in calibration_db]
@@ -333,16 +362,20 @@ class BatchSignalAnalyzer:
             calibration_db = per_stream_cal[0]
         self.calibration_db = calibration_db
         self.sample_rate = sample_rate
-        self.center_freq = center_freq
+        self.center_freq = per_center if per_center is not None else center_freq
         if sdr_callback_length is None:  # analyze.py:108-109
             sdr_callback_length = sample_rate
         self.sdr_callback_length = int(sdr_callback_length)
         self.fft_nperseg = fft_nperseg
         self.fft_window = fft_window
-        self.signal_min_duration = signal_min_duration_ms / 1000  # :113
-        self.signal_max_duration = signal_max_duration_ms / 1000  # :114
-        self.signal_threshold = from_dB(signal_threshold_dbw + calibration_db)  # :115
-        self.snr_threshold = from_dB(snr_threshold_db)  # :116
+        # per-stream values as lists; the handle's own (rt_config) are the envelope of the durations and the first stream's thresholds
+        self.signal_min_duration = [v / 1000 for v in per_min] if per_min else signal_min_duration_ms / 1000  # :113
+        self.signal_max_duration = [v / 1000 for v in per_max] if per_max else signal_max_duration_ms / 1000  # :114
+        self.snr_threshold = [from_dB(v) for v in per_snr] if per_snr else from_dB(snr_threshold_db)  # :116
+        self._min_envelope = min(self.signal_min_duration) if per_min else self.signal_min_duration
+        self._max_envelope = max(self.signal_max_duration) if per_max else self.signal_max_duration
+        snr0 = self.snr_threshold[0] if per_snr else self.snr_threshold
+        self.signal_threshold = from_dB((per_thr[0] if per_thr else signal_threshold_dbw) + calibration_db)  # :115
 
         if f64:
             win32, scale32 = stft_constants_f64(fft_window, fft_nperseg, sample_rate)
@@ -361,10 +394,10 @@ class BatchSignalAnalyzer:
             scale=float(scale32),
             # thresholds are compared against float32 data in float32; a float64 handle keeps the Python floats
             threshold=float(self.signal_threshold) if f64 else float(np.float32(self.signal_threshold)),
-            snr_threshold=float(self.snr_threshold) if f64 else float(np.float32(self.snr_threshold)),
+            snr_threshold=float(snr0) if f64 else float(np.float32(snr0)),
             calibration_db=calibration_db,
-            min_duration_s=self.signal_min_duration,
-            max_duration_s=self.signal_max_duration,
+            min_duration_s=self._min_envelope,
+            max_duration_s=self._max_envelope,
             device=gpu,
             mode={"auto": _native.RT_MODE_AUTO, "dense": _native.RT_MODE_DENSE, "sparse": _native.RT_MODE_SPARSE, "prefilter": _native.RT_MODE_PREFILTER,
                   "runfilter": _native.RT_MODE_RUNFILTER}[mode],
@@ -381,16 +414,21 @@ class BatchSignalAnalyzer:
             row_means=bool(row_means),
             record_cells=bool(record_cells),
         )
-        if per_stream_cal is not None:
-            self.calibration_db = per_stream_cal
-            self.signal_threshold = [from_dB(signal_threshold_dbw + c) for c in per_stream_cal]  # :115, per SDR
+        if per_stream_cal is not None or per_thr is not None:
+            n = len(self.devices)
+            cals = per_stream_cal if per_stream_cal is not None else [calibration_db] * n
+            dbws = per_thr if per_thr is not None else [signal_threshold_dbw] * n
+            self.signal_threshold = [from_dB(t + c) for t, c in zip(dbws, cals)]  # :115, per SDR
+            if per_stream_cal is not None:
+                self.calibration_db = per_stream_cal
+            cal_arr = None if per_stream_cal is None else np.array(per_stream_cal, dtype=np.float64 if f64 else np.float32)
             if f64:
-                self._native.set_stream_params(np.array(self.signal_threshold, dtype=np.float64), np.array(per_stream_cal, dtype=np.float64))
+                self._native.set_stream_params(np.array(self.signal_threshold, dtype=np.float64), cal_arr)
             else:
-                self._native.set_stream_params(
-                    np.array(self.signal_threshold, dtype=np.float64).astype(np.float32), np.array(per_stream_cal, dtype=np.float32)
-                )
-        self._decoder = _RecordDecoder(fft_nperseg, sample_rate, center_freq, self.calibration_db, f64=f64)
+                self._native.set_stream_params(np.array(self.signal_threshold, dtype=np.float64).astype(np.float32), cal_arr)
+        if per_snr is not None or per_min is not None or per_max is not None:
+            self._push_stream_settings()
+        self._decoder = _RecordDecoder(fft_nperseg, sample_rate, self.center_freq, self.calibration_db, f64=f64)
         self.decoder = self._decoder  # record -> field conversion, shared with pyradiotracking_amd.match
         self.gpu = gpu
         self._hip_stream = hip_stream
@@ -414,6 +452,47 @@ class BatchSignalAnalyzer:
         """``_spectrogram_last = None`` for one stream: its SDR was restarted, i.e. the reference would have
         replaced its analyzer by a fresh one (``__main__.py:185-190``)."""
         self._native.reset_stream(stream)
+
+    def _push_stream_settings(self):
+        """The per-stream attributes -> ``rt_set_stream_settings`` (scalars stay the handle's own: null arrays).  The SNR
+        threshold is rounded as the handle compares it: float32 on a float32 handle, like the scalar path; Python floats on a
+        float64 handle."""
+        f64 = self.precision == "float64"
+        snr = lo = hi = None
+        if np.ndim(self.snr_threshold):
+            snr = np.array(self.snr_threshold, dtype=np.float64)
+            if not f64:
+                snr = snr.astype(np.float32)
+        if np.ndim(self.signal_min_duration):
+            lo = np.array(self.signal_min_duration, dtype=np.float64)
+        if np.ndim(self.signal_max_duration):
+            hi = np.array(self.signal_max_duration, dtype=np.float64)
+        self._native.set_stream_settings(snr, lo, hi)
+
+    def set_stream_settings(self, snr_threshold_db=None, signal_min_duration_ms=None, signal_max_duration_ms=None):
+        """Change the streams' SNR thresholds and duration gates (``rt_set_stream_settings``): each argument one value for
+        every stream, one per device, or ``None`` = as it is.  The durations must stay inside the envelope the analyzer was
+        built with (smallest minimum, largest maximum); no call may be pending.  A stream whose settings change starts its
+        next buffer without look-back -- in the reference new settings mean a new analyzer (``analyze.py:113-116, 128``) --,
+        the others keep theirs.  A refused call (``ValueError`` for a wrong length, ``NativeError`` otherwise) changes nothing."""
+        n = len(self.devices)
+
+        def values(name, v, conv):
+            per = _per_stream(name, v, self.devices)
+            return [conv(x) for x in (per if per is not None else [v] * n)]
+
+        old = (self.snr_threshold, self.signal_min_duration, self.signal_max_duration)
+        if snr_threshold_db is not None:
+            self.snr_threshold = values("snr_threshold_db", snr_threshold_db, from_dB)
+        if signal_min_duration_ms is not None:
+            self.signal_min_duration = values("signal_min_duration_ms", signal_min_duration_ms, lambda x: x / 1000)
+        if signal_max_duration_ms is not None:
+            self.signal_max_duration = values("signal_max_duration_ms", signal_max_duration_ms, lambda x: x / 1000)
+        try:
+            self._push_stream_settings()
+        except Exception:
+            self.snr_threshold, self.signal_min_duration, self.signal_max_duration = old
+            raise
 
     def close(self):
         """Destroy the native handle (waits for everything in flight), then let go of the device tensors the

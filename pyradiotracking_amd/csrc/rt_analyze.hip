@@ -173,6 +173,8 @@ struct F64State {
     int tail_cur = 0, n_seg_last = -1;
     double *d_thr_s = nullptr, *d_cal_s = nullptr;
     std::vector<double> h_thr_s;
+    StreamSettings64 *d_set_s = nullptr;  // [S] rt_set_stream_settings_f64, or null: rt_config's for every stream
+    std::vector<StreamSettings64> h_set_s;
     std::vector<uint8_t> reset_pending;
     bool any_reset = false;
     int rec_cap = 1024;
@@ -265,6 +267,10 @@ struct rt_handle {
     std::vector<uint8_t> reset_pending;  // [S] streams whose look-back is dropped at the next rt_process
     bool any_reset_pending = false;
     float *d_thr_s = nullptr, *d_cal_s = nullptr;  // [S] per-stream thresholds / calibration (rt_set_stream_params)
+    // [S] per-stream snr_threshold, duration gates and probe stride (rt_set_stream_settings), or null: rt_config's for every stream.
+    // K, prefilter_ok and run_cells stay derived from rt_config's durations, the envelope of every stream's.
+    StreamSettings *d_set_s = nullptr;
+    std::vector<StreamSettings> h_set_s;  // host copy (empty: none)
 
     rt_call_info info{};
     bool timing = false;
@@ -653,6 +659,7 @@ DetectArgs make_detect_args(rt_handle *h, Slot &sl, int n_seg, int n_bins, int n
     a.host_counters = sl.h_counters;
     a.thr_s = h->d_thr_s;
     a.cal_s = h->d_cal_s;
+    a.set_s = h->d_set_s;
     a.no_last = sl.call.no_last ? sl.h_no_last : nullptr;
     a.stream_overflow = sl.h_overflow;
     a.stream_incons = sl.h_incons;
@@ -843,7 +850,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         const int64_t cells = (int64_t)S * h->N;
         if (own_means) {
             hipLaunchKernelGGL(make_bin_thresholds_from_means, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->s_scan, sl.d_psum, sp.blocks_per_stream,
-                               c.n_seg, sl.d_thr_bin, sl.d_thr_nat, S, h->R3, h->LG, h->cfg.snr_threshold);
+                               c.n_seg, sl.d_thr_bin, sl.d_thr_nat, S, h->R3, h->LG, h->cfg.snr_threshold, h->d_set_s);
         } else {
         // Chunk minima are kept by this level's own scans only (round 5: the sparse scans of an AUTO handle paid for them in every
         // item's epilogue -- config 3 +1.8 % per launch -- for the one call in thousands that climbs here).  None on hand -- the handle's
@@ -866,7 +873,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         }
         const Slot &ps = h->slot[src];
         hipLaunchKernelGGL(make_bin_thresholds, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->s_scan, ps.d_chunk_min, ps.min_items, sl.d_thr_bin,
-                           sl.d_thr_nat, S, h->R3, h->LG, h->L * minsum_group(h->L, std::min(h->GPW, 16)), h->cfg.snr_threshold);
+                           sl.d_thr_nat, S, h->R3, h->LG, h->L * minsum_group(h->L, std::min(h->GPW, 16)), h->cfg.snr_threshold, h->d_set_s);
         }
     }
     if (mode == RT_MODE_RUNFILTER && !second_pass_only) {
@@ -913,7 +920,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
             // check of the per-bin thresholds against this buffer's row means, the segment counters back to zero
             const int64_t cells = (int64_t)S * h->N;
             hipLaunchKernelGGL(after_bit_scan, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s2, sl.d_abs_hot, sl.h_abs_hot, sl.d_thr_nat, sl.d_psum, S, h->N,
-                               sp.blocks_per_stream, c.n_seg, h->cfg.snr_threshold, sl.h_overflow, sl.d_counters, kFlagHotOverflow | kFlagThrStale,
+                               sp.blocks_per_stream, c.n_seg, h->cfg.snr_threshold, h->d_set_s, sl.h_overflow, sl.d_counters, kFlagHotOverflow | kFlagThrStale,
                                const_cast<int32_t *>(sp.seg_count));
         }
         sl.call.abs_counted = true;
@@ -1243,6 +1250,60 @@ int for_each_lane(rt_handle *h, F call, bool enqueues = false) {
 
 }  // namespace
 
+// rt_set_stream_settings[_f64]: the arrays against the rules of the header, before anything is copied or launched.
+template <class P>
+static int check_stream_settings(rt_handle *h, const char *what, const P *snr, const double *min_d, const double *max_d) {
+    for (int s = 0; s < h->cfg.n_streams; ++s) {
+        const std::string who = std::string(what) + ": stream " + std::to_string(s) + ": ";
+        if (snr && !(snr[s] > (P)0 && std::isfinite(snr[s]))) {
+            h->err = who + "snr_threshold must be positive and finite";
+            return RT_E_INVALID;
+        }
+        if (min_d && !std::isfinite(min_d[s])) {
+            h->err = who + "min_duration_s is not finite";
+            return RT_E_INVALID;
+        }
+        if (max_d && !std::isfinite(max_d[s])) {
+            h->err = who + "max_duration_s is not finite";
+            return RT_E_INVALID;
+        }
+        if (min_d && min_d[s] < h->cfg.min_duration_s) {
+            h->err = who + "min_duration_s " + std::to_string(min_d[s]) + " is under the handle's (rt_config.min_duration_s " + std::to_string(h->cfg.min_duration_s) + ")";
+            return RT_E_INVALID;
+        }
+        if (max_d && max_d[s] > h->cfg.max_duration_s) {
+            h->err = who + "max_duration_s " + std::to_string(max_d[s]) + " is over the handle's (rt_config.max_duration_s " + std::to_string(h->cfg.max_duration_s) + ")";
+            return RT_E_INVALID;
+        }
+    }
+    return RT_OK;
+}
+
+// ... and the table itself: `cur` becomes the new settings (empty: all three arrays null), `changed[s]` says whether stream s's differ from before
+template <class P>
+static void build_stream_settings(const rt_config &cfg, int N, P cfg_snr, const P *snr, const double *min_d, const double *max_d,
+                                  std::vector<StreamSettingsT<P>> &cur, std::vector<uint8_t> &changed) {
+    const int S = cfg.n_streams;
+    StreamSettingsT<P> dflt{};
+    dflt.snr = cfg_snr;
+    dflt.min_d = cfg.min_duration_s;
+    dflt.max_d = cfg.max_duration_s;
+    std::vector<StreamSettingsT<P>> next;
+    if (snr || min_d || max_d) next.resize((size_t)S);
+    changed.assign((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        const StreamSettingsT<P> was = cur.empty() ? dflt : cur[(size_t)s];
+        StreamSettingsT<P> is = dflt;
+        if (snr) is.snr = snr[s];
+        if (min_d) is.min_d = min_d[s];
+        if (max_d) is.max_d = max_d[s];
+        is.stride = probe_stride(N, cfg.sample_rate, is.min_d);
+        if (!(was.snr == is.snr && was.min_d == is.min_d && was.max_d == is.max_d)) changed[(size_t)s] = 1;
+        if (!next.empty()) next[(size_t)s] = is;
+    }
+    cur.swap(next);
+}
+
 extern "C" {
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
@@ -1293,6 +1354,7 @@ void rt_destroy(rt_handle *h) {
     for (auto &st : h->d_iq_stage) (void)hipFree(st);
     (void)hipFree(h->d_thr_s);
     (void)hipFree(h->d_cal_s);
+    (void)hipFree(h->d_set_s);
     for (auto &sl : h->slot) {
         (void)hipFree(sl.d_hot);
         (void)hipFree(sl.d_hot_count);
@@ -1971,6 +2033,52 @@ int rt_set_stream_params(rt_handle *h, const float *threshold, const float *cali
     return put(h->d_cal_s, calibration_db);
 }
 
+static int set_stream_settings_lane(rt_handle *h, const float *snr, const double *min_d, const double *max_d) {
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    // kernels in flight read the table: let them finish first (a configuration call, not on the hot path)
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    RT_HIP(h, hipStreamSynchronize(h->s_detect));
+    const size_t bytes = (size_t)h->cfg.n_streams * sizeof(StreamSettings);
+    if ((snr || min_d || max_d) && !h->d_set_s) RT_HIP(h, hipMalloc(&h->d_set_s, bytes));
+    // A stream whose settings change starts without look-back, as after rt_reset_stream: in the reference they are fixed when the
+    // SignalAnalyzer is built (analyze.py:113-116), new ones mean a new analyzer (_spectrogram_last = None, analyze.py:128).
+    std::vector<uint8_t> changed;
+    build_stream_settings<float>(h->cfg, h->N, h->cfg.snr_threshold, snr, min_d, max_d, h->h_set_s, changed);
+    for (int s = 0; s < h->cfg.n_streams; ++s)
+        if (changed[(size_t)s]) {
+            h->reset_pending[(size_t)s] = 1;
+            h->any_reset_pending = true;
+        }
+    if (h->h_set_s.empty()) {
+        if (h->d_set_s) (void)hipFree(h->d_set_s);
+        h->d_set_s = nullptr;
+        return RT_OK;
+    }
+    RT_HIP(h, hipMemcpy(h->d_set_s, h->h_set_s.data(), bytes, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const double *min_duration_s, const double *max_duration_s) {
+    if (!h) return RT_E_INVALID;
+    if (h->f64) return refuse_on_f64(h, "rt_set_stream_settings", "rt_set_stream_settings_f64");
+    // every refusal before the first copy, in every lane: the values (checked on the whole batch, so that a message names the
+    // stream as the caller counts it -- the lanes share rt_config's envelope), then the pending calls
+    const int rc = check_stream_settings<float>(h, "rt_set_stream_settings", snr_threshold, min_duration_s, max_duration_s);
+    if (rc != RT_OK) return rc;
+    bool pending = h->kids.empty() && oldest_pending(h);
+    for (rt_handle *k : h->kids) pending = pending || oldest_pending(k);
+    if (pending) {
+        // a pending call may still be re-run when it is fetched (AUTO mode): it must see the settings it was enqueued with
+        h->err = "rt_set_stream_settings with unfetched calls pending: fetch them first";
+        return RT_E_INVALID;
+    }
+    if (!h->kids.empty())
+        return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
+            return set_stream_settings_lane(k, snr_threshold ? snr_threshold + s0 : nullptr, min_duration_s ? min_duration_s + s0 : nullptr,
+                                            max_duration_s ? max_duration_s + s0 : nullptr);
+        });
+    return set_stream_settings_lane(h, snr_threshold, min_duration_s, max_duration_s);
+}
 
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, bool u8);
 
@@ -2960,6 +3068,7 @@ F64DetectArgs f64_detect_args(rt_handle *h, F64Slot &sl) {
     }
     a.thr_s = f->d_thr_s;
     a.cal_s = f->d_cal_s;
+    a.set_s = f->d_set_s;
     a.raw = sl.d_raw;
     a.raw_count = sl.d_raw_count;
     a.rec_cap = sl.rec_cap;
@@ -3083,6 +3192,7 @@ static void destroy_f64(rt_handle *h) {
     for (double *t : f->d_tail) (void)hipFree(t);
     (void)hipFree(f->d_thr_s);
     (void)hipFree(f->d_cal_s);
+    (void)hipFree(f->d_set_s);
     if (h->own_scan_stream && h->s_scan) (void)hipStreamDestroy(h->s_scan);
     delete f;
     h->f64 = nullptr;
@@ -3330,6 +3440,38 @@ int rt_set_stream_params_f64(rt_handle *h, const double *threshold, const double
     const int rc = put(f->d_thr_s, threshold);
     if (rc != RT_OK) return rc;
     return put(f->d_cal_s, calibration_db);
+}
+
+int rt_set_stream_settings_f64(rt_handle *h, const double *snr_threshold, const double *min_duration_s, const double *max_duration_s) {
+    if (!h) return RT_E_INVALID;
+    if (!h->f64) {
+        h->err = "rt_set_stream_settings_f64 on a float32 handle: use rt_set_stream_settings";
+        return RT_E_INVALID;
+    }
+    F64State *f = h->f64;
+    const int rc = check_stream_settings<double>(h, "rt_set_stream_settings_f64", snr_threshold, min_duration_s, max_duration_s);
+    if (rc != RT_OK) return rc;
+    if (f64_oldest(f)) return f64_err(h, RT_E_INVALID, "rt_set_stream_settings_f64 with unfetched calls pending: fetch them first");
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    const int S = h->cfg.n_streams;
+    const size_t bytes = (size_t)S * sizeof(StreamSettings64);
+    if ((snr_threshold || min_duration_s || max_duration_s) && !f->d_set_s) RT_HIP(h, hipMalloc(&f->d_set_s, bytes));
+    // a stream whose settings change starts without look-back (a new analyzer in the reference, analyze.py:113-116, 128)
+    std::vector<uint8_t> changed;
+    build_stream_settings<double>(h->cfg, f->N, f->c.snr_threshold, snr_threshold, min_duration_s, max_duration_s, f->h_set_s, changed);
+    for (int s = 0; s < S; ++s)
+        if (changed[(size_t)s]) {
+            f->reset_pending[(size_t)s] = 1;
+            f->any_reset = true;
+        }
+    if (f->h_set_s.empty()) {
+        if (f->d_set_s) (void)hipFree(f->d_set_s);
+        f->d_set_s = nullptr;
+        return RT_OK;
+    }
+    RT_HIP(h, hipMemcpy(f->d_set_s, f->h_set_s.data(), bytes, hipMemcpyHostToDevice));
+    return RT_OK;
 }
 
 int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t n_bins, const double *last_dev, int32_t n_seg_last) {

@@ -47,6 +47,25 @@ struct DetectParamsT {
 };
 using DetectParams = DetectParamsT<float>;
 using DetectParams64 = DetectParamsT<double>;
+
+// One stream's own detection settings (rt_set_stream_settings): what the reference fixes per SignalAnalyzer besides the
+// absolute threshold (analyze.py:113-116).  `stride` is probe_stride of the stream's min_d, computed where the entry is built.
+template <class P>
+struct StreamSettingsT {
+    double min_d;    // seconds
+    double max_d;    // seconds
+    P snr;           // snr_threshold (linear)
+    int32_t stride;  // max(1, int(min_d / hop))
+};
+using StreamSettings = StreamSettingsT<float>;
+using StreamSettings64 = StreamSettingsT<double>;
+template <class P>
+RT_HD void apply_stream_settings(DetectParamsT<P> &dp, const StreamSettingsT<P> &q) {
+    dp.snr = q.snr;
+    dp.min_d = q.min_d;
+    dp.max_d = q.max_d;
+    dp.stride = q.stride;
+}
 template <class T>
 struct same_t {  // (keeps an argument out of template deduction: the power type comes from the parameters)
     using type = T;

@@ -177,6 +177,7 @@ struct F64DetectArgs {
     const int32_t *no_last;     // [S] non-zero: the stream has no previous buffer in this call, or null
     const double *thr_s;        // [S] per-stream thresholds, or null
     const double *cal_s;        // [S] per-stream calibrations, or null
+    const StreamSettings64 *set_s;  // [S] per-stream snr_threshold, duration gates and probe stride (rt_set_stream_settings_f64), or null
     rt_record_f64 *raw;         // [S][rec_cap] unordered candidates
     int32_t *raw_count;         // [S] candidates each stream found (may exceed rec_cap: the fetch then grows it); zeroed by finalize_f64
     int32_t rec_cap;
@@ -194,6 +195,7 @@ __device__ __forceinline__ DetectParams64 f64_stream_params(const F64DetectArgs 
     }
     if (a.thr_s) dp.thr = a.thr_s[s];
     if (a.cal_s) dp.cal_db = a.cal_s[s];
+    if (a.set_s) apply_stream_settings(dp, a.set_s[s]);
     return dp;
 }
 

@@ -1837,7 +1837,8 @@ __device__ __forceinline__ int lane_order_bin(int R3, int lg, int j) {
 // more than ~2.5 dB from one buffer to the next) is analysed again (rt_fetch: a few streams dense, else the call on its own
 // row means).  No estimate (first call, buffers shorter than a chunk): theta = 0, the bits are the absolute threshold's alone.
 __global__ __launch_bounds__(256) void make_bin_thresholds(const uint32_t *chunk_min_prev /* [S][prev_items][N] */, int prev_items, float *thr_bin /* lane order */,
-                                                          float *thr_nat /* [S][N] */, int n_streams, int R3, int lg, int L, float snr) {
+                                                          float *thr_nat /* [S][N] */, int n_streams, int R3, int lg, int L, float snr,
+                                                          const StreamSettings *set_s /* [S], or null: `snr` for every stream */) {
     const int N = 16 * lg;  // (every scan holds sixteen bins per lane -- stft_scan64: 64 per lane, lg = 256 there as well)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over [S][LG][16]
     if (i >= (int64_t)n_streams * N) return;
@@ -1848,7 +1849,7 @@ __global__ __launch_bounds__(256) void make_bin_thresholds(const uint32_t *chunk
         uint32_t m = 0x7f7f7f7fu;  // (positive floats order like their bits)
         for (int c = 0; c < prev_items; ++c) m = min(m, chunk_min_prev[((int64_t)s * prev_items + c) * N + bin]);
         const float mn = __uint_as_float(m);
-        if (mn < 1.0e38f && mn == mn) th = snr * minsum_margin(L) * (mn / (float)L);
+        if (mn < 1.0e38f && mn == mn) th = (set_s ? set_s[s].snr : snr) * minsum_margin(L) * (mn / (float)L);
     }
     thr_bin[i] = th;
     thr_nat[(int64_t)s * N + bin] = th;
@@ -1857,7 +1858,7 @@ __global__ __launch_bounds__(256) void make_bin_thresholds(const uint32_t *chunk
 // The same table from THIS buffer's row means (a call analysed again after its thresholds failed the check below: the
 // failed scan left the partial row sums): theta = snr * row_mean * (1 - 1e-6), the bound itself -- the check cannot fail.
 __global__ __launch_bounds__(256) void make_bin_thresholds_from_means(const float *psum, int items_per_stream, int n_seg, float *thr_bin, float *thr_nat,
-                                                                     int n_streams, int R3, int lg, float snr) {
+                                                                     int n_streams, int R3, int lg, float snr, const StreamSettings *set_s) {
     const int N = 16 * lg;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over [S][LG][16]
     if (i >= (int64_t)n_streams * N) return;
@@ -1866,7 +1867,7 @@ __global__ __launch_bounds__(256) void make_bin_thresholds_from_means(const floa
     double sum = 0.0;
     for (int c = 0; c < items_per_stream; ++c) sum += (double)psum[((int64_t)s * items_per_stream + c) * N + bin];
     const float avg = (float)sum / (float)n_seg;
-    float th = snr * avg * (1.0f - 1.0e-6f);
+    float th = (set_s ? set_s[s].snr : snr) * avg * (1.0f - 1.0e-6f);
     if (!(th > 0.f) || !(th < 3.0e38f)) th = 0.f;  // (NaN / overflowing sums: the absolute threshold alone)
     thr_bin[i] = th;
     thr_nat[(int64_t)s * N + bin] = th;
@@ -1876,7 +1877,8 @@ __global__ __launch_bounds__(256) void make_bin_thresholds_from_means(const floa
 // the detection computes it, from the same partial sums).  A stream that fails is marked like one whose candidate lists
 // overflowed: rt_fetch re-runs it dense (a few streams) or takes the batch one level up.
 __global__ __launch_bounds__(256) void check_bin_thresholds(const float *thr_nat, const float *psum, int n_streams, int N, int items_per_stream, int n_seg,
-                                                           float snr, int32_t *stream_overflow, unsigned long long *counters, unsigned long long flag) {
+                                                           float snr, const StreamSettings *set_s, int32_t *stream_overflow, unsigned long long *counters,
+                                                           unsigned long long flag) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)n_streams * N) return;
     const float th = thr_nat[i];
@@ -1885,7 +1887,7 @@ __global__ __launch_bounds__(256) void check_bin_thresholds(const float *thr_nat
     double sum = 0.0;
     for (int c = 0; c < items_per_stream; ++c) sum += (double)psum[((int64_t)s * items_per_stream + c) * N + bin];
     const float avg = (float)sum / (float)n_seg;
-    if (!(th <= snr * avg * (1.0f - 1.0e-6f))) {
+    if (!(th <= (set_s ? set_s[s].snr : snr) * avg * (1.0f - 1.0e-6f))) {
         stream_overflow[s] = 1;
         atomicOr(counters + 2, flag);
     }
@@ -1896,7 +1898,7 @@ __global__ __launch_bounds__(256) void check_bin_thresholds(const float *thr_nat
 // the check above for every (stream, bin); the segment counters of the planner back to zero (words 0 .. n_streams of
 // `seg_count`); and, by workgroup 0, max_abs_hot's job.
 __global__ __launch_bounds__(256) void after_bit_scan(uint32_t *abs_hot, uint32_t *host_max, const float *thr_nat, const float *psum, int n_streams, int N,
-                                                     int items_per_stream, int n_seg, float snr, int32_t *stream_overflow, unsigned long long *counters,
+                                                     int items_per_stream, int n_seg, float snr, const StreamSettings *set_s, int32_t *stream_overflow, unsigned long long *counters,
                                                      unsigned long long flag, int32_t *seg_count) {
     __shared__ uint32_t wave_max[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1920,7 +1922,7 @@ __global__ __launch_bounds__(256) void after_bit_scan(uint32_t *abs_hot, uint32_
     double sum = 0.0;
     for (int c = 0; c < items_per_stream; ++c) sum += (double)psum[((int64_t)s * items_per_stream + c) * N + bin];
     const float avg = (float)sum / (float)n_seg;
-    if (!(th <= snr * avg * (1.0f - 1.0e-6f))) {
+    if (!(th <= (set_s ? set_s[s].snr : snr) * avg * (1.0f - 1.0e-6f))) {
         stream_overflow[s] = 1;
         atomicOr(counters + 2, flag);
     }
@@ -1965,6 +1967,7 @@ struct DetectArgs {
     // per-stream overrides (null = dp's value for every stream)
     const float *thr_s;        // [S] signal_threshold of the stream's SDR (analyze.py:115)
     const float *cal_s;        // [S] its calibration_db (orders maxima in the shadow filter)
+    const StreamSettings *set_s;  // [S] its snr_threshold, duration gates and probe stride (rt_set_stream_settings), or null: dp's for all
     const int32_t *no_last;    // [S] (host-visible) non-zero: this stream has no previous buffer in this call
                                //     (a restarted SDR's fresh analyzer, analyze.py:128)
     const int32_t *stream_list;  // detect_dense: null, or the streams of this launch (spectrogram indexed by position, see StftParams)
@@ -1985,6 +1988,7 @@ __device__ __forceinline__ DetectParams stream_params(const DetectArgs &a, int s
     DetectParams dp = a.dp;
     if (a.thr_s) dp.thr = a.thr_s[s];
     if (a.cal_s) dp.cal_db = a.cal_s[s];
+    if (a.set_s) apply_stream_settings(dp, a.set_s[s]);
     if (a.no_last && a.no_last[s]) dp.n_seg_last = -1;
     return dp;
 }

@@ -75,6 +75,9 @@ class StreamState:
 class BatchRunner:
     """Life cycle of the SDR streams of one station around the batched analysis path."""
 
+    #: analysis keywords that may be given per device (one SignalAnalyzer per SDR in the reference, analyze.py:113-116, :360)
+    PER_DEVICE_KWARGS = ("signal_threshold_dbw", "snr_threshold_db", "signal_min_duration_ms", "signal_max_duration_ms", "center_freq")
+
     def __init__(
         self,
         device: Sequence[str] = ("0",),
@@ -92,8 +95,14 @@ class BatchRunner:
         arguments of the same names (``__main__.py:44-56``); ``analysis_kwargs`` (sample_rate, fft_nperseg,
         thresholds, ...) go to every analyzer like ``**vars(dargs)`` (:113-118).  ``analyzer_factory(devices,
         calibration_db=[...], gpu=..., **analysis_kwargs)`` defaults to ``BatchSignalAnalyzer``; ``clock``
-        returns seconds since the epoch (tests pass their own)."""
+        returns seconds since the epoch (tests pass their own).  The detection keywords an analyzer takes per stream
+        (``PER_DEVICE_KWARGS``) may be sequences with one value per ``device`` entry: every GPU's analyzer then gets the
+        values of its own devices, in slot order, like ``calibration``; scalars go to every analyzer as they are."""
         self.devices = [str(d) for d in device]
+        for name in self.PER_DEVICE_KWARGS:
+            v = analysis_kwargs.get(name)
+            if v is not None and np.ndim(v) and len(v) != len(self.devices):
+                raise ValueError(f"{name} values {list(v)} do not match devices {self.devices}.")
         calibration = list(calibration)
         if len(calibration) == 0:  # __main__.py:215-217
             calibration = [0.0] * len(self.devices)
@@ -132,11 +141,15 @@ class BatchRunner:
         for i, st in enumerate(self.streams):
             self._members.setdefault(st.gpu, []).append(i)
         for gpu, members in self._members.items():
+            kwargs = dict(self.analysis_kwargs)
+            for name in self.PER_DEVICE_KWARGS:
+                if name in kwargs and np.ndim(kwargs[name]):
+                    kwargs[name] = [kwargs[name][i] for i in members]  # this GPU's devices, in slot order
             self.analyzers[gpu] = self._factory(
                 [self.streams[i].device for i in members],
                 calibration_db=[self.streams[i].calibration_db for i in members],
                 gpu=gpu,
-                **self.analysis_kwargs,
+                **kwargs,
             )
             for i in members:
                 logger.info(f"SDR {self.streams[i].device} -> GPU {gpu}, stream slot {self.streams[i].slot}")
