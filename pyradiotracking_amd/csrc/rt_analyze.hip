@@ -50,6 +50,8 @@ thread_local std::string g_create_error;
 constexpr uint32_t kFlagLaneOfLargeBatch = 0x40000000u;  // rt_config.flags of a lane's own handle (internal): the whole batch has >= 1 024 streams
 thread_local bool g_creating_lane = false;  // rt_create of a laned handle is creating one of its lanes
 
+// bytes of a sample on a float32 handle, by input format (rt_kernels.h: kFmt*)
+constexpr size_t fmt_sample_bytes(int fmt) { return fmt == kFmtU8 ? 2u : fmt == kFmtI16 ? 4u : sizeof(cf); }
 constexpr int kSlots = 2;
 constexpr int kTails = 3;
 constexpr int64_t kInitialPoolRecords = 4 << 20;  // pinned record pool per slot at rt_create unless rt_config.record_pool says otherwise
@@ -71,7 +73,7 @@ struct CallCtx {
     int mode_used = 0;
     bool fell_back = false;
     bool is_extract = false;
-    bool u8 = false;        // IQ is interleaved uint8 (RTL-SDR wire format)
+    int fmt = kFmtC64;      // the format the IQ was enqueued in: complex64, interleaved uint8 (RTL-SDR wire format) or interleaved int16 (CS16)
     bool no_last = false;   // the slot's h_no_last flags apply (some stream was reset, rt_reset_stream)
     int n_dense_streams = 0;  // streams of this call that were re-run dense on their own (AUTO, partial fall-back)
     int pool_grown = 0;       // times the record pool was enlarged for this call and the call analysed again (fetch_one)
@@ -139,7 +141,8 @@ struct Slot {
 struct F64Slot {
     bool pending = false;
     uint64_t seq = 0;
-    bool is_extract = false, u8 = false, no_last = false;
+    bool is_extract = false, no_last = false;
+    int fmt = kFmtC64;  // (as CallCtx::fmt)
     const void *iq = nullptr;  // device IQ of the call (the caller's, or d_stage)
     int64_t stream_stride = 0;
     int n_seg = 0, n_seg_last = -1, tail_read = 0, tail_write = 0;
@@ -153,7 +156,7 @@ struct F64Slot {
     rt_record_f64 *h_out = nullptr;                    // pinned, device-visible: [S * rec_cap] the call's records
     double *d_row_means = nullptr;                     // [S][N] the call's row means (RT_FLAG_ROW_MEANS only; rt_fetch_row_means_f64 copies them)
     int32_t *h_meta = nullptr;                         // pinned, device-visible: [S + 1] offsets + total, then [S] wanted
-    void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host
+    void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host / rt_process_i16_host
     size_t stage_bytes = 0;
     // RT_FLAG_RECORD_CELLS only, as in Slot:
     double *d_cells = nullptr;
@@ -344,17 +347,21 @@ int next_pow2(int v) {
 // that just fills the chip: CUs x the workgroups of this instantiation a CU holds (its __launch_bounds__), each
 // workgroup drawing further items from p.work (rt_kernels.h: "Work items") -- more workgroups than that would only
 // queue in the dispatcher and find the counter exhausted.
-template <int MODE, bool U8, bool LIN>
+// the fused scans' template arguments of an input format (rt_kernels.h, scan_fmt): <.., MODE | kModeI16, false, ..> is int16 input
+#define RT_SCAN_KERNEL(R3_, QS_) (stft_scan<R3_, MODEF, FMT == kFmtU8, LIN, QS_>)
+#define RT_WG_KERNEL(B_, W_) (stft_wg<B_, MODEF, FMT == kFmtU8, W_>)
+template <int MODE, int FMT, bool LIN>
 void launch_stft_lin(rt_handle *h, const StftParams &p, int items, hipStream_t st) {
+    constexpr int MODEF = MODE | (FMT == kFmtI16 ? kModeI16 : 0);
     if (h->big) {
         // nperseg 8192 / 16 384: one workgroup per item (a chunk of one stream), a segment per step (rt_scan_wg.h)
         if constexpr (MODE <= 2) {
             if (h->big == 256) {
-                if (h->wcos) hipLaunchKernelGGL((stft_wg<256, MODE, U8, true>), dim3(items), dim3(256), wg_lds_bytes(256), st, p);
-                else hipLaunchKernelGGL((stft_wg<256, MODE, U8, false>), dim3(items), dim3(256), wg_lds_bytes(256), st, p);
+                if (h->wcos) hipLaunchKernelGGL(RT_WG_KERNEL(256, true), dim3(items), dim3(256), wg_lds_bytes(256), st, p);
+                else hipLaunchKernelGGL(RT_WG_KERNEL(256, false), dim3(items), dim3(256), wg_lds_bytes(256), st, p);
             } else {
-                if (h->wcos) hipLaunchKernelGGL((stft_wg<512, MODE, U8, true>), dim3(items), dim3(512), wg_lds_bytes(512), st, p);
-                else hipLaunchKernelGGL((stft_wg<512, MODE, U8, false>), dim3(items), dim3(512), wg_lds_bytes(512), st, p);
+                if (h->wcos) hipLaunchKernelGGL(RT_WG_KERNEL(512, true), dim3(items), dim3(512), wg_lds_bytes(512), st, p);
+                else hipLaunchKernelGGL(RT_WG_KERNEL(512, false), dim3(items), dim3(512), wg_lds_bytes(512), st, p);
             }
         }
         return;  // (the other modes do not exist at these sizes: rt_create refuses them)
@@ -362,65 +369,69 @@ void launch_stft_lin(rt_handle *h, const StftParams &p, int items, hipStream_t s
     if (scan_wave64(h->R3)) {
         // nperseg 4096: one wave per segment, items drawn per wave; one 8-wave workgroup (all of a CU's LDS) per CU
         const int wgs = std::min((items + kW64Waves - 1) / kW64Waves, h->n_cu);
-        hipLaunchKernelGGL((stft_scan64<MODE, U8, LIN>), dim3(wgs), dim3(kW64Block), 0, st, p);
+        hipLaunchKernelGGL((stft_scan64<MODEF, FMT == kFmtU8, LIN>), dim3(wgs), dim3(kW64Block), 0, st, p);
         return;
     }
     const int blk = scan_block(h->R3);
     // workgroups a CU holds: three waves per SIMD by registers (four for the leaner uint8 / RT_WG4 instantiations), and at
     // nperseg 256 twelve one-wave workgroups by LDS whatever the registers allow
-    const int per_cu = scan_dma(h->R3, U8, h->QS) ? 2 : std::min(((h->R3 <= RT_WG4_MAX_R3 || (U8 && h->R3 == 1)) ? 4 : 3) * (kBlock / blk), blk == 64 ? 12 : 4);
+    const int per_cu = scan_dma(h->R3, FMT, h->QS) ? 2 : std::min(((h->R3 <= RT_WG4_MAX_R3 || (FMT == kFmtU8 && h->R3 == 1)) ? 4 : 3) * (kBlock / blk), blk == 64 ? 12 : 4);
     // (A/B on one box, whole path, profiles/r03_h_persistent_ab.txt: config 3 one lane 662 k -> 684 k MS/s, config 5 share +1 %)
     const bool persist = scan_persistent(h->R3, MODE);
     const int blocks = persist ? std::min(items, h->n_cu * per_cu) : items;
     switch (h->QS ? -h->QS : h->R3) {
-        case -8: hipLaunchKernelGGL((stft_scan<1, MODE, U8, LIN, 8>), dim3(blocks), dim3(blk), 0, st, p); break;  // nperseg 128
-        case -4: hipLaunchKernelGGL((stft_scan<1, MODE, U8, LIN, 4>), dim3(blocks), dim3(blk), 0, st, p); break;  // 64
-        case -2: hipLaunchKernelGGL((stft_scan<1, MODE, U8, LIN, 2>), dim3(blocks), dim3(blk), 0, st, p); break;  // 32
-        case 1: hipLaunchKernelGGL((stft_scan<1, MODE, U8, LIN>), dim3(blocks), dim3(blk), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((stft_scan<2, MODE, U8, LIN>), dim3(blocks), dim3(blk), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((stft_scan<4, MODE, U8, LIN>), dim3(blocks), dim3(blk), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((stft_scan<8, MODE, U8, LIN>), dim3(blocks), dim3(blk), 0, st, p); break;
+        case -8: hipLaunchKernelGGL(RT_SCAN_KERNEL(1, 8), dim3(blocks), dim3(blk), 0, st, p); break;  // nperseg 128
+        case -4: hipLaunchKernelGGL(RT_SCAN_KERNEL(1, 4), dim3(blocks), dim3(blk), 0, st, p); break;  // 64
+        case -2: hipLaunchKernelGGL(RT_SCAN_KERNEL(1, 2), dim3(blocks), dim3(blk), 0, st, p); break;  // 32
+        case 1: hipLaunchKernelGGL(RT_SCAN_KERNEL(1, 0), dim3(blocks), dim3(blk), 0, st, p); break;
+        case 2: hipLaunchKernelGGL(RT_SCAN_KERNEL(2, 0), dim3(blocks), dim3(blk), 0, st, p); break;
+        case 4: hipLaunchKernelGGL(RT_SCAN_KERNEL(4, 0), dim3(blocks), dim3(blk), 0, st, p); break;
+        case 8: hipLaunchKernelGGL(RT_SCAN_KERNEL(8, 0), dim3(blocks), dim3(blk), 0, st, p); break;
 #if !RT_WAVE64_4096
-        default: hipLaunchKernelGGL((stft_scan<16, MODE, U8, LIN>), dim3(blocks), dim3(blk), 0, st, p); break;
+        default: hipLaunchKernelGGL(RT_SCAN_KERNEL(16, 0), dim3(blocks), dim3(blk), 0, st, p); break;
 #else
         default: break;  // (nperseg 4096 is stft_scan64's, above)
 #endif
     }
 }
+#undef RT_SCAN_KERNEL
+#undef RT_WG_KERNEL
 
 // MODE 3 (load stream only) has no detrend: one instantiation
 // uint8 input keeps the subtract-first form: quantised samples make exact cancellations real (a saturated segment is
 // constant, x - mean is exactly zero and so is every cell of it in the reference -> std = NaN over a plateau that holds
-// one; the linearity form leaves a residue 140 dB under the offset there -- found by the round-2 soak)
-template <int MODE, bool U8 = false>
+// one; the linearity form leaves a residue 140 dB under the offset there -- found by the round-2 soak).
+// int16 input follows complex64 in this as in everything: its results are those of rt_process on the same values, bit for bit
+template <int MODE, int FMT = kFmtC64>
 void launch_stft(rt_handle *h, const StftParams &p, int blocks, hipStream_t st) {
+    constexpr bool U8 = (FMT == kFmtU8);
     if (h->lin && MODE != 3 && !U8) {
         if (p.stream_list || h->n_sub == 0 || !p.sub_first) {
             // (a launch over a list of its own -- AUTO's dense re-run of a few streams -- keeps the linearity form for all of them: its
             // dense spectrogram is indexed by position in that list, which a second launch over a sub-list cannot address)
             StftParams q = p;
             if (p.stream_list) q.sub_first = nullptr;
-            launch_stft_lin<MODE, U8, (MODE != 3 && !U8)>(h, q, blocks, st);
+            launch_stft_lin<MODE, FMT, (MODE != 3 && !U8)>(h, q, blocks, st);
         } else {
             // the streams the guard of that form has marked (StftParams::dc_flag): the first launch leaves them alone, the
             // subtract-first instantiation takes them, by list
-            launch_stft_lin<MODE, U8, (MODE != 3 && !U8)>(h, p, blocks, st);
+            launch_stft_lin<MODE, FMT, (MODE != 3 && !U8)>(h, p, blocks, st);
             StftParams q = p;
             q.sub_first = nullptr;
             q.dc_flag = nullptr;
             q.spec_by_stream = 1;
             q.stream_list = h->h_sub_list;
             q.n_streams = h->n_sub;
-            launch_stft_lin<MODE, U8, false>(h, q, h->n_sub * p.blocks_per_stream, st);
+            launch_stft_lin<MODE, FMT, false>(h, q, h->n_sub * p.blocks_per_stream, st);
         }
     } else {
-        launch_stft_lin<MODE, U8, false>(h, p, blocks, st);
+        launch_stft_lin<MODE, FMT, false>(h, p, blocks, st);
     }
 }
 
 // the general transform (rt_general.h): the dense spectrogram of an nperseg the fused scans do not cover (the caller runs
 // row_sums_dense over the map)
-void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_seg, float *spec, float *tail, bool u8) {
+void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_seg, float *spec, float *tail, int fmt) {
     if (h->bluestein) {
         BluesteinParams b{};
         b.iq = iq;
@@ -444,8 +455,9 @@ void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_s
         // where LDS leaves room for one or two workgroups per CU (16 384: 512 threads 27.4 k MS/s at nperseg 6000, 1 024 34 k).
 #define RT_BLU(U_, B_)                                                                                                            \
     do {                                                                                                                          \
-        if (u8) hipLaunchKernelGGL((stft_bluestein<true, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);                     \
-        else hipLaunchKernelGGL((stft_bluestein<false, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);                       \
+        if (fmt == kFmtU8) hipLaunchKernelGGL((stft_bluestein<kFmtU8, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);        \
+        else if (fmt == kFmtI16) hipLaunchKernelGGL((stft_bluestein<kFmtI16, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b); \
+        else hipLaunchKernelGGL((stft_bluestein<kFmtC64, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);                     \
     } while (0)
         if (h->gen_m >= 16384) RT_BLU(4, 1024);
         else if (h->gen_m >= 8192) RT_BLU(4, 512);  // (8 groups x 256 threads: 31.8 k MS/s at nperseg 3000, this 41.6 k)
@@ -470,8 +482,9 @@ void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_s
     g.tail = tail;
     const int blocks = h->cfg.n_streams * ((n_seg + g.segs_per_block - 1) / g.segs_per_block);
     const size_t lds = (size_t)g.segs_per_block * h->N * sizeof(cf);
-    if (u8) hipLaunchKernelGGL((stft_general<true>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
-    else hipLaunchKernelGGL((stft_general<false>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
+    if (fmt == kFmtU8) hipLaunchKernelGGL((stft_general<kFmtU8>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
+    else if (fmt == kFmtI16) hipLaunchKernelGGL((stft_general<kFmtI16>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
+    else hipLaunchKernelGGL((stft_general<kFmtC64>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
 }
 
 // cells a run must have to pass the duration gate unless it runs through t = 0 (see rt_create)
@@ -781,9 +794,11 @@ int level_down(const rt_handle *h, int mode) { return level_down(AutoLevels{h->p
 
 // (`st`: the handle's scan stream, or -- the selective second scans of the pre-filter levels -- the stream of what follows a call's first scan)
 template <int MODE>
-void launch_scan(rt_handle *h, const StftParams &sp, int blocks, bool u8, hipStream_t st = nullptr) {
+void launch_scan(rt_handle *h, const StftParams &sp, int blocks, int fmt, hipStream_t st = nullptr) {
     if (!st) st = h->s_scan;
-    if (u8) launch_stft<MODE, true>(h, sp, blocks, st); else launch_stft<MODE>(h, sp, blocks, st);
+    if (fmt == kFmtU8) launch_stft<MODE, kFmtU8>(h, sp, blocks, st);
+    else if (fmt == kFmtI16) launch_stft<MODE, kFmtI16>(h, sp, blocks, st);
+    else launch_stft<MODE>(h, sp, blocks, st);
 }
 
 // enqueue scan + detect + readback for the call described by sl.call, analysed the way `mode` says.
@@ -801,7 +816,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         if (rc != RT_OK) return rc;
         RT_HIP(h, hipEventRecord(sl.ev_begin, h->s_scan));
         if (launched) *launched = true;
-        launch_general(h, c.iq, c.stream_stride, c.n_seg, h->d_spec, h->d_tail[c.tail_write], c.u8);
+        launch_general(h, c.iq, c.stream_stride, c.n_seg, h->d_spec, h->d_tail[c.tail_write], c.fmt);
         {
             const int64_t cells = (int64_t)h->cfg.n_streams * h->N;
             hipLaunchKernelGGL(row_sums_dense, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->s_scan, h->d_spec, sl.d_psum, h->cfg.n_streams, c.n_seg, h->N);
@@ -842,7 +857,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
     }
     if (!second_pass_only) RT_HIP(h, hipEventRecord(sl.ev_begin, h->s_scan));
     if (launched) *launched = true;
-    sl.call.ran_lin = h->lin && !c.u8;
+    sl.call.ran_lin = h->lin && c.fmt != kFmtU8;
     sl.call.sub_epoch = h->sub_epoch;
     const int slot_index = (int)(&sl - h->slot);
     if (mode == RT_MODE_RUNFILTER) {
@@ -864,7 +879,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         int src = h->minsum_slot;
         const bool on_hand = src >= 0 && h->slot[src].min_items > 0 && (h->slot[src].min_seq + 1 == c.seq || h->slot[src].min_seq == c.seq);
         if (!on_hand) {
-            launch_scan<6>(h, sp, blocks, c.u8);
+            launch_scan<6>(h, sp, blocks, c.fmt);
             sl.min_items = sp.blocks_per_stream;
             sl.min_seq = sl.call.seq;
             src = slot_index;
@@ -906,12 +921,12 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         return RT_OK;
     };
     if (dense) {
-        launch_scan<1>(h, sp, blocks, c.u8);
+        launch_scan<1>(h, sp, blocks, c.fmt);
     } else if (mode == RT_MODE_RUNFILTER) {
         // threshold bits of every cell (+ row sums, tail) -> cells of runs long enough -> only their segments again
         sp.thr_bin = sl.d_thr_bin;
         sp.abs_hot = sl.d_abs_hot;
-        launch_scan<6>(h, sp, blocks, c.u8);
+        launch_scan<6>(h, sp, blocks, c.fmt);
         sp.thr_bin = nullptr;
         sp.abs_hot = nullptr;
         { const int rc = behind_first_scan(); if (rc != RT_OK) return rc; }
@@ -935,11 +950,11 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
             hipLaunchKernelGGL(kern, dim3(S, waves), dim3(64), plan_lds, s2, sp.cell_hot, sl.d_cell_need,
                                sl.d_seg_list, const_cast<int32_t *>(sp.seg_count), c.n_seg, h->LG, r, tile);
         }
-        launch_scan<7>(h, sp, blocks, c.u8, s2);
+        launch_scan<7>(h, sp, blocks, c.fmt, s2);
     } else if (mode == RT_MODE_PREFILTER) {
         if (!second_pass_only) {
             sp.abs_hot = sl.d_abs_hot;
-            launch_scan<4>(h, sp, blocks, c.u8);
+            launch_scan<4>(h, sp, blocks, c.fmt);
             sp.abs_hot = nullptr;
         }
         { const int rc = behind_first_scan(); if (rc != RT_OK) return rc; }
@@ -949,7 +964,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         }
         hipLaunchKernelGGL(plan_pass_b, dim3(S), dim3(256), sizeof(uint32_t) * ((sp.chunks + 31) / 32), s2, sp.full, sp.first,
                            sp.item_chunks, sp.item_count, h->LG, sp.segs_per_chunk, c.n_seg, sp.chunks, sp.blocks_per_stream, h->GPW);
-        launch_scan<5>(h, sp, blocks, c.u8, s2);
+        launch_scan<5>(h, sp, blocks, c.fmt, s2);
     } else {
 #ifdef RT_STAMPS  // diagnostic build: per-stage cycle sums of every wave of the sparse scan, averaged and printed (stderr)
         static uint32_t *d_dbg = nullptr;
@@ -963,7 +978,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
         RT_HIP(h, hipMemsetAsync(d_dbg, 0, words * sizeof(uint32_t), h->s_scan));
         sp.dbg = d_dbg;
 #endif
-        launch_scan<0>(h, sp, blocks, c.u8);
+        launch_scan<0>(h, sp, blocks, c.fmt);
 #ifdef RT_STAMPS
         {
             std::vector<uint32_t> hd(words);
@@ -1067,7 +1082,7 @@ int enqueue_partial_dense(rt_handle *h, Slot &sl, int n_list, unsigned long long
     sp.spec = h->d_spec_part;
     *sl.h_total = records_so_far;
     RT_HIP(h, hipMemcpyAsync(sl.d_counters, sl.h_total, sizeof(unsigned long long), hipMemcpyHostToDevice, h->s_scan));
-    launch_scan<1>(h, sp, n_list * sp.blocks_per_stream, c.u8);
+    launch_scan<1>(h, sp, n_list * sp.blocks_per_stream, c.fmt);
     RT_HIP(h, hipGetLastError());
     DetectArgs a = make_detect_args(h, sl, c.n_seg, h->N, c.n_seg_last);
     a.prev = h->d_tail[c.tail_read];
@@ -1650,12 +1665,15 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         RT_CREATE_HIP(hipMalloc(&h->d_twg, sizeof(cf) * twg.size()));
         RT_CREATE_HIP(hipMemcpy(h->d_twg, twg.data(), sizeof(cf) * twg.size(), hipMemcpyHostToDevice));
         {
-            const void *big_lds[] = {reinterpret_cast<const void *>(stft_general<false>), reinterpret_cast<const void *>(stft_general<true>),
-                                     reinterpret_cast<const void *>(stft_bluestein<false, 1, 256>), reinterpret_cast<const void *>(stft_bluestein<true, 1, 256>),
-                                     reinterpret_cast<const void *>(stft_bluestein<false, 2, 256>), reinterpret_cast<const void *>(stft_bluestein<true, 2, 256>),
-                                     reinterpret_cast<const void *>(stft_bluestein<false, 2, 512>), reinterpret_cast<const void *>(stft_bluestein<true, 2, 512>),
-                                     reinterpret_cast<const void *>(stft_bluestein<false, 4, 512>), reinterpret_cast<const void *>(stft_bluestein<true, 4, 512>),
-                                     reinterpret_cast<const void *>(stft_bluestein<false, 4, 1024>), reinterpret_cast<const void *>(stft_bluestein<true, 4, 1024>)};
+            std::vector<const void *> big_lds;
+#define RT_BIG_LDS(F_)                                                                                                             \
+    big_lds.insert(big_lds.end(), {reinterpret_cast<const void *>(stft_general<F_>), reinterpret_cast<const void *>(stft_bluestein<F_, 1, 256>), \
+                                   reinterpret_cast<const void *>(stft_bluestein<F_, 2, 256>), reinterpret_cast<const void *>(stft_bluestein<F_, 2, 512>), \
+                                   reinterpret_cast<const void *>(stft_bluestein<F_, 4, 512>), reinterpret_cast<const void *>(stft_bluestein<F_, 4, 1024>)})
+            RT_BIG_LDS(kFmtC64);
+            RT_BIG_LDS(kFmtU8);
+            RT_BIG_LDS(kFmtI16);
+#undef RT_BIG_LDS
             for (const void *f : big_lds) RT_CREATE_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, padded_len(kGeneralMaxN, 14) * (int)sizeof(cf)));
         }
         if (h->bluestein) {
@@ -1928,7 +1946,8 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
 
     if (big) {
 #define RT_WG_SET(B_, M_, U_, W_) RT_CREATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(stft_wg<B_, M_, U_, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_bytes(B_)))
-#define RT_WG_SET4(B_, M_) RT_WG_SET(B_, M_, false, false); RT_WG_SET(B_, M_, false, true); RT_WG_SET(B_, M_, true, false); RT_WG_SET(B_, M_, true, true)
+#define RT_WG_SET4(B_, M_) RT_WG_SET(B_, M_, false, false); RT_WG_SET(B_, M_, false, true); RT_WG_SET(B_, M_, true, false); RT_WG_SET(B_, M_, true, true); \
+    RT_WG_SET(B_, M_ | kModeI16, false, false); RT_WG_SET(B_, M_ | kModeI16, false, true)
         RT_WG_SET4(256, 0); RT_WG_SET4(256, 1); RT_WG_SET4(256, 2);
         RT_WG_SET4(512, 0); RT_WG_SET4(512, 1); RT_WG_SET4(512, 2);
 #undef RT_WG_SET4
@@ -2080,27 +2099,31 @@ int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const doubl
     return set_stream_settings_lane(h, snr_threshold, min_duration_s, max_duration_s);
 }
 
-static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, bool u8);
+static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, int fmt);
 
 int rt_process(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride) {
-    return process_impl(h, iq_dev, n_samples, stream_stride, false);
+    return process_impl(h, iq_dev, n_samples, stream_stride, kFmtC64);
 }
 
 int rt_process_u8(rt_handle *h, const void *iq_u8_dev, int64_t n_samples, int64_t stream_stride) {
-    return process_impl(h, iq_u8_dev, n_samples, stream_stride, true);
+    return process_impl(h, iq_u8_dev, n_samples, stream_stride, kFmtU8);
 }
 
-static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, bool u8, bool host);
+int rt_process_i16(rt_handle *h, const void *iq_i16_dev, int64_t n_samples, int64_t stream_stride) {
+    return process_impl(h, iq_i16_dev, n_samples, stream_stride, kFmtI16);
+}
 
-static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, bool u8) {
+static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, int fmt, bool host);
+
+static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, int fmt) {
     if (!h) return RT_E_INVALID;
     forget_row_means(h);
-    if (h->f64) return process_f64(h, iq_dev, n_samples, stream_stride, u8, false);
+    if (h->f64) return process_f64(h, iq_dev, n_samples, stream_stride, fmt, false);
     if (!h->kids.empty()) {
-        const int64_t bytes = u8 ? 2 : (int64_t)sizeof(cf);
+        const int64_t bytes = (int64_t)fmt_sample_bytes(fmt);
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
             const char *base = iq_dev ? static_cast<const char *>(iq_dev) + s0 * stream_stride * bytes : nullptr;
-            return process_impl(k, base, n_samples, stream_stride, u8);
+            return process_impl(k, base, n_samples, stream_stride, fmt);
         }, true);
     }
     if (!iq_dev && n_samples > 0) {
@@ -2111,10 +2134,11 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
         h->err = "n_samples/stream_stride out of range for this handle";
         return RT_E_INVALID;
     }
-    // the scan kernel loads whole samples (8-byte complex64 / 2-byte I,Q pairs): a misaligned pointer would
-    // fault on the device, so it is refused here
-    if (reinterpret_cast<uintptr_t>(iq_dev) % (u8 ? 2u : 8u) != 0) {
-        h->err = u8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)" : "IQ pointer must be 8-byte aligned (complex64)";
+    // the scan kernel loads whole samples (8-byte complex64 / 2-byte uint8 / 4-byte int16 I,Q pairs): a misaligned pointer
+    // would fault on the device, so it is refused here
+    if (reinterpret_cast<uintptr_t>(iq_dev) % fmt_sample_bytes(fmt) != 0) {
+        h->err = fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
+                 : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)" : "IQ pointer must be 8-byte aligned (complex64)";
         return RT_E_INVALID;
     }
     RT_HIP(h, hipSetDevice(h->cfg.device));
@@ -2134,7 +2158,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     c.prev_dense_sticky = h->dense_sticky;
     c.prev_minsum_slot = h->minsum_slot;
     c.iq = iq_dev;
-    c.u8 = u8;
+    c.fmt = fmt;
     c.n_samples = n_samples;
     c.stream_stride = stream_stride;
     c.n_seg = T;
@@ -2213,15 +2237,15 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     return RT_OK;
 }
 
-static int process_host_impl(rt_handle *h, const void *iq_host, int64_t n_samples, int64_t stream_stride, bool u8) {
+static int process_host_impl(rt_handle *h, const void *iq_host, int64_t n_samples, int64_t stream_stride, int fmt) {
     if (!h) return RT_E_INVALID;
     forget_row_means(h);
-    if (h->f64) return process_f64(h, iq_host, n_samples, stream_stride, u8, true);
-    const size_t sample_bytes = u8 ? 2 : sizeof(cf);
+    if (h->f64) return process_f64(h, iq_host, n_samples, stream_stride, fmt, true);
+    const size_t sample_bytes = fmt_sample_bytes(fmt);
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
             const char *base = iq_host ? static_cast<const char *>(iq_host) + s0 * stream_stride * (int64_t)sample_bytes : nullptr;
-            return process_host_impl(k, base, n_samples, stream_stride, u8);
+            return process_host_impl(k, base, n_samples, stream_stride, fmt);
         }, true);
     if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples || (!iq_host && n_samples > 0)) {
         h->err = "n_samples/stream_stride out of range for this handle, or null IQ pointer";
@@ -2248,15 +2272,19 @@ static int process_host_impl(rt_handle *h, const void *iq_host, int64_t n_sample
     }
     // blocking copy: the caller may reuse or free its (pageable) buffer as soon as this returns
     if (bytes) RT_HIP(h, hipMemcpy(h->d_iq_stage[which], iq_host, bytes, hipMemcpyHostToDevice));
-    return process_impl(h, h->d_iq_stage[which], n_samples, stream_stride, u8);
+    return process_impl(h, h->d_iq_stage[which], n_samples, stream_stride, fmt);
 }
 
 int rt_process_host(rt_handle *h, const void *iq_host, int64_t n_samples, int64_t stream_stride) {
-    return process_host_impl(h, iq_host, n_samples, stream_stride, false);
+    return process_host_impl(h, iq_host, n_samples, stream_stride, kFmtC64);
 }
 
 int rt_process_u8_host(rt_handle *h, const void *iq_u8_host, int64_t n_samples, int64_t stream_stride) {
-    return process_host_impl(h, iq_u8_host, n_samples, stream_stride, true);
+    return process_host_impl(h, iq_u8_host, n_samples, stream_stride, kFmtU8);
+}
+
+int rt_process_i16_host(rt_handle *h, const void *iq_i16_host, int64_t n_samples, int64_t stream_stride) {
+    return process_host_impl(h, iq_i16_host, n_samples, stream_stride, kFmtI16);
 }
 
 int rt_extract(rt_handle *h, const float *spec_dev, int32_t n_seg, int32_t n_bins, const float *last_dev,
@@ -3103,12 +3131,15 @@ int f64_enqueue(rt_handle *h, F64Slot &sl) {
         p.tail = f->d_tail[sl.tail_write];
         const int64_t grid = (int64_t)S * ((sl.n_seg + f->SPB - 1) / f->SPB);
         const size_t lds = (size_t)f->SPB * f->M * sizeof(cd);
-        if (sl.u8) {
-            if (f->blu) stft_f64<true, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
-            else stft_f64<true, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+        if (sl.fmt == kFmtU8) {
+            if (f->blu) stft_f64<kFmtU8, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            else stft_f64<kFmtU8, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+        } else if (sl.fmt == kFmtI16) {
+            if (f->blu) stft_f64<kFmtI16, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            else stft_f64<kFmtI16, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
         } else {
-            if (f->blu) stft_f64<false, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
-            else stft_f64<false, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            if (f->blu) stft_f64<kFmtC64, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            else stft_f64<kFmtC64, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
         }
         RT_HIP(h, hipGetLastError());
     }
@@ -3199,13 +3230,16 @@ static void destroy_f64(rt_handle *h) {
     delete h;
 }
 
-static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, bool u8, bool host) {
+static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, int fmt, bool host) {
     F64State *f = h->f64;
     if (!iq && n_samples > 0) return f64_err(h, RT_E_INVALID, "null IQ pointer");
     if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples)
         return f64_err(h, RT_E_INVALID, "n_samples/stream_stride out of range for this handle");
-    if (!host && reinterpret_cast<uintptr_t>(iq) % (u8 ? 2u : 16u) != 0)
-        return f64_err(h, RT_E_INVALID, u8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)" : "IQ pointer must be 16-byte aligned (complex128 on a float64 handle)");
+    const size_t sample_bytes = fmt == kFmtC64 ? 16u : fmt_sample_bytes(fmt);  // (complex128 on a float64 handle)
+    if (!host && reinterpret_cast<uintptr_t>(iq) % sample_bytes != 0)
+        return f64_err(h, RT_E_INVALID, fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
+                                        : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)"
+                                                         : "IQ pointer must be 16-byte aligned (complex128 on a float64 handle)");
     const int T = (int)(n_samples / f->N);
     if (T == 1) return f64_err(h, RT_E_ONE_SEGMENT, "exactly one segment: the reference raises IndexError (times[1])");
     RT_HIP(h, hipSetDevice(h->cfg.device));
@@ -3213,7 +3247,7 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
     F64Slot &sl = f64_claim(f);
     sl.pending = false;
     sl.is_extract = false;
-    sl.u8 = u8;
+    sl.fmt = fmt;
     sl.stream_stride = stream_stride;
     sl.n_seg = T;
     sl.n_seg_last = f->n_seg_last;
@@ -3221,7 +3255,7 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
     sl.tail_write = (f->tail_cur + 1) % kTails;
     sl.iq = iq;
     if (host && n_samples > 0) {
-        const size_t bytes = (size_t)S * (size_t)stream_stride * (u8 ? 2u : 16u);
+        const size_t bytes = (size_t)S * (size_t)stream_stride * sample_bytes;
         if (sl.stage_bytes < bytes) {
             RT_HIP(h, hipStreamSynchronize(h->s_scan));  // (the slot's last call may still read its staging buffer)
             (void)hipFree(sl.d_stage);
@@ -3370,8 +3404,8 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     }
     const int lds = f->SPB * f->M * (int)sizeof(cd);
     if (lds > 64 * 1024) {
-        const void *fns[] = {(const void *)stft_f64<false, false>, (const void *)stft_f64<false, true>,
-                             (const void *)stft_f64<true, false>, (const void *)stft_f64<true, true>};
+        const void *fns[] = {(const void *)stft_f64<kFmtC64, false>, (const void *)stft_f64<kFmtC64, true>, (const void *)stft_f64<kFmtU8, false>,
+                             (const void *)stft_f64<kFmtU8, true>, (const void *)stft_f64<kFmtI16, false>, (const void *)stft_f64<kFmtI16, true>};
         for (const void *fn : fns) RT_F64_CREATE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     // the float64 map (S T N 8 bytes) and the look-back tails
@@ -3656,8 +3690,8 @@ int rt_spectrogram_f64(rt_handle *h, const void *iq_dev, int64_t n_samples, int6
     p.tail = nullptr;
     const int64_t grid = (int64_t)h->cfg.n_streams * ((T + f->SPB - 1) / f->SPB);
     const size_t lds = (size_t)f->SPB * f->M * sizeof(cd);
-    if (f->blu) stft_f64<false, true><<<(unsigned)grid, kF64Block, lds, h->s_scan>>>(p);
-    else stft_f64<false, false><<<(unsigned)grid, kF64Block, lds, h->s_scan>>>(p);
+    if (f->blu) stft_f64<kFmtC64, true><<<(unsigned)grid, kF64Block, lds, h->s_scan>>>(p);
+    else stft_f64<kFmtC64, false><<<(unsigned)grid, kF64Block, lds, h->s_scan>>>(p);
     RT_HIP(h, hipGetLastError());
     RT_HIP(h, hipStreamSynchronize(h->s_scan));
     return RT_OK;

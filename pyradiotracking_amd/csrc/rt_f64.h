@@ -47,11 +47,15 @@ struct F64StftParams {
 
 // One segment's sample n in float64: complex128 as it is; a wire-format byte pair as pyrtlsdr converts it (packed_bytes_to_iq:
 // `iq /= 127.5; iq -= 1 + 1j` -- a division by (127.5 + 0j) is the real division, then the subtraction; no fma, -ffp-contract=off)
-template <bool U8>
+// An int16 pair is component / 32768: the conversion and the multiplication by 2^-15 are exact.
+template <int FMT>
 __device__ __forceinline__ cd load_f64(const void *base, int64_t i) {
-    if constexpr (U8) {
+    if constexpr (FMT == kFmtU8) {
         const uint16_t b = reinterpret_cast<const uint16_t *>(base)[i];  // low byte I, high byte Q
         return cd{(double)(b & 0xFFu) / 127.5 - 1.0, (double)(b >> 8) / 127.5 - 1.0};
+    } else if constexpr (FMT == kFmtI16) {
+        const uint32_t b = reinterpret_cast<const uint32_t *>(base)[i];  // low half I, high half Q
+        return cd{(double)(int16_t)(b & 0xFFFFu) * (1.0 / 32768.0), (double)((int32_t)b >> 16) * (1.0 / 32768.0)};
     } else {
         const double2 v = reinterpret_cast<const double2 *>(base)[i];
         return cd{v.x, v.y};
@@ -92,7 +96,7 @@ __device__ __forceinline__ void f64_fft_dif(cd *xs, int M, int LOG, const cd *tw
 // SPB segments per workgroup of kF64Block threads (TPS = kF64Block / SPB threads each); M * SPB complex doubles of dynamic LDS.
 // BLU = false: nperseg = M is a power of two.  BLU = true: Bluestein -- A = DIF_M((x - mean) * cwin, zero-padded) (bit-reversed),
 // conj(A * bfilt) in place, DIT_M of that = FFT(conj(C)), whose first N values have the spectrum's magnitudes (rt_general.h).
-template <bool U8, bool BLU>
+template <int FMT, bool BLU>
 __global__ __launch_bounds__(kF64Block) void stft_f64(const F64StftParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char f64_smem[];
     cd *const x = reinterpret_cast<cd *>(f64_smem);  // [SPB][M]
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(kF64Block) void stft_f64(const F64StftParams p) {
     double sx = 0.0, sy = 0.0;
     if (live) {
         for (int n = lt; n < N; n += TPS) {
-            const cd v = load_f64<U8>(p.iq, first + n);
+            const cd v = load_f64<FMT>(p.iq, first + n);
             sx += v.x;
             sy += v.y;
             xs[BLU ? n : (int)(__brev((unsigned)n) >> (32 - LOG))] = v;

@@ -204,9 +204,9 @@ __device__ __forceinline__ void lds_fft_stages_dif(cf *xs, int N, int LOG, const
 }
 
 // nperseg 8 and 16: up to 64 segments per workgroup.
-template <bool U8>
+template <int FMT>
 __global__ __launch_bounds__(kGeneralBlock) void stft_general(const GeneralParams p) {
-    using raw_t = typename std::conditional<U8, iq_u8, cf>::type;
+    using raw_t = typename raw_of<FMT>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char gen_smem[];
     cf *const x = reinterpret_cast<cf *>(gen_smem);                       // [SPB][N]
     __shared__ double red[2 * kGeneralBlock];                              // partial sums of the segment means
@@ -292,9 +292,9 @@ struct BluesteinParams {
     float *spec, *tail;
 };
 
-template <bool U8, int U = 1, int BLK = kGeneralBlock>
+template <int FMT, int U = 1, int BLK = kGeneralBlock>
 __global__ __launch_bounds__(BLK) void stft_bluestein(const BluesteinParams p) {
-    using raw_t = typename std::conditional<U8, iq_u8, cf>::type;
+    using raw_t = typename raw_of<FMT>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char blu_smem[];
     cf *const xs = reinterpret_cast<cf *>(blu_smem);  // [M]
     constexpr int NW = BLK / 64;

@@ -43,7 +43,7 @@ constexpr int kBlock = 256;          // threads per workgroup (4 waves)
 constexpr int kRowF2 = 18;           // LDS exchange row stride in float2 (16 data + 2 pad = 144 B)
 
 struct StftParams {
-    const void *iq;          // [S][stream_stride] complex64, or interleaved uint8 I/Q (U8 instantiations)
+    const void *iq;          // [S][stream_stride] complex64, or interleaved uint8 / int16 I/Q (the FMT of the instantiation)
     int64_t stream_stride;   // samples
     int32_t n_streams;
     int32_t n_seg;           // T
@@ -385,10 +385,18 @@ constexpr int kStamps = 16;  // 0 .. 10 stage sums, 11 steps, 12 / 13 shader-clo
         continue;                                                       \
     }
 
-// raw sample as it sits in HBM: complex64, or the RTL-SDR wire format (interleaved uint8 I, Q)
+// raw sample as it sits in HBM: complex64, the RTL-SDR wire format (interleaved uint8 I, Q), or CS16 (interleaved little-endian int16 I, Q)
 struct iq_u8 {
     uint16_t iq;  // low byte I, high byte Q
 };
+struct iq_i16 {
+    uint32_t iq;  // low half I, high half Q
+};
+// the input format of a kernel instantiation (the FMT template parameter) and its raw type
+constexpr int kFmtC64 = 0, kFmtU8 = 1, kFmtI16 = 2;
+template <int FMT> struct raw_of { using type = cf; };
+template <> struct raw_of<kFmtU8> { using type = iq_u8; };
+template <> struct raw_of<kFmtI16> { using type = iq_i16; };
 
 // IQ is read exactly once: the loads carry the non-temporal hint (load-only instantiation +4..9 %)
 __device__ __forceinline__ cf load_iq(const cf *p) {
@@ -397,6 +405,7 @@ __device__ __forceinline__ cf load_iq(const cf *p) {
     return cf{v.x, v.y};
 }
 __device__ __forceinline__ iq_u8 load_iq(const iq_u8 *p) { return iq_u8{__builtin_nontemporal_load(&p->iq)}; }
+__device__ __forceinline__ iq_i16 load_iq(const iq_i16 *p) { return iq_i16{__builtin_nontemporal_load(&p->iq)}; }
 
 // Buffer loads (wave-uniform descriptor in SGPRs + one 32-bit lane offset + a scalar offset): the 16 loads of a
 // segment share ONE address VGPR.  With flat addresses hipcc keeps a 64-bit pointer per 4 KiB of immediate range
@@ -409,6 +418,7 @@ __device__ float raw_buffer_load_f1(rsrc_t rsrc, int voffset, int soffset, int a
 typedef float buf_f4 __attribute__((ext_vector_type(4)));
 __device__ buf_f4 raw_buffer_load_f4(rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
 __device__ short raw_buffer_load_i16(rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.i16");
+__device__ int raw_buffer_load_i32(rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.i32");
 
 // `base` must be wave-uniform (the descriptor lives in SGPRs)
 __device__ __forceinline__ rsrc_t make_rsrc(const void *base, uint32_t bytes) {
@@ -428,6 +438,9 @@ __device__ __forceinline__ cf buf_load_iq(rsrc_t r, int voff, int soff, cf) {
 __device__ __forceinline__ iq_u8 buf_load_iq(rsrc_t r, int voff, int soff, iq_u8) {
     return iq_u8{(uint16_t)raw_buffer_load_i16(r, voff, soff, kAuxNT)};
 }
+__device__ __forceinline__ iq_i16 buf_load_iq(rsrc_t r, int voff, int soff, iq_i16) {
+    return iq_i16{(uint32_t)raw_buffer_load_i32(r, voff, soff, kAuxNT)};
+}
 
 // pyrtlsdr's packed_bytes_to_iq is (byte / 127.5) - 1 per component (in float64); here one
 // float32 fma per component, at most one float32 ulp away, then float32 like complex64 input
@@ -436,9 +449,15 @@ __device__ __forceinline__ cf to_cf(iq_u8 x) {
     constexpr float c = 1.0f / 127.5f;
     return cf{__builtin_fmaf((float)(x.iq & 0xFFu), c, -1.0f), __builtin_fmaf((float)(x.iq >> 8), c, -1.0f)};
 }
+// CS16: component / 32768.  int16 -> float32 and the multiplication by 2^-15 are both exact, so the values -- and everything
+// computed from them -- are those of the complex64 path on the same samples, bit for bit
+__device__ __forceinline__ cf to_cf(iq_i16 x) {
+    constexpr float c = 1.0f / 32768.0f;
+    return cf{(float)(int16_t)(x.iq & 0xFFFFu) * c, (float)((int32_t)x.iq >> 16) * c};
+}
 
 // stft_scan<.., QS>: the PER = 16 / QS consecutive samples a lane holds of one sixteenth of its segment, as 16-byte loads (complex64:
-// two samples each; uint8 I/Q: 4 / 8 / 16 bytes in one load) into the registers e QS + m, e < PER.  The stream bases the host passes
+// two samples each; uint8 I/Q: 4 / 8 / 16 bytes in one load; int16 I/Q: 8 bytes, or 16-byte loads of four samples) into the registers e QS + m, e < PER.  The stream bases the host passes
 // are aligned to these loads (rt_analyze.hip: process_impl); segments are 16 QS samples long, so every run is.
 template <int PER, int QS>
 __device__ __forceinline__ void load_iq_run(const cf *p, cf (&dst)[16], int m) {
@@ -468,6 +487,26 @@ __device__ __forceinline__ void load_iq_run(const iq_u8 *p, iq_u8 (&dst)[16], in
     for (int h = 0; h < PER / 2; ++h) {
         dst[(2 * h) * QS + m] = iq_u8{(uint16_t)(w[h] & 0xFFFFu)};
         dst[(2 * h + 1) * QS + m] = iq_u8{(uint16_t)(w[h] >> 16)};
+    }
+}
+
+template <int PER, int QS>
+__device__ __forceinline__ void load_iq_run(const iq_i16 *p, iq_i16 (&dst)[16], int m) {
+    if constexpr (PER == 2) {
+        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+        const u2 v = __builtin_nontemporal_load(reinterpret_cast<const u2 *>(p));
+        dst[m] = iq_i16{v.x};
+        dst[QS + m] = iq_i16{v.y};
+    } else {
+        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int h = 0; h < PER / 4; ++h) {
+            const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(p + 4 * h));
+            dst[(4 * h) * QS + m] = iq_i16{v.x};
+            dst[(4 * h + 1) * QS + m] = iq_i16{v.y};
+            dst[(4 * h + 2) * QS + m] = iq_i16{v.z};
+            dst[(4 * h + 3) * QS + m] = iq_i16{v.w};
+        }
     }
 }
 
@@ -501,7 +540,12 @@ __host__ __device__ constexpr int scan_block(int R3) { return R3 <= RT_ONE_WAVE_
 #ifndef RT_EXP_DMA1024
 #define RT_EXP_DMA1024 0
 #endif
-__host__ __device__ constexpr bool scan_dma(int r3, bool u8, int qs) { return RT_EXP_DMA1024 && r3 == 4 && !u8 && qs == 0; }
+// The fused scans (stft_scan, stft_scan64, stft_wg) keep the template signatures <.., MODE, bool U8, ..> -- and so the symbol names -- they
+// had before there was a third input format: the benchmark's PMC bookkeeping and the tools name instantiations by symbol.  int16 input
+// is MODE | kModeI16 with U8 = false.
+constexpr int kModeI16 = 16;
+__host__ __device__ constexpr int scan_fmt(int modef, bool u8) { return (modef & kModeI16) ? kFmtI16 : u8 ? kFmtU8 : kFmtC64; }
+__host__ __device__ constexpr bool scan_dma(int r3, int fmt, int qs) { return RT_EXP_DMA1024 && r3 == 4 && fmt == kFmtC64 && qs == 0; }  // (the landing zone holds complex64)
 __device__ void raw_buffer_load_lds_fwd(rsrc_t rsrc, __attribute__((address_space(3))) void *lds, int size, int voffset, int soffset, int offset, int aux)
     __asm("llvm.amdgcn.raw.buffer.load.lds");
 // QS (round 6): nperseg 128 / 64 / 32 = 16 QS, lane groups of QS = 8 / 4 / 2 lanes (R3 = 1 in every other respect: one wave-private
@@ -514,7 +558,6 @@ __device__ void raw_buffer_load_lds_fwd(rsrc_t rsrc, __attribute__((address_spac
 // so everything behind the transform -- power, row sums, look-back tail, threshold bits, candidate emission, every MODE -- is the
 // nperseg-256 code with LG = QS.  (Round 5 served these sizes by a kernel of its own on the dense path, stft_small: 282 k MS/s at
 // nperseg 128 against the 650 k+ of the sparse path at 256.)
-template <int R3, int MODE, bool U8 = false, bool LIN = false, int QS = 0>
 // Experiment switch (default off): -DRT_WG4_MAX_R3=1 runs nperseg 256 at four workgroups per CU (its kernels need
 // <= 124 VGPRs and, with 32 staged cells per wave, exactly 40 960 B of LDS).  Measured in round 2: one lane 0.792 ->
 // 0.826 ms, two lanes 0.766 -> 0.788 ms per step (uint8 input +3 %): more waves do not help the complex64 scan.
@@ -533,9 +576,15 @@ template <int R3, int MODE, bool U8 = false, bool LIN = false, int QS = 0>
 #ifndef RT_EXP_U8_PK
 #define RT_EXP_U8_PK 0
 #endif
-__global__ __launch_bounds__(scan_block(R3), scan_dma(R3, U8, QS) ? 2 : (R3 <= RT_WG4_MAX_R3 || (U8 && R3 == 1 && !RT_EXP_U8_PK)) ? 4 : 3)  // workgroups per CU = waves/SIMD: at most 128 / 168 VGPRs (left alone, hipcc takes 200 for nperseg 1024)
+__host__ __device__ constexpr int scan_wgs_per_cu(int r3, int fmt, int qs) {
+    return scan_dma(r3, fmt, qs) ? 2 : (r3 <= RT_WG4_MAX_R3 || (fmt == kFmtU8 && r3 == 1 && !RT_EXP_U8_PK)) ? 4 : 3;
+}
+template <int R3, int MODEF, bool U8 = false, bool LIN = false, int QS = 0>
+__global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF, U8), QS))  // workgroups per CU = waves/SIMD: at most 128 / 168 VGPRs (left alone, hipcc takes 200 for nperseg 1024)
  void stft_scan(const StftParams p) {
-    using raw_t = typename std::conditional<U8, iq_u8, cf>::type;
+    constexpr int MODE = MODEF & (kModeI16 - 1);
+    constexpr int FMT = scan_fmt(MODEF, U8);
+    using raw_t = typename raw_of<FMT>::type;  // (int16 input takes complex64's answer in every `U8 ? :` below: DESIGN 4.13)
     static_assert(QS == 0 || (R3 == 1 && (QS == 2 || QS == 4 || QS == 8)), "QS: lane groups of 2 / 4 / 8 lanes, R3 = 1");
     constexpr int N = QS ? 16 * QS : 256 * R3;
     constexpr int LG = QS ? QS : 16 * R3;
@@ -552,12 +601,12 @@ __global__ __launch_bounds__(scan_block(R3), scan_dma(R3, U8, QS) ? 2 : (R3 <= R
     // One LDS block carved by hand: at nperseg 256 the pieces add up to exactly 40 960 B, a quarter of a CU's LDS
     // (separate __shared__ arrays cannot have size zero, and their placeholders cost the fourth workgroup).
     constexpr bool W_IN_LDS = (R3 <= 8);  // N = 4096: the window comes from L2 as well (3 workgroups per CU)
-    constexpr bool T1_IN_LDS = (R3 <= 4) && !scan_dma(R3, U8, QS);  // (the landing-zone experiment: the factored form, 6 KiB less -- two workgroups' 78 KiB fit a CU)
+    constexpr bool T1_IN_LDS = (R3 <= 4) && !scan_dma(R3, FMT, QS);  // (the landing-zone experiment: the factored form, 6 KiB less -- two workgroups' 78 KiB fit a CU)
     constexpr bool T1_FACTORED = !T1_IN_LDS;
     // (uint8 input at nperseg 256 does run at four workgroups per CU: 106 VGPRs, +3 %)
     // (nperseg 2048: 96 -- with 128 the block is 54 576 B, and LDS is handed out in 512-byte pieces: three workgroups
     // would need 164 352 of the CU's 163 840 B, so the kernel ran at two; profiles/r03_d_stage_stamps.txt)
-    constexpr bool DMA = scan_dma(R3, U8, QS);
+    constexpr bool DMA = scan_dma(R3, FMT, QS);
     constexpr int kStage = (R3 <= RT_WG4_MAX_R3 || (U8 && R3 == 1 && !RT_EXP_U8_PK)) ? 32 : (R3 == 8) ? 96 : DMA ? 64 : kStageCap;  // candidate cells staged per wave before a flush
     constexpr size_t kXchB = sizeof(cf) * (BLK * ROW + GPW * GPAD);
     constexpr size_t kRedB = (LG > 64) ? sizeof(cf) * (BLK / 64) + 16 : 0;  // + the three tail_any words

@@ -74,13 +74,23 @@ __device__ void raw_buffer_load_lds(rsrc_t rsrc, __attribute__((address_space(3)
 
 // Quarters 0 and 1 of a segment (pieces m = 4 j and 4 j + 1: runs of two pieces, 1 KiB of complex64 / 256 B of uint8 pairs)
 // into a wave's area, piece (2 j + n0) at element offset 64 (2 j + n0): sixteen instructions, nothing to wait for here.
+// int16 pairs (256 B a piece): a run of two pieces is 8 bytes a lane, a size the LDS-DMA does not have (1 / 2 / 4 / 12 / 16), so an
+// instruction takes TWO runs at 16 bytes a lane -- lanes 0 .. 31 pieces 8 j, 8 j + 1, lanes 32 .. 63 pieces 8 j + 4, 8 j + 5 (the lane
+// offset carries the gap; the area is filled in lane order, which is the order above) -- eight instructions.
 template <class raw_t>
 __device__ __forceinline__ void w64_prefetch(rsrc_t r, float *area, int lane) {
     constexpr int PB = 64 * (int)sizeof(raw_t);  // bytes of a piece
-    constexpr int SZ = 2 * PB / 64;              // bytes per lane and instruction
+    if constexpr (sizeof(raw_t) == 4) {
+        const int voff = (lane & 31) * 16 + (lane >> 5) * 4 * PB;
 #pragma unroll
-    for (int j = 0; j < 16; ++j)
-        raw_buffer_load_lds(r, (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(area) + 2 * PB * j), SZ, lane * SZ, 4 * PB * j, 0, kAuxNT);
+        for (int j = 0; j < 8; ++j)
+            raw_buffer_load_lds(r, (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(area) + 4 * PB * j), 16, voff, 8 * PB * j, 0, kAuxNT);
+    } else {
+        constexpr int SZ = 2 * PB / 64;          // bytes per lane and instruction
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            raw_buffer_load_lds(r, (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(area) + 2 * PB * j), SZ, lane * SZ, 4 * PB * j, 0, kAuxNT);
+    }
 }
 
 // P[r] for a register index that differs from lane to lane (rt_kernels.h: pick_range, 63 v_cndmask)
@@ -126,9 +136,11 @@ __device__ __forceinline__ bool bit_of(uint32_t lo, uint32_t hi, int r) { return
 // register allocation from 2 spilled registers outside the step to 53 / 152 inside it.)
 
 
-template <int MODE, bool U8, bool LIN>
+template <int MODEF, bool U8, bool LIN>  // (MODEF: MODE, | kModeI16 for int16 input -- rt_kernels.h, scan_fmt)
 __global__ __launch_bounds__(kW64Block, 1) void stft_scan64(const StftParams p) {
-    using raw_t = typename std::conditional<U8, iq_u8, cf>::type;
+    constexpr int MODE = MODEF & (kModeI16 - 1);
+    constexpr int FMT = scan_fmt(MODEF, U8);
+    using raw_t = typename raw_of<FMT>::type;
     using C = typename std::conditional<RT_W64_PK == 1, cfv, cf>::type;    // pass 1
     using C2 = typename std::conditional<RT_W64_PK != 0, cfv, cf>::type;   // twiddles and pass 2
     constexpr int N = 4096;

@@ -131,9 +131,11 @@ __device__ __forceinline__ void wg_emit(const StftParams &p, int s, int seg, con
 // for the detrend by linearity): w[t + BLK j] = c0 + c1 cos(alpha_t + beta_j), alpha_t = 2 pi t / N (the thread's own W_N^t holds its
 // cosine and sine), beta_j = 2 pi j / 32 (constants) -- two fused multiply-adds per sample instead of a table in registers: the table's
 // 32 registers, live from the request to the multiplication, were what made the kernel spill.  Other windows keep the table (from L2).
-template <int BLK, int MODE, bool U8, bool WCOS>
+template <int BLK, int MODEF, bool U8, bool WCOS>  // (MODEF: MODE, | kModeI16 for int16 input -- rt_kernels.h, scan_fmt)
 __global__ __launch_bounds__(BLK, wg_half(BLK) ? 3 : (BLK == 256 ? 2 : 1)) void stft_wg(const StftParams p) {
-    using raw_t = typename std::conditional<U8, iq_u8, cf>::type;
+    constexpr int MODE = MODEF & (kModeI16 - 1);
+    constexpr int FMT = scan_fmt(MODEF, U8);
+    using raw_t = typename raw_of<FMT>::type;
     static_assert(BLK == 256 || BLK == 512, "nperseg 8192 / 16384");
     static_assert(MODE == 0 || MODE == 1 || MODE == 2, "sparse, dense, spectrogram only");
     constexpr int N = 32 * BLK, R = BLK / 16, S1 = wg_row(BLK), NW = BLK / 64;
