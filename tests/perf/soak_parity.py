@@ -2,7 +2,12 @@
 """Randomised parity soak (GPU box): random geometries, thresholds, durations, calibrations, lanes and pulse
 placements (incl. pulses across buffer boundaries and at buffer ends), every stream of every case compared with the
 oracle record by record.  Not part of the pytest suite (minutes of runtime); prints one line per case and a
-summary.  usage: soak_parity.py [seconds] [seed]"""
+summary.  usage: soak_parity.py [--long] [seconds] [seed]
+
+--long: 4 .. 9 consecutive buffers per case instead of 2 .. 3, ragged lengths in two thirds of the cases instead of a third.  Three
+look-back tails rotate, so only from the fourth call on does a scan write a tail that was written before
+(tests/test_gpu_sequences.py).  The option's draws come from a random stream of their own, behind all others: without it every
+recorded (seed, case) is the case it was."""
 import datetime
 import os
 import sys
@@ -16,6 +21,8 @@ from pyradiotracking_amd import synth  # noqa: E402
 from pyradiotracking_amd.analyze import BatchSignalAnalyzer  # noqa: E402
 
 TS0 = datetime.datetime(2024, 1, 1)
+LONG = "--long" in sys.argv[1:]
+sys.argv = [a for a in sys.argv if a != "--long"]
 BIG = os.environ.get("SOAK_BIG") == "1"  # long buffers (1000..8000 segments), 16..128 streams, many pulses per stream
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -37,6 +44,13 @@ while time.time() < t_end:
     if BIG:
         n_streams = int(rng.integers(16, 129))
     n_buf = int(rng.integers(2, 4))
+    rng_long = np.random.default_rng([seed0, case, 17])
+    if LONG:
+        n_buf = int(rng_long.integers(4, 6 if BIG else 10))
+        if not BIG:  # (nine buffers of 400 segments x 4096 samples for 40 streams would be 4.7 GB)
+            n_seg = min(n_seg, 160)
+            blen = n_seg * nperseg + blen % nperseg
+            n_streams = min(n_streams, 16)
     hop = nperseg / fs
     min_ms = float(rng.choice([0.0, 2 * hop * 1e3, 8.0, 5.0]))
     max_ms = float(max(min_ms + 3 * hop * 1e3, rng.choice([10.0, 40.0, 80.0])))
@@ -80,6 +94,8 @@ while time.time() < t_end:
     lanes = int(rng.choice([1, 1, 2, 3]))
     pipelined = bool(rng.random() < 0.4)   # enqueue buffer k + 1 before fetching buffer k
     vary_len = bool(rng.random() < 0.3)    # shorter buffers than sdr_callback_length
+    if LONG:
+        vary_len = vary_len or bool(rng_long.random() < 0.5)
     resets = bool(rng.random() < 0.3)      # single streams restarted between buffers (rt_reset_stream)
     u8 = bool(rng.random() < 0.2)          # RTL-SDR wire format: uint8 I/Q converted in the scan kernel's load
     if u8:
