@@ -809,6 +809,11 @@ void launch_scan(rt_handle *h, const StftParams &sp, int blocks, int fmt, hipStr
 int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr, bool second_pass_only = false, bool own_means = false) {
     sl.call.rec_cap_used = h->rec_cap;
     const CallCtx &c = sl.call;
+    // A call whose thresholds failed their check once keeps the thresholds from its own row means through every further re-run
+    // (record or pool growth, the detrend guard): taken from its own chunk minima again they fail the same check again, and
+    // that re-run is granted once per call -- a pinned RT_MODE_RUNFILTER handle then refused the call (a NaN column: every row
+    // mean NaN, so every positive threshold fails; thousands of NaN records: the record room grows behind the re-run).
+    if (mode == RT_MODE_RUNFILTER && c.thr_rerun && !second_pass_only) own_means = true;
     if (launched) *launched = false;
     if (h->general) {
         // any other power-of-two nperseg: the general transform into the dense map, then the dense extractor (which sums the rows itself)
@@ -2764,6 +2769,9 @@ int rt_spectrogram(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t 
     StftParams sp = make_stft_params(h, h->slot[0], iq_dev, stream_stride, T, 0);
     sp.spec = spec_dev;
     launch_stft<2>(h, sp, h->cfg.n_streams * sp.blocks_per_stream, h->s_scan);
+    if (h->lin)  // (the map scan has no guard of the detrend by linearity: rt_kernels.h)
+        hipLaunchKernelGGL(nan_columns_of_nonfinite_segments, dim3((unsigned)((int64_t)h->cfg.n_streams * T)), dim3(256), 0, h->s_scan,
+                           static_cast<const float2 *>(iq_dev), stream_stride, T, h->N, spec_dev);
     RT_HIP(h, hipGetLastError());
     RT_HIP(h, hipStreamSynchronize(h->s_scan));
     return RT_OK;

@@ -1542,7 +1542,10 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
                 constexpr int kLanesPerGroup = LG < 64 ? LG : 64;
                 const float groups = (float)__builtin_popcountll(__builtin_amdgcn_ballot_w64(chunk_ok)) / (float)kLanesPerGroup;
                 const float d = dsum / (float)kLanesPerGroup;  // D summed over the wave's groups
-                if (d > p.dc_limit * mn * groups && d > p.dc_limit2 * tot && (threadIdx.x & 63) == 0) p.dc_flag[s] = 1;
+                // (a NaN or Inf sample: D or the total is not finite.  SciPy's mean is then NaN or Inf and x - mean NaN at every sample
+                // BEFORE the transform -- an all-NaN column; this form would transform the Inf into +-Inf cells.  Marked as well.)
+                const bool wild = !(d < 3.0e38f) || !(tot < 3.0e38f);
+                if (((d > p.dc_limit * mn * groups && d > p.dc_limit2 * tot) || wild) && (threadIdx.x & 63) == 0) p.dc_flag[s] = 1;
             }
         }
         // deterministic workgroup reduction of the lane groups' row sums: one
@@ -1975,6 +1978,22 @@ __global__ __launch_bounds__(256) void after_bit_scan(uint32_t *abs_hot, uint32_
         stream_overflow[s] = 1;
         atomicOr(counters + 2, flag);
     }
+}
+
+// rt_spectrogram on a handle that detrends by linearity: the map scan (MODE 2) keeps no row sums and so has no guard of that form.
+// A segment that holds a NaN or +-Inf sample is an all-NaN column in the reference (the segment mean is NaN or Inf, x - mean NaN
+// at every sample before the transform), where the form transforms an Inf into +-Inf cells: one workgroup per (stream, segment)
+// reads the segment again and overwrites such a column.  Behind the scan on its stream; the call is a synchronous, cold one.
+__global__ __launch_bounds__(256) void nan_columns_of_nonfinite_segments(const float2 *iq, int64_t stream_stride, int n_seg, int N, float *spec /* [S][T][N] */) {
+    const int64_t st = blockIdx.x;  // stream * n_seg + segment
+    const float2 *x = iq + (st / n_seg) * stream_stride + (st % n_seg) * (int64_t)N;
+    int bad = 0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        const float2 v = x[i];
+        bad |= (!(fabsf(v.x) < INFINITY) || !(fabsf(v.y) < INFINITY)) ? 1 : 0;
+    }
+    if (!__syncthreads_or(bad)) return;
+    for (int i = threadIdx.x; i < N; i += 256) spec[st * N + i] = NAN;
 }
 
 // ---------------------------------------------------------------------------

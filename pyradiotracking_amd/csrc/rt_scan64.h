@@ -695,7 +695,8 @@ __global__ __launch_bounds__(kW64Block, 1) void stft_scan64(const StftParams p) 
                             mn = fminf(mn, __shfl_xor(mn, o));
                             tot += __shfl_xor(tot, o);
                         }
-                        if (dc_acc > p.dc_limit * mn && dc_acc > p.dc_limit2 * tot && lane == 0) p.dc_flag[s] = 1;
+                        const bool wild = !(dc_acc < 3.0e38f) || !(tot < 3.0e38f);  // a NaN or Inf sample (rt_kernels.h: the same guard)
+                        if (((dc_acc > p.dc_limit * mn && dc_acc > p.dc_limit2 * tot) || wild) && lane == 0) p.dc_flag[s] = 1;
                     }
                 }
                 // one partial row of sums per item (= chunk): the detection adds a stream's rows in chunk order, float64

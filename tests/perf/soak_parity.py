@@ -127,16 +127,21 @@ while time.time() < t_end:
         who = np.arange(n_streams) if rng_step.random() < 0.5 else rng_step.choice(n_streams, size=max(1, n_streams // 4), replace=False)
         iq[who, k0 * blen:] *= np.complex64(0.5)
     poison = os.environ.get("SOAK_POISON") == "1" and not u8 and rng.random() < 0.5
+    crash_only = False
+    counted = (n_unexplained, n_field)
     if poison:
         # NaN samples (SOAK_POISON_KIND=nan, the default): a NaN segment and NaN row means in every bin, the same on both
-        # sides.  Inf / huge samples (SOAK_POISON_KIND=all) overflow inside the FFT: whether a bin ends up Inf or NaN -- and
-        # with it whether a row mean is Inf (rejects every other cell of the row) or NaN (accepts them) -- depends on the
-        # order of pocketfft's additions, so the reference itself is not a stable yardstick there; that kind only checks
-        # that nothing crashes.
+        # sides.  SOAK_POISON_KIND=all adds two more kinds (the same six values in the same order: a case's draws stay what they were).
+        # +-Inf components are compared like NaN: the segment mean is Inf and x - mean NaN before the transform, an all-NaN column in
+        # the reference (tests/nonfinite_cases.py).  Huge FINITE samples (1e30, 3e38) overflow inside the FFT: whether a bin ends up
+        # Inf or NaN -- and with it whether a row mean is Inf (rejects every other cell of the row) or NaN (accepts them) -- depends
+        # on the order of pocketfft's additions, so the reference itself is not a stable yardstick there; a case that draws one only
+        # checks that nothing crashes (its differences are printed, not counted).
         for _ in range(int(rng.integers(1, 4))):
-            iq[int(rng.integers(0, n_streams)), int(rng.integers(0, iq.shape[1]))] = rng.choice(
-                np.array([np.nan, complex(np.nan, 1.0)] if os.environ.get("SOAK_POISON_KIND", "nan") == "nan"
-                         else [np.nan, np.inf, complex(0, -np.inf), 1e30, complex(np.nan, 1.0), 3e38], dtype=np.complex64))
+            v = rng.choice(np.array([np.nan, complex(np.nan, 1.0)] if os.environ.get("SOAK_POISON_KIND", "nan") == "nan"
+                                    else [np.nan, np.inf, complex(0, -np.inf), 1e30, complex(np.nan, 1.0), 3e38], dtype=np.complex64))
+            crash_only = crash_only or bool(np.isfinite(v))
+            iq[int(rng.integers(0, n_streams)), int(rng.integers(0, iq.shape[1]))] = v
     kw = dict(sample_rate=fs, fft_nperseg=nperseg, fft_window=window, signal_min_duration_ms=min_ms, signal_max_duration_ms=max_ms,
               signal_threshold_dbw=thr, snr_threshold_db=snr)
     # (round 6: the per-stream record capacity STARTS small -- a stream that needs more grows it inside rt_fetch, so no buffer is
@@ -298,8 +303,10 @@ while time.time() < t_end:
     b.close()
     n_cases += 1
     n_records += nrec
-    n_bad += bad
+    n_bad += 0 if crash_only else bad
+    if crash_only:
+        n_unexplained, n_field = counted
     print(f"case {case}: N={nperseg} fs={fs} {window} T={n_seg} S={n_streams} bufs={n_buf} min/max={min_ms:.2f}/{max_ms:.1f} ms thr={thr} snr={snr} "
-          f"mode={mode} lanes={lanes} cal={'per-stream' if isinstance(cal, list) else cal}{' pipelined' if pipelined else ''}{' ragged' if vary_len else ''}{' restarts' if resets else ''}{' uint8' if u8 else ''}{' device-tensors' if dev_tensor else ''}{' poisoned' if poison else ''}{' noisy' if noisy else ''}{' floor-step' if floor_step else ''}{' noisy-streams=' + str(sorted(noisy_some)) if noisy_some else ''}{' subtract-first' if subtract_first else ''}{' wave-per-stream' if whole_stream else ''} chunk={chunking}: {nrec} records, {bad} mismatching stream-buffers", flush=True)
+          f"mode={mode} lanes={lanes} cal={'per-stream' if isinstance(cal, list) else cal}{' pipelined' if pipelined else ''}{' ragged' if vary_len else ''}{' restarts' if resets else ''}{' uint8' if u8 else ''}{' device-tensors' if dev_tensor else ''}{' poisoned' if poison else ''}{' (crash-only: a huge finite sample)' if crash_only else ''}{' noisy' if noisy else ''}{' floor-step' if floor_step else ''}{' noisy-streams=' + str(sorted(noisy_some)) if noisy_some else ''}{' subtract-first' if subtract_first else ''}{' wave-per-stream' if whole_stream else ''} chunk={chunking}: {nrec} records, {bad} mismatching stream-buffers", flush=True)
 print(f"SOAK: {n_cases} cases, {n_records} oracle records, {n_bad} mismatching stream-buffers "
       f"({n_unexplained} not explained by a float32 round-off margin, {n_field} with a field beyond 0.1 dB)")

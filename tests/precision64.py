@@ -50,6 +50,8 @@ Record bounds (propagated from the cell bounds)
   |d std| <= rms_i (10 / ln 10) * -ln(1 - dP_i / P_i) + C_STD * u * max_i |dB_i|; a plateau holding a cell whose bound
   reaches its value (round-off far under a strong tone) gets an infinite bound on its own.
 * Records with ``start < 0`` take those cells (and their bounds) from the previous buffer's map.
+* NaN (tests/nonfinite_cases.py): a field that is NaN in float64 must be NaN, a finite one finite.  A record whose cells hold a
+  NaN has NaN max, mean and std; a record of a row that holds a NaN elsewhere keeps its bounds on those and has a NaN ``row_mean``.
 
 The constants were fixed from float32 arithmetic only (SciPy's pocketfft and the NumPy restatements in
 ``test_precision_model.py``), about 4x over the worst ratio those reach over the model tests' sweep.
@@ -211,6 +213,10 @@ def record_bounds(rec, ref: Ref64, b: Bounds, L: int, ref_prev: Optional[Ref64] 
             dbs = DB * np.log(P)
             std = float(np.std(dbs)) if np.all(P > 0) else float("nan")
         std_b = float(np.sqrt(np.mean(ddb ** 2))) + C_STD * U * float(np.max(np.abs(dbs))) if np.all(P > 0) else float("inf")
+        if np.isnan(P).any():
+            # a NaN cell (a non-finite sample's column), in this buffer or in the look-back: max, mean and std are NaN in the
+            # reference (np.max propagates it) and must be NaN here -- the std too, which a zero cell would leave unbounded
+            std, std_b = float("nan"), 0.0
         out.append({
             "max_p": (float(P.max()), float(dP.max())),
             "mean_p": (float(P.mean()), float(dP.mean()) + (n + 2) * U * float(P.mean())),

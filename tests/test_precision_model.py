@@ -344,6 +344,23 @@ def test_a_sequential_float32_row_sum_fails_at_config2_length():
     assert abs(sequential[40] - want[40]) > bound[40], (sequential[40], want[40], bound[40])
 
 
+def test_a_finite_value_where_nan_is_due_fails_and_the_reverse():
+    """tests/nonfinite_cases.py: a NaN cell in the reference makes the record's max, mean and std (and its row's mean) NaN."""
+    import dataclasses
+
+    x, spec, recs, fields, ref, b = _tone_case(150)
+    r = recs[0]
+    P = ref.P.copy()
+    P[(max(r.start, 0) + r.end) // 2, r.fi] = np.nan
+    due = p64.check_records(fields[:1], dataclasses.replace(ref, P=P), b, 32).failures
+    assert len(due) == 4 and all(any(f" {k}: " in f for f in due) for k in ("max_p", "mean_p", "std_db", "row_mean")), due  # finite where NaN is due
+    mut = fields.copy()
+    for k in ("max_p", "mean_p", "std_db", "row_mean"):
+        mut[k][0] = np.nan
+    assert len(p64.check_records(mut[:1], ref, b, 32).failures) == 4  # NaN where a finite value is due
+    assert not p64.check_records(mut[:1], dataclasses.replace(ref, P=P), b, 32).failures  # NaN where NaN is due
+
+
 if __name__ == "__main__":
     by_family = {}
     for case in SWEEP:
