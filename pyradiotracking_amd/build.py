@@ -3,7 +3,7 @@
 * ``librt_analyze.so``   gfx950 HIP kernels + C-ABI (include/rt_analyze.h, rt_match.h, rt_format.h) -- the product
 * ``librt_analyze_diag.so``  the same sources with ``-DRT_DIAG`` (csrc/rt_diag.h): the only build that reads the
   laboratory's environment switches -- the fault-injection test loads it; nothing else does
-* ``_rt_hostcheck.so``   host build of csrc/rt_core.h's scalar logic          -- unit tests only
+* ``_rt_hostcheck.so``   host build of csrc/rt_core.h's scalar logic and csrc/rt_tables.h's table builders -- unit tests only
 """
 import os
 import shutil
@@ -104,7 +104,8 @@ def build_library(force=False, verbose=False, diag=False):
 
 def build_hostcheck(force=False, verbose=False):
     src = os.path.join(CSRC, "rt_hostcheck.cpp")
-    if not force and _newer(HOSTCHECK, [src, os.path.join(CSRC, "rt_core.h")]):
+    headers = [os.path.join(REPO, "include", "rt_analyze.h")] + [os.path.join(CSRC, n) for n in sorted(os.listdir(CSRC)) if n.endswith(".h")]
+    if not force and _newer(HOSTCHECK, [src] + headers):
         return HOSTCHECK
     cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-o", HOSTCHECK, src]
     if verbose:

@@ -32,6 +32,7 @@
 #include "rt_general.h"
 #include "rt_f64.h"
 #include "rt_cells.h"
+#include "rt_tables.h"
 
 using namespace rt;
 
@@ -324,6 +325,20 @@ void warn_unknown_switches() {
 }
 #endif
 
+// hipMalloc + upload, and hipMalloc + zero fill, at handle creation.  CHECK is the caller's error macro (RT_CREATE_HIP,
+// RT_F64_CREATE): it sees each call as it is written here with the arguments put in, so a failure still reads
+// "hipMalloc(&h->d_tw1, sizeof(cf) * ...): <hipGetErrorString>" and frees what that macro frees.
+#define RT_DEVICE_COPY(CHECK, dst, src, bytes)                     \
+    do {                                                           \
+        CHECK(hipMalloc(&dst, bytes));                             \
+        CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));  \
+    } while (0)
+#define RT_DEVICE_ZEROS(CHECK, dst, bytes) \
+    do {                                   \
+        CHECK(hipMalloc(&dst, bytes));     \
+        CHECK(hipMemset(dst, 0, bytes));   \
+    } while (0)
+
 int fail_create(int code, const std::string &msg) {
     g_create_error = msg;
     return code;
@@ -336,12 +351,6 @@ size_t rec_lds_bytes(int rec_cap) { return (size_t)std::min(rec_cap, kDenseLdsRe
 // reference appends without limit, analyze.py:449-450) the list is staged in the streams' raw-record areas and finalize_records,
 // the sparse path's last kernel, finishes the call.
 void launch_detect_dense(rt_handle *h, int grid, hipStream_t st, const DetectArgs &a);
-
-int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
 
 // `items` work items (one per stream and group of GPW chunks).  Every mode but the selective pass runs them on a grid
 // that just fills the chip: CUs x the workgroups of this instantiation a CU holds (its __launch_bounds__), each
@@ -487,99 +496,15 @@ void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_s
     else hipLaunchKernelGGL((stft_general<kFmtC64>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
 }
 
-// cells a run must have to pass the duration gate unless it runs through t = 0 (see rt_create)
-long long min_run_cells(const rt_config &cfg, int N) {
-    const double hop = seg_time(1, N, cfg.sample_rate) - seg_time(0, N, cfg.sample_rate);
-    const double cells = cfg.min_duration_s * (1.0 - 1e-9) / hop;
-    return (long long)std::ceil(std::min(cells, 1.0e9)) - 1;
-}
-long long min_run_cells(const rt_handle *h) { return min_run_cells(h->cfg, h->N); }
+// cells a run must have to pass the duration gate unless it runs through t = 0 (rt_core.h)
+long long min_run_cells(const rt_handle *h) { return rt::min_run_cells(h->N, h->cfg.sample_rate, h->cfg.min_duration_s); }
 
 // segments per chunk for a handle of `n_streams` streams (for a laned handle: of all lanes together -- the lanes take the
-// parent's choice, so that a stream's row sums are added in the same order however the batch is split into lanes)
-int choose_chunk(const rt_config &cfg, int R3, int QS, int n_streams, int n_seg) {
-    if (cfg.segs_per_chunk > 0) return cfg.segs_per_chunk;
-    if (cfg.nperseg >= 8192) {
-        // stft_wg: one chunk per workgroup, 512 workgroup slots on the chip (two per CU at 8192; 256 at 16 384).  A workgroup pays
-        // ~2 steps on top of its L (tables, the first segment's round trip with nothing to overlap it, the row sums' stores): chunks of
-        // about 40 segments where the batch fills the chip eight times over, shorter ones -- down to 8 -- for small batches; then the
-        // length that leaves no short last chunk.
-        int L = 40;
-        while (L > 8 && (int64_t)n_streams * ((n_seg + L - 1) / L) < 8 * 512) L -= 8;
-        const int chunks = std::max(1, (n_seg + L - 1) / L);
-        return std::max(1, (n_seg + chunks - 1) / chunks);
-    }
-    const int N = QS ? 16 * QS : 256 * R3, GPW = scan_block(R3) / (QS ? QS : 16 * R3);
-    // enough workgroups to fill 256 CUs several times over, halo overhead <= 1/L
-    int L = 32;
-    // ... but where the run-length pre-filter is possible with chunks of 32 (minimum duration >= 64 hops) the chunks
-    // stay that long for small batches too: its selectivity is p^L (a small batch is launch-bound anyway)
-    // (whatever the mode: the chunk length sets the order of the row sums' partial sums, and the modes return the same bits)
-    const bool keep_long = 2ll * L - 1 <= min_run_cells(cfg, N) && n_seg >= 2 * L;
-    while (L > 4 && !keep_long) {
-        const int64_t chunks = (n_seg + L - 1) / L;
-        const int64_t blocks = (int64_t)n_streams * ((chunks + GPW - 1) / GPW);
-        if (blocks >= 2048) break;
-        L >>= 1;
-    }
-    if (L == 32 && R3 < 4 && n_seg > 32 && !keep_long) {
-        // nperseg <= 512, a batch that fills the chip, no chunk bits to serve: a workgroup holds GPW chunks and its lane groups walk in
-        // step, so a stream costs (workgroups) x L steps whatever its last workgroup holds -- 1 171 segments (the reference's default
-        // geometry) are 37 chunks of 32 in three workgroups of 16, eleven lane groups idle, or 47 chunks of 25 in the same three, one
-        // idle: 22 % fewer steps (551 -> 636 k MS/s).  Among the lengths 20 .. 32 the one with the fewest steps, a step of overhead per
-        // workgroup, and 2 % against multiples of eight (a wave's four lane groups read four chunks L x 2 KiB apart: 32- and 64-KiB
-        // strides are the slowest per step in every sweep).  (Not a function of the number of streams, like the rules below.)
-        // Where the chunk bits exist (config 2 / 4 geometry) the chunks stay 32 long: at config 2 a length of 25 (20 full workgroups
-        // per stream instead of 15.6) makes the scan alone 1.5 - 5.5 % faster on four boxes and the uint8 path 2 %, the whole path with
-        // two lanes the same, and the chunk-bit and exact pre-filter levels 2 - 7 % slower (shorter chunks are less selective, more
-        // workgroups in the second scan); config 4 (2 048 segments = four full workgroups) is fastest at 32 anyway --
-        // profiles/r04_q_chunk_length_sweep_nperseg256.txt.
-        double best = 0.0;
-        for (int cand = 20; cand <= 32; ++cand) {
-            const int64_t chunks = (n_seg + cand - 1) / cand;
-            const int64_t wgs = (chunks + GPW - 1) / GPW;
-            const double cost = (double)wgs * (cand + 1.0) * (cand % 8 == 0 ? 1.02 : 1.0);
-            if (best == 0.0 || cost < best * (1.0 - 1e-9)) {
-                best = cost;
-                L = cand;
-            }
-        }
-    }
-    if (L == 32 && !keep_long && R3 >= 4) {
-        // nperseg >= 1024, a batch that fills the chip: the chunk length is chosen by what a workgroup costs.  All lane
-        // groups of a workgroup take L steps (a last chunk that is short leaves its group idle), and a workgroup pays
-        // c0 steps on top: tables into LDS, the first segment's HBM round trip with nothing to overlap it, the halo
-        // step (nperseg 4096), the row-sum epilogue.  Measured (profiles/r03_a_chunk_length_sweep.txt, one lane):
-        // nperseg 4096, 781 segments: L = 32 -> 71 (11 chunks, none short) takes 5.8 - 6.7 % less time at 1 024 and at
-        // 4 096 streams, L = 52 (a last chunk of one segment) 1.6 % more; that fits c0 = 3.8.  nperseg 1024, 2 343 segments,
-        // four chunks to a workgroup: L = 28 / 31 (84 / 76 chunks: 21 / 19 full workgroups) take 4 % less than 32 (19
-        // workgroups, three chunk slots idle), 36 and 64 more: c0 = 2.  (No term for the end of the launch: the choice
-        // must not depend on the number of streams, or shards of one population would add their row sums in different orders.)
-        // nperseg 2048 (no halo step: c0 = 2.8; 512 streams x 1 000 segments): L = 72 (7 workgroups per stream) 2 % less
-        // than 32, but 48 / 62 / 77 take 4 - 13 % more -- with 3 584 workgroups the launch is under five rounds of the
-        // chip's 768 slots and its last round counts: the search keeps at least eight rounds.
-        const double c0 = R3 >= 16 ? 3.8 : R3 >= 8 ? 2.8 : 2.0;
-        const int lo = 24, hi = R3 >= 8 ? 80 : 40;
-        double best = 0.0;
-        for (int cand = lo; cand <= hi; ++cand) {
-            const int64_t chunks = (n_seg + cand - 1) / cand;
-            const int64_t wgs = (chunks + GPW - 1) / GPW;
-            if ((int64_t)n_streams * wgs < 8 * 768) break;  // (nothing qualifies: L stays 32)
-            const double cost = (double)wgs * (cand + c0);
-            if (best == 0.0 || cost < best * (1.0 - 1e-9)) {
-                best = cost;
-                L = cand;
-            }
-        }
-    }
-    return L;
+// parent's choice, so that a stream's row sums are added in the same order however the batch is split into lanes); rt_core.h
+int choose_chunk(const rt_config &cfg, const ScanFamily &fam, int n_streams, int n_seg) {
+    return rt::choose_chunk(cfg.nperseg, fam.R3, fam.QS, scan_block(fam.R3), cfg.sample_rate, cfg.min_duration_s, cfg.segs_per_chunk, n_streams, n_seg);
 }
 
-int key_tbits(int n_seg) {
-    int t = 1;
-    while ((1ll << t) < (long long)n_seg) ++t;
-    return t;
-}
 
 StftParams make_stft_params(rt_handle *h, Slot &sl, const void *iq, int64_t stream_stride, int n_seg, int tail_write) {
     StftParams p{};
@@ -1431,32 +1356,12 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         return fail_create(RT_E_INVALID, "n_streams, max_samples, window and sample_rate must be set");
     if (!(cfg->max_duration_s >= 0) || !(cfg->min_duration_s >= 0))
         return fail_create(RT_E_INVALID, "durations must be non-negative");
-    int R3 = 0, QS = 0;
-    for (int r : {1, 2, 4, 8, 16})
-        if (cfg->nperseg == 256 * r) R3 = r;
-    for (int q : {2, 4, 8})
-        if (cfg->nperseg == 16 * q) {  // 32 / 64 / 128: the fused scans with lane groups of q lanes (rt_kernels.h: stft_scan<.., QS>)
-            R3 = 1;
-            QS = q;
-        }
-    int big = 0;
-    if (cfg->nperseg == 8192 || cfg->nperseg == 16384) {  // one workgroup per segment (rt_scan_wg.h: stft_wg), sparse and dense path
-        R3 = 1;  // (sizes scratch nobody uses at these sizes)
-        big = wg_block(cfg->nperseg);
-    }
-    bool general = false, bluestein = false;
-    if (!R3) {
-        // every other size the reference may be given (it passes any integer on to SciPy): the other powers of two from 8 to 16 384 by a
-        // general LDS transform, everything else from 8 to 8 192 by Bluestein's algorithm on it -- both on the dense path (rt_general.h)
-        const int n = cfg->nperseg;
-        const bool pow2 = n > 0 && (n & (n - 1)) == 0;
-        if (n < 8 || (pow2 && n > kGeneralMaxN) || (!pow2 && n > kGeneralMaxN / 2))
-            return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(n) + " is not supported: 8 ... 8192, or a power of two up to 16384 (the powers of two from 32 "
-                                                 "on run the fused scan kernels, every other size a general transform on the dense path)");
-        general = true;
-        bluestein = !pow2;
-        R3 = 1;  // (sizes the scratch the general path does not use)
-    }
+    const ScanFamily fam = scan_family(cfg->nperseg);  // which kernels run this size (rt_core.h)
+    if (!fam.supported)
+        return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(cfg->nperseg) + " is not supported: 8 ... 8192, or a power of two up to 16384 (the powers of two from 32 "
+                                             "on run the fused scan kernels, every other size a general transform on the dense path)");
+    const int R3 = fam.R3, QS = fam.QS, big = fam.big;
+    const bool general = fam.general, bluestein = fam.bluestein;
     if (cfg->mode < RT_MODE_AUTO || cfg->mode > RT_MODE_RUNFILTER) return fail_create(RT_E_INVALID, "bad mode");
     if (general && cfg->mode != RT_MODE_AUTO && cfg->mode != RT_MODE_DENSE)
         return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(cfg->nperseg) + " runs on the dense path only: mode must be RT_MODE_AUTO or RT_MODE_DENSE");
@@ -1481,7 +1386,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         for (int k = 0; k < lanes; ++k) {
             rt_config kc = *cfg;
             kc.lanes = 1;
-            kc.segs_per_chunk = choose_chunk(*cfg, R3, QS, cfg->n_streams, (int)(cfg->max_samples / cfg->nperseg));  // the whole batch's choice
+            kc.segs_per_chunk = choose_chunk(*cfg, fam, cfg->n_streams, (int)(cfg->max_samples / cfg->nperseg));  // the whole batch's choice
             kc.n_streams = p->kid_base[(size_t)k + 1] - p->kid_base[(size_t)k];
             // (detection by groups of buckets is decided by the whole batch: the lanes' launches run side by side)
             if (cfg->n_streams >= 1024) kc.flags |= (int32_t)kFlagLaneOfLargeBatch;
@@ -1529,14 +1434,9 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     h->timing = (cfg->flags & RT_FLAG_TIMING) != 0;
     h->rec_cap = cfg->record_capacity > 0 ? cfg->record_capacity : 1024;
     h->stride = probe_stride(h->N, cfg->sample_rate, cfg->min_duration_s);
-    {
-        const double hop = seg_time(1, h->N, cfg->sample_rate) - seg_time(0, h->N, cfg->sample_rate);
-        const double k = std::floor(cfg->max_duration_s / hop) + 2.0;
-        h->K = (int)std::min(k, 1.0e6);
-        if (h->K < 1) h->K = 1;
-    }
+    h->K = tail_cols(h->N, cfg->sample_rate, cfg->max_duration_s);
     h->max_seg = (int)(cfg->max_samples / h->N);
-    h->L = choose_chunk(*cfg, R3, QS, cfg->n_streams, h->max_seg);  // fixed per handle so the scratch bound holds for every call
+    h->L = choose_chunk(*cfg, fam, cfg->n_streams, h->max_seg);  // fixed per handle so the scratch bound holds for every call
     h->max_chunks = std::max(1, (h->max_seg + h->L - 1) / h->L);
     int max_blocks_per_stream = (h->max_chunks + h->GPW - 1) / h->GPW;
     h->max_blocks = max_blocks_per_stream;
@@ -1662,13 +1562,8 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     h->reset_pending.assign((size_t)S, 0);
     if (general) {
         const int M = h->gen_m;
-        std::vector<cf> twg((size_t)M / 2);
-        for (int m = 0; m < M / 2; ++m) {
-            const double ang = -6.283185307179586476925286766559 * (double)m / (double)M;
-            twg[(size_t)m] = cf{(float)std::cos(ang), (float)std::sin(ang)};
-        }
-        RT_CREATE_HIP(hipMalloc(&h->d_twg, sizeof(cf) * twg.size()));
-        RT_CREATE_HIP(hipMemcpy(h->d_twg, twg.data(), sizeof(cf) * twg.size(), hipMemcpyHostToDevice));
+        const std::vector<cf> twg = transform_twiddles<cf, double>(M);
+        RT_DEVICE_COPY(RT_CREATE_HIP, h->d_twg, twg.data(), sizeof(cf) * twg.size());
         {
             std::vector<const void *> big_lds;
 #define RT_BIG_LDS(F_)                                                                                                             \
@@ -1682,199 +1577,48 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
             for (const void *f : big_lds) RT_CREATE_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, padded_len(kGeneralMaxN, 14) * (int)sizeof(cf)));
         }
         if (h->bluestein) {
-            // chirp w[n] = exp(-i pi n^2 / N) (the exponent reduced mod 2 N in integers); the window (times sqrt(scale), as every scan
-            // takes it) times the chirp; the filter conj(w) on -N < m < N, wrapped to length M, its transform in double precision
-            const double pi = 3.14159265358979323846264338327950288;
-            auto chirp = [&](long long n, double sign, double *re, double *im) {
-                const long long e = (n * n) % (2ll * N);
-                const double ang = sign * pi * (double)e / (double)N;
-                *re = std::cos(ang);
-                *im = std::sin(ang);
-            };
-            std::vector<cf> cwin((size_t)N);
-            const double root = std::sqrt((double)cfg->scale);
-            for (int n = 0; n < N; ++n) {
-                double cr, ci;
-                chirp(n, -1.0, &cr, &ci);
-                const double wv = (double)cfg->window[n] * root;
-                cwin[(size_t)n] = cf{(float)(wv * cr), (float)(wv * ci)};
-            }
-            std::vector<double> br((size_t)M, 0.0), bi((size_t)M, 0.0);
-            for (int m = 0; m < N; ++m) {
-                double cr, ci;
-                chirp(m, +1.0, &cr, &ci);
-                br[(size_t)m] = cr;
-                bi[(size_t)m] = ci;
-                if (m) {
-                    br[(size_t)(M - m)] = cr;
-                    bi[(size_t)(M - m)] = ci;
-                }
-            }
-            {  // in-place radix-2 transform of the filter, float64 (bit reversal, then log2 M stages)
-                for (int i = 1, j = 0; i < M; ++i) {
-                    int bit = M >> 1;
-                    for (; j & bit; bit >>= 1) j ^= bit;
-                    j ^= bit;
-                    if (i < j) {
-                        std::swap(br[(size_t)i], br[(size_t)j]);
-                        std::swap(bi[(size_t)i], bi[(size_t)j]);
-                    }
-                }
-                for (int len = 2; len <= M; len <<= 1) {
-                    for (int i = 0; i < M; i += len)
-                        for (int k = 0; k < len / 2; ++k) {
-                            const double ang = -2.0 * pi * (double)k / (double)len;
-                            const double wr = std::cos(ang), wi = std::sin(ang);
-                            const size_t a = (size_t)(i + k), b = (size_t)(i + k + len / 2);
-                            const double xr = br[b] * wr - bi[b] * wi, xi = br[b] * wi + bi[b] * wr;
-                            br[b] = br[a] - xr;
-                            bi[b] = bi[a] - xi;
-                            br[a] += xr;
-                            bi[a] += xi;
-                        }
-                }
-            }
-            // kept in bit-reversed order: the kernel's first transform (decimation in frequency) leaves its values in that order
-            std::vector<cf> bf((size_t)M);
-            for (int i = 0; i < M; ++i) {
-                unsigned r = 0;
-                for (int b = 0; b < h->log2n; ++b) r |= ((unsigned)(i >> b) & 1u) << (h->log2n - 1 - b);
-                bf[(size_t)i] = cf{(float)(br[(size_t)r] / M), (float)(bi[(size_t)r] / M)};
-            }
-            RT_CREATE_HIP(hipMalloc(&h->d_cwin, sizeof(cf) * cwin.size()));
-            RT_CREATE_HIP(hipMemcpy(h->d_cwin, cwin.data(), sizeof(cf) * cwin.size(), hipMemcpyHostToDevice));
-            RT_CREATE_HIP(hipMalloc(&h->d_bfilt, sizeof(cf) * bf.size()));
-            RT_CREATE_HIP(hipMemcpy(h->d_bfilt, bf.data(), sizeof(cf) * bf.size(), hipMemcpyHostToDevice));
+            const BluesteinTables<cf> bt = bluestein_tables<cf, double>(cfg->window, N, M, h->log2n, std::sqrt((double)cfg->scale));
+            RT_DEVICE_COPY(RT_CREATE_HIP, h->d_cwin, bt.cwin.data(), sizeof(cf) * bt.cwin.size());
+            RT_DEVICE_COPY(RT_CREATE_HIP, h->d_bfilt, bt.bfilt.data(), sizeof(cf) * bt.bfilt.size());
         }
     }
-    // window and twiddle tables (twiddles in double, rounded once to float32)
-    std::vector<cf> tw1((size_t)LG * 16), tw2((size_t)R3 * 16);
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int a = 0; a < LG; ++a)
-        for (int k1 = 0; k1 < 16; ++k1) {
-            // (QS: register r = e QS + k1 of lane a holds A[n' = (16 / QS) a + e][k1] and takes W_N^(n' k1))
-            const int e = QS ? (((16 / QS) * a + k1 / QS) * (k1 % QS)) % N : (a * k1) % N;
-            const double ang = -two_pi * (double)e / (double)N;
-            tw1[(size_t)a * 16 + k1] = cf{(float)std::cos(ang), (float)std::sin(ang)};
-        }
-    if (big) {
-        // stft_wg: W_N^(t 2^i), i < 5, as [i][t]; W_BLK^(d p) as [d][p] (rt_scan_wg.h)
-        const int R = big / 16;
-        tw1.assign((size_t)5 * big, cf{1.f, 0.f});
-        for (int i = 0; i < 5; ++i)
-            for (int t = 0; t < big; ++t) {
-                const double ang = -two_pi * (double)(((long long)t << i) % N) / (double)N;
-                tw1[(size_t)i * big + t] = cf{(float)std::cos(ang), (float)std::sin(ang)};
-            }
-        tw2.assign((size_t)R * 16, cf{1.f, 0.f});
-        for (int d = 0; d < R; ++d)
-            for (int pp = 0; pp < 16; ++pp) {
-                const double ang = -two_pi * (double)((d * pp) % big) / (double)big;
-                tw2[(size_t)d * 16 + pp] = cf{(float)std::cos(ang), (float)std::sin(ang)};
-            }
-    }
-    if (scan_wave64(R3)) {
-        // stft_scan64: W_N^(ka n1) with n1 = c + 8 d as W^(8 ka d) (rows 0..6, d = 1..7) times W^(ka c) (rows 7..13, c = 1..7), lane ka
-        tw1.assign((size_t)kW64TwRows * 64, cf{1.f, 0.f});
-        for (int row = 0; row < 14; ++row)
-            for (int ka = 0; ka < 64; ++ka) {
-                const int e = row < 7 ? 8 * ka * (row + 1) : ka * (row - 6);
-                const double ang = -two_pi * (double)(e % N) / (double)N;
-                tw1[(size_t)row * 64 + ka] = cf{(float)std::cos(ang), (float)std::sin(ang)};
-            }
-    }
-    for (int b = 0; b < R3 && !big; ++b)
-        for (int q1 = 0; q1 < 16; ++q1) {
-            // W_LG^(b q1), times the phase W16^(-s q1) that undoes the column rotation s = x1_rotation(b) of exchange 1
-            // (rt_kernels.h): together W_LG^((b - s R3) q1), the exponent reduced in integers
-            const int s1 = ((16 / R3 - 2) * b) & 15;
-            const int e = (((b - s1 * R3) * q1) % LG + LG) % LG;
-            const double ang = -two_pi * (double)e / (double)LG;
-            tw2[(size_t)b * 16 + q1] = cf{(float)std::cos(ang), (float)std::sin(ang)};
-        }
+    // window and twiddle tables, built in rt_tables.h (where each layout is described beside the kernel that reads it)
+    static_assert(kScan64TwiddleRows == kW64TwRows, "rt_tables.h builds stft_scan64's twiddle rows");
+    const ScanTwiddles tw = scan_twiddles(N, R3, QS, big, scan_wave64(R3));
+    const std::vector<float> ws = scaled_window(cfg->window, N, cfg->scale);
     {
         int cus = 0;
         RT_CREATE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
         if (cus > 0) h->n_cu = cus;
     }
     h->h_sub_first.assign((size_t)cfg->n_streams, 0);
-    RT_CREATE_HIP(hipMalloc(&h->d_sub_first, (size_t)cfg->n_streams * sizeof(int32_t)));
-    RT_CREATE_HIP(hipMemset(h->d_sub_first, 0, (size_t)cfg->n_streams * sizeof(int32_t)));
+    RT_DEVICE_ZEROS(RT_CREATE_HIP, h->d_sub_first, (size_t)cfg->n_streams * sizeof(int32_t));
     RT_CREATE_HIP(hipHostMalloc(&h->h_sub_list, (size_t)cfg->n_streams * sizeof(int32_t)));
-    RT_CREATE_HIP(hipMalloc(&h->d_work, 2 * sizeof(uint32_t)));
-    RT_CREATE_HIP(hipMemset(h->d_work, 0, 2 * sizeof(uint32_t)));
-    RT_CREATE_HIP(hipMalloc(&h->d_window, sizeof(float) * N));
-    RT_CREATE_HIP(hipMalloc(&h->d_tw1, sizeof(cf) * tw1.size()));
-    RT_CREATE_HIP(hipMalloc(&h->d_tw2, sizeof(cf) * tw2.size()));
+    RT_DEVICE_ZEROS(RT_CREATE_HIP, h->d_work, 2 * sizeof(uint32_t));
+    RT_DEVICE_COPY(RT_CREATE_HIP, h->d_window, ws.data(), sizeof(float) * N);
+    RT_DEVICE_COPY(RT_CREATE_HIP, h->d_tw1, tw.tw1.data(), sizeof(cf) * tw.tw1.size());
+    RT_DEVICE_COPY(RT_CREATE_HIP, h->d_tw2, tw.tw2.data(), sizeof(cf) * tw.tw2.size());
+    if (big || R3 == 16) {
+        const std::vector<float> wt = big ? window_thread_order(ws, N, big) : window_lane_order(ws, N, LG, scan_wave64(R3));
+        RT_DEVICE_COPY(RT_CREATE_HIP, h->d_window_t, wt.data(), sizeof(float) * N);
+    }
     {
-        // |X|^2 * scale is computed as |X'|^2 with X' the transform of the segment under sqrt(scale) * window:
-        // one multiplication per output cell less in the scan kernel (each coefficient rounded once, from double)
-        std::vector<float> ws((size_t)N);
-        const double root = std::sqrt((double)cfg->scale);
-        for (int i = 0; i < N; ++i) ws[(size_t)i] = (float)((double)cfg->window[i] * root);
-        RT_CREATE_HIP(hipMemcpy(h->d_window, ws.data(), sizeof(float) * N, hipMemcpyHostToDevice));
-        if (big) {
-            // stft_wg reads the window in thread order: [t][32] = window[t + BLK j]
-            std::vector<float> wt((size_t)N);
-            for (int t = 0; t < big; ++t)
-                for (int j = 0; j < 32; ++j) wt[(size_t)t * 32 + j] = ws[(size_t)t + (size_t)big * j];
-            RT_CREATE_HIP(hipMalloc(&h->d_window_t, sizeof(float) * N));
-            RT_CREATE_HIP(hipMemcpy(h->d_window_t, wt.data(), sizeof(float) * N, hipMemcpyHostToDevice));
-        }
-        if (R3 == 16) {
-            std::vector<float> wt((size_t)N);
-            for (int l = 0; l < LG; ++l)
-                for (int m = 0; m < 16; ++m) wt[(size_t)l * 16 + m] = ws[(size_t)l + (size_t)LG * m];
-            if (scan_wave64(R3)) {
-                // the order stft_scan64's lanes read it: 16-byte pieces [n0][jq][lane] holding the elements m = n0 + 4 (4 jq + e)
-                for (int n0 = 0; n0 < 4; ++n0)
-                    for (int jq = 0; jq < 4; ++jq)
-                        for (int l = 0; l < 64; ++l)
-                            for (int e2 = 0; e2 < 4; ++e2)
-                                wt[(((size_t)n0 * 4 + jq) * 64 + l) * 4 + e2] = ws[(size_t)l + 64 * (size_t)(n0 + 4 * (4 * jq + e2))];
-            }
-            RT_CREATE_HIP(hipMalloc(&h->d_window_t, sizeof(float) * N));
-            RT_CREATE_HIP(hipMemcpy(h->d_window_t, wt.data(), sizeof(float) * N, hipMemcpyHostToDevice));
-        }
-        // Transform of the coefficients as the kernel uses them.  If it is real and confined to bins 0 and +-1 (hamming,
-        // hann, boxcar: every cosine-sum window of order <= 1 in get_window's periodic form) the constant detrend is
-        // applied to the transform (LIN kernels); any other window keeps the subtract-first kernels.
-        double wr[3] = {0, 0, 0}, wi[3] = {0, 0, 0};  // W[0], W[1], W[N-1]
-        const int ks[3] = {0, 1, N - 1};
-        for (int j = 0; j < 3; ++j)
-            for (int n = 0; n < N; ++n) {
-                const double ang = -two_pi * (double)(((long long)ks[j] * n) % N) / (double)N;
-                wr[j] += (double)ws[(size_t)n] * std::cos(ang);
-                wi[j] += (double)ws[(size_t)n] * std::sin(ang);
-            }
-        // the window is of that form iff the three bins reproduce it:  w[n] = (W0 + W1 e^(+i t) + W_(N-1) e^(-i t)) / N
-        double wmax = 0.0, dev = 0.0;
-        for (int n = 0; n < N; ++n) {
-            const double t = two_pi * (double)n / (double)N;
-            const double fit = (wr[0] + (wr[1] + wr[2]) * std::cos(t) - (wi[1] - wi[2]) * std::sin(t)) / N;
-            wmax = std::max(wmax, std::fabs((double)ws[(size_t)n]));
-            dev = std::max(dev, std::fabs((double)ws[(size_t)n] - fit));
-        }
-        const double w0 = std::fabs(wr[0]);
-        bool cosine_sum = w0 > 0.0 && dev <= 1e-6 * wmax;
-        for (int j = 0; j < 3; ++j)
-            if (std::fabs(wi[j]) > 1e-6 * w0) cosine_sum = false;  // real transform (w[n] = w[N-n])
-        const bool ok = cosine_sum && !(cfg->flags & RT_FLAG_NO_LIN_DETREND) && !big;
-        h->lin = ok;
-        if (ok) {
-            for (int j = 0; j < 3; ++j) h->lin_c[j] = (float)(wr[j] / N);
+        // If the window is a cosine sum of order <= 1 the constant detrend is applied to the transform (LIN kernels); any other
+        // window keeps the subtract-first kernels.
+        const CosineFit fit = fit_cosine_window(ws, N);
+        h->lin = fit.cosine_sum && !(cfg->flags & RT_FLAG_NO_LIN_DETREND) && !big;
+        if (h->lin) {
+            for (int j = 0; j < 3; ++j) h->lin_c[j] = (float)(fit.wr[j] / N);
         }
         if (big) {
             // stft_wg subtracts the mean first, in SciPy's order (no linearity form, no guard); what it takes from the fit is the WINDOW:
-            // w[n] = c0 + c1 cos(2 pi n / N), c0 = W[0] / N, c1 = (W[1] + W[N-1]) / N (rt_scan_wg.h: WCOS)
-            h->wcos = cosine_sum;
-            h->lin_c[0] = (float)(wr[0] / N);
-            h->lin_c[1] = (float)((wr[1] + wr[2]) / N);
+            // w[n] = c0 + c1 cos 2 pi n / N, c0 = W[0] / N, c1 = (W[1] + W[N-1]) / N (rt_scan_wg.h: WCOS)
+            h->wcos = fit.cosine_sum;
+            h->lin_c[0] = (float)(fit.wr[0] / N);
+            h->lin_c[1] = (float)((fit.wr[1] + fit.wr[2]) / N);
             h->lin_c[2] = 0.f;
         }
     }
-    RT_CREATE_HIP(hipMemcpy(h->d_tw1, tw1.data(), sizeof(cf) * tw1.size(), hipMemcpyHostToDevice));
-    RT_CREATE_HIP(hipMemcpy(h->d_tw2, tw2.data(), sizeof(cf) * tw2.size(), hipMemcpyHostToDevice));
 
     const size_t psum_bytes = (size_t)S * max_blocks_per_stream * N * sizeof(float);
     const size_t tail_bytes = (size_t)S * h->K * N * sizeof(float);
@@ -1891,8 +1635,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         if (h->runfilter_ok) {
             const size_t cells = (size_t)S * std::max(h->max_seg, 1) * LG;
             RT_CREATE_HIP(hipMalloc(&sl.d_cell_hot, cells * sizeof(uint16_t)));
-            RT_CREATE_HIP(hipMalloc(&sl.d_cell_need, cells * sizeof(uint16_t)));
-            RT_CREATE_HIP(hipMemset(sl.d_cell_need, 0, cells * sizeof(uint16_t)));  // (all zeros between calls: plan_runs writes only the words that keep anything)
+            RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_cell_need, cells * sizeof(uint16_t));  // (all zeros between calls: plan_runs writes only the words that keep anything)
             RT_CREATE_HIP(hipMalloc(&sl.d_chunk_min, std::max<size_t>(psum_bytes, 4)));  // (a row per work item, like psum)
             RT_CREATE_HIP(hipMalloc(&sl.d_thr_bin, (size_t)S * N * sizeof(float)));
             RT_CREATE_HIP(hipMalloc(&sl.d_thr_nat, (size_t)S * N * sizeof(float)));
@@ -1901,23 +1644,18 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
             *sl.h_seg_total = 0;
         }
         if (sl.d_full || sl.d_cell_hot) {
-            RT_CREATE_HIP(hipMalloc(&sl.d_abs_hot, (size_t)S * sizeof(uint32_t)));
-            RT_CREATE_HIP(hipMemset(sl.d_abs_hot, 0, (size_t)S * sizeof(uint32_t)));
+            RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_abs_hot, (size_t)S * sizeof(uint32_t));
             RT_CREATE_HIP(hipHostMalloc(&sl.h_abs_hot, sizeof(uint32_t)));
             *sl.h_abs_hot = 0u;
         }
         RT_CREATE_HIP(hipMalloc(&sl.d_hot, (size_t)S * kBuckets * h->hot_cap * sizeof(uint2)));
-        RT_CREATE_HIP(hipMalloc(&sl.d_hot_count, (size_t)S * kBuckets * sizeof(uint32_t)));
-        RT_CREATE_HIP(hipMalloc(&sl.d_hot_seen, (size_t)S * kBuckets * sizeof(uint32_t)));
-        RT_CREATE_HIP(hipMemset(sl.d_hot_seen, 0, (size_t)S * kBuckets * sizeof(uint32_t)));
+        RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_hot_count, (size_t)S * kBuckets * sizeof(uint32_t));
+        RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_hot_seen, (size_t)S * kBuckets * sizeof(uint32_t));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_hot_total, (size_t)S * sizeof(int32_t)));
         std::memset(sl.h_hot_total, 0, (size_t)S * sizeof(int32_t));
         RT_CREATE_HIP(hipMalloc(&sl.d_raw, (size_t)S * h->rec_cap * sizeof(rt_record)));
-        RT_CREATE_HIP(hipMalloc(&sl.d_raw_count, (size_t)S * sizeof(int32_t)));
-        RT_CREATE_HIP(hipMalloc(&sl.d_counters, kCounterWords * sizeof(unsigned long long)));
-        RT_CREATE_HIP(hipMemset(sl.d_hot_count, 0, (size_t)S * kBuckets * sizeof(uint32_t)));
-        RT_CREATE_HIP(hipMemset(sl.d_raw_count, 0, (size_t)S * sizeof(int32_t)));
-        RT_CREATE_HIP(hipMemset(sl.d_counters, 0, kCounterWords * sizeof(unsigned long long)));
+        RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_raw_count, (size_t)S * sizeof(int32_t));
+        RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_counters, kCounterWords * sizeof(unsigned long long));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_counters, kCounterWords * sizeof(unsigned long long)));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_rec_offset, (size_t)S * sizeof(int32_t)));
         RT_CREATE_HIP(hipHostMalloc(&sl.h_rec_count, (size_t)S * sizeof(int32_t)));
@@ -1936,8 +1674,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         if (cfg->flags & RT_FLAG_RECORD_CELLS) {
             sl.cell_cap = std::max<int64_t>(64, std::min<int64_t>(kInitialPoolCells, 16 * sl.pool_cap));
             RT_CREATE_HIP(hipMalloc(&sl.d_cells, (size_t)sl.cell_cap * sizeof(float)));
-            RT_CREATE_HIP(hipMalloc(&sl.d_hot_kept, (size_t)S * kBuckets * sizeof(uint32_t)));
-            RT_CREATE_HIP(hipMemset(sl.d_hot_kept, 0, (size_t)S * kBuckets * sizeof(uint32_t)));
+            RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_hot_kept, (size_t)S * kBuckets * sizeof(uint32_t));
             RT_CREATE_HIP(hipMalloc(&sl.d_stream_cells, (size_t)S * sizeof(long long)));
             RT_CREATE_HIP(hipMalloc(&sl.d_stream_base, (size_t)S * sizeof(long long)));
             RT_CREATE_HIP(hipHostMalloc(&sl.h_cells_info, 2 * sizeof(unsigned long long)));
@@ -3003,37 +2740,6 @@ int rt_dev_download(int32_t device, void *dst_host, const void *src_dev, size_t 
 // ---- float64 handles (include/rt_analyze.h: rt_create_f64; kernels: rt_f64.h) ----
 namespace {
 
-// W_M^j = exp(-2 pi i j / M), j < M / 2, and the chirp w[n] = exp(-i pi n^2 / N) with n^2 reduced mod 2 N in integers: sin / cos
-// in long double, rounded once to double
-constexpr long double kPiL = 3.141592653589793238462643383279502884L;
-cd f64_expi(long double a) { return cd{(double)cosl(a), (double)sinl(a)}; }
-
-// FFT_M in long double on the host (iterative radix-2): the transform of Bluestein's chirp filter
-void host_fft_ld(std::vector<long double> &re, std::vector<long double> &im) {
-    const size_t M = re.size();
-    for (size_t i = 1, j = 0; i < M; ++i) {
-        size_t bit = M >> 1;
-        for (; j & bit; bit >>= 1) j ^= bit;
-        j ^= bit;
-        if (i < j) {
-            std::swap(re[i], re[j]);
-            std::swap(im[i], im[j]);
-        }
-    }
-    for (size_t len = 2; len <= M; len <<= 1)
-        for (size_t i = 0; i < M; i += len)
-            for (size_t k = 0; k < len / 2; ++k) {
-                const long double a = -2.0L * kPiL * (long double)k / (long double)len;
-                const long double wr = cosl(a), wi = sinl(a);
-                const size_t u = i + k, v = i + k + len / 2;
-                const long double xr = re[v] * wr - im[v] * wi, xi = re[v] * wi + im[v] * wr;
-                re[v] = re[u] - xr;
-                im[v] = im[u] - xi;
-                re[u] += xr;
-                im[u] += xi;
-            }
-}
-
 int f64_err(rt_handle *h, int code, const std::string &msg) {
     h->err = msg;
     return code;
@@ -3341,12 +3047,7 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     while ((1 << f->log2m) < f->M) ++f->log2m;
     f->SPB = std::max(1, std::min(64, 1024 / f->M));
     f->stride = probe_stride(n, cfg->sample_rate, cfg->min_duration_s);
-    {
-        const double hop = seg_time(1, n, cfg->sample_rate) - seg_time(0, n, cfg->sample_rate);
-        const double k = std::floor(cfg->max_duration_s / hop) + 2.0;
-        f->K = (int)std::min(k, 1.0e6);
-        if (f->K < 1) f->K = 1;
-    }
+    f->K = tail_cols(n, cfg->sample_rate, cfg->max_duration_s);
     f->max_seg = (int)(cfg->max_samples / n);
     f->rec_cap = cfg->record_capacity > 0 ? cfg->record_capacity : 1024;
     f->reset_pending.assign((size_t)cfg->n_streams, 0);
@@ -3369,45 +3070,15 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
         h->own_scan_stream = true;
     }
     h->s_detect = h->s_scan;
-    // tables, made on the host so that every entry is rounded once to double
+    // tables, made on the host so that every entry is rounded once to double (rt_tables.h)
     {
-        std::vector<cd> tw((size_t)f->M / 2);
-        for (int j = 0; j < f->M / 2; ++j) tw[(size_t)j] = f64_expi(-2.0L * kPiL * (long double)j / (long double)f->M);
-        RT_F64_CREATE(hipMalloc(&f->d_tw, tw.size() * sizeof(cd)));
-        RT_F64_CREATE(hipMemcpy(f->d_tw, tw.data(), tw.size() * sizeof(cd), hipMemcpyHostToDevice));
-        RT_F64_CREATE(hipMalloc(&f->d_window, (size_t)n * sizeof(double)));
-        RT_F64_CREATE(hipMemcpy(f->d_window, f64->window, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        const std::vector<cd> tw = transform_twiddles<cd, long double>(f->M);
+        RT_DEVICE_COPY(RT_F64_CREATE, f->d_tw, tw.data(), tw.size() * sizeof(cd));
+        RT_DEVICE_COPY(RT_F64_CREATE, f->d_window, f64->window, (size_t)n * sizeof(double));
         if (f->blu) {
-            const int M = f->M;
-            std::vector<cd> cwin((size_t)n), chirp((size_t)n);
-            for (int k = 0; k < n; ++k) {
-                const long long r = ((long long)k * k) % (2LL * n);  // exp(-i pi k^2 / N) has period 2 N in k^2
-                chirp[(size_t)k] = f64_expi(-kPiL * (long double)r / (long double)n);
-                const long double w = (long double)f64->window[k];
-                const long double a = -kPiL * (long double)r / (long double)n;
-                cwin[(size_t)k] = cd{(double)(w * cosl(a)), (double)(w * sinl(a))};
-            }
-            std::vector<long double> re((size_t)M, 0.0L), im((size_t)M, 0.0L);
-            for (int k = 0; k < n; ++k) {  // the filter conj(w[m]) at m = k and m = M - k
-                const long long r = ((long long)k * k) % (2LL * n);
-                const long double a = kPiL * (long double)r / (long double)n;
-                re[(size_t)k] = cosl(a);
-                im[(size_t)k] = sinl(a);
-                if (k) {
-                    re[(size_t)(M - k)] = cosl(a);
-                    im[(size_t)(M - k)] = sinl(a);
-                }
-            }
-            host_fft_ld(re, im);
-            std::vector<cd> bf((size_t)M);
-            for (int i = 0; i < M; ++i) {  // bit-reversed order (the DIF transform's output order), divided by M
-                const unsigned rv = __builtin_bitreverse32((unsigned)i) >> (32 - f->log2m);
-                bf[(size_t)i] = cd{(double)(re[rv] / (long double)M), (double)(im[rv] / (long double)M)};
-            }
-            RT_F64_CREATE(hipMalloc(&f->d_cwin, (size_t)n * sizeof(cd)));
-            RT_F64_CREATE(hipMemcpy(f->d_cwin, cwin.data(), (size_t)n * sizeof(cd), hipMemcpyHostToDevice));
-            RT_F64_CREATE(hipMalloc(&f->d_bfilt, (size_t)M * sizeof(cd)));
-            RT_F64_CREATE(hipMemcpy(f->d_bfilt, bf.data(), (size_t)M * sizeof(cd), hipMemcpyHostToDevice));
+            const BluesteinTables<cd> bt = bluestein_tables<cd, long double>(f64->window, n, f->M, f->log2m, 1.0L);
+            RT_DEVICE_COPY(RT_F64_CREATE, f->d_cwin, bt.cwin.data(), (size_t)n * sizeof(cd));
+            RT_DEVICE_COPY(RT_F64_CREATE, f->d_bfilt, bt.bfilt.data(), (size_t)f->M * sizeof(cd));
         }
     }
     const int lds = f->SPB * f->M * (int)sizeof(cd);
@@ -3419,12 +3090,10 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     // the float64 map (S T N 8 bytes) and the look-back tails
     RT_F64_CREATE(hipMalloc(&f->d_map, std::max<size_t>(8, S * (size_t)f->max_seg * (size_t)n * sizeof(double))));
     for (double *&t : f->d_tail) {
-        RT_F64_CREATE(hipMalloc(&t, S * (size_t)f->K * (size_t)n * sizeof(double)));
-        RT_F64_CREATE(hipMemset(t, 0, S * (size_t)f->K * (size_t)n * sizeof(double)));
+        RT_DEVICE_ZEROS(RT_F64_CREATE, t, S * (size_t)f->K * (size_t)n * sizeof(double));
     }
     for (F64Slot &sl : f->slot) {
-        RT_F64_CREATE(hipMalloc(&sl.d_raw_count, S * sizeof(int32_t)));
-        RT_F64_CREATE(hipMemset(sl.d_raw_count, 0, S * sizeof(int32_t)));
+        RT_DEVICE_ZEROS(RT_F64_CREATE, sl.d_raw_count, S * sizeof(int32_t));
         RT_F64_CREATE(hipMalloc(&sl.d_no_last, S * sizeof(int32_t)));
         RT_F64_CREATE(hipHostMalloc(&sl.h_meta, (2 * S + 1) * sizeof(int32_t)));
         if (cfg->flags & RT_FLAG_ROW_MEANS) RT_F64_CREATE(hipMalloc(&sl.d_row_means, S * (size_t)n * sizeof(double)));

@@ -12,12 +12,16 @@
 //   * timedelta microsecond rounding   CPython Modules/_datetimemodule.c
 //                                      (delta_new / accum), used by the shadow
 //                                      filter analyze.py:300-311 (T16)
+// and the geometry a handle derives from its configuration on the host (look-back columns, chunk length, kernel family).
 #ifndef RT_CORE_H
 #define RT_CORE_H
 
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
 #include <type_traits>
 #include <utility>
 
@@ -28,6 +32,15 @@
 #endif
 
 namespace rt {
+
+// A complex value as two floats / two doubles: the element type of the kernels' tables and registers (arithmetic on them:
+// rt_fft.h, rt_f64.h) and of the host's table builders (rt_tables.h).
+struct cf {
+    float x, y;
+};
+struct cd {
+    double x, y;
+};
 
 // Geometry/thresholds of one detect pass (one spectrogram of T columns).  P is the power type of the map: float for
 // the complex64 path, double for a float64 handle (rt_create_f64), whose thresholds are the reference's Python floats.
@@ -148,6 +161,165 @@ RT_HD int32_t probe_stride(int32_t nperseg, double fs, double min_d) {
     int32_t s = (q >= 2147483647.0) ? 2147483647 : (int32_t)q;  // int() truncates toward zero
     return s < 1 ? 1 : s;
 }
+
+// ---- Geometry of a handle (host side of rt_analyze.hip; here so that the CPU suite can test it: tests/test_host_tables.py) ----
+
+// K: the trailing columns of the previous buffer's map a look-back can reach -- floor(max duration / hop) + 2, at most 1e6
+inline int tail_cols(int nperseg, double fs, double max_d) {
+    const double hop = seg_time(1, nperseg, fs) - seg_time(0, nperseg, fs);
+    const double k = std::floor(max_d / hop) + 2.0;
+    const int K = (int)std::min(k, 1.0e6);
+    return K < 1 ? 1 : K;
+}
+
+// cells a run must have to pass the duration gate unless it runs through t = 0: (len + 1) * hop < signal_min_duration fails
+// the gate (analyze.py:427-430; gate_run below), with a margin of 1e-9 for the rounding of the float64 expressions
+inline long long min_run_cells(int N, double fs, double min_d) {
+    const double hop = seg_time(1, N, fs) - seg_time(0, N, fs);
+    const double cells = min_d * (1.0 - 1e-9) / hop;
+    return (long long)std::ceil(std::min(cells, 1.0e9)) - 1;
+}
+
+inline int next_pow2(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+// bits of the segment index in a 32-bit cell key
+inline int key_tbits(int n_seg) {
+    int t = 1;
+    while ((1ll << t) < (long long)n_seg) ++t;
+    return t;
+}
+
+// Which kernel family an nperseg runs on:
+//   256 r, r in {1, 2, 4, 8, 16}   the fused scans (rt_kernels.h: stft_scan<R3 = r>; 4096: rt_scan64.h), lane groups of 16 r lanes
+//   16 q, q in {2, 4, 8}           the fused scans with lane groups of q lanes (stft_scan<1, .., QS = q>)
+//   8192, 16 384                   one workgroup per segment (rt_scan_wg.h: stft_wg), `big` = its threads (nperseg / 32); sparse and dense path
+//   every other size the reference may be given (it passes any integer on to SciPy): the other powers of two from 8 to 16 384 by a
+//   general LDS transform, everything else from 8 to 8 192 by Bluestein's algorithm on it -- both on the dense path (rt_general.h)
+// R3 = 1 in the last two (it sizes scratch nobody uses there).
+constexpr int kGeneralMaxN = 16384;  // the general transform's longest segment: 128 KiB of LDS
+struct ScanFamily {
+    int R3 = 0, QS = 0, big = 0;
+    bool general = false, bluestein = false;
+    bool supported = false;
+};
+inline ScanFamily scan_family(int nperseg) {
+    ScanFamily f;
+    for (int r : {1, 2, 4, 8, 16})
+        if (nperseg == 256 * r) f.R3 = r;
+    for (int q : {2, 4, 8})
+        if (nperseg == 16 * q) {
+            f.R3 = 1;
+            f.QS = q;
+        }
+    if (nperseg == 8192 || nperseg == 16384) {
+        f.R3 = 1;
+        f.big = nperseg / 32;  // (rt_scan_wg.h: wg_block)
+    }
+    f.supported = true;
+    if (!f.R3) {
+        const int n = nperseg;
+        const bool pow2 = n > 0 && (n & (n - 1)) == 0;
+        f.supported = !(n < 8 || (pow2 && n > kGeneralMaxN) || (!pow2 && n > kGeneralMaxN / 2));
+        f.general = true;
+        f.bluestein = !pow2;
+        f.R3 = 1;
+    }
+    return f;
+}
+
+// Segments per chunk for a handle of `n_streams` streams whose buffers hold up to `n_seg` segments; `block` = threads of a scan
+// workgroup (rt_kernels.h: scan_block(R3)), `segs_per_chunk` > 0 forces the length (rt_config.segs_per_chunk).  The chunk length
+// sets the order in which a row's partial sums are added, so every part of one population must run with the same one: a laned
+// handle asks with the number of streams of all lanes together and hands the answer to its lanes as a forced length.  The choice
+// does depend on that number, in two places: the halving for batches too small to fill the chip (`blocks >= 2048`, and stft_wg's
+// `8 * 512`), and the "at least eight rounds" cut-off of the nperseg >= 1024 search -- shards of one population that are to add
+// their row sums in the same order must pass the whole population's count (or force the length), as the lanes do.
+inline int choose_chunk(int nperseg, int R3, int QS, int block, double fs, double min_duration_s, int segs_per_chunk, int n_streams, int n_seg) {
+    if (segs_per_chunk > 0) return segs_per_chunk;
+    if (nperseg >= 8192) {
+        // stft_wg: one chunk per workgroup, 512 workgroup slots on the chip (two per CU at 8192; 256 at 16 384).  A workgroup pays
+        // ~2 steps on top of its L (tables, the first segment's round trip with nothing to overlap it, the row sums' stores): chunks of
+        // about 40 segments where the batch fills the chip eight times over, shorter ones -- down to 8 -- for small batches; then the
+        // length that leaves no short last chunk.
+        int L = 40;
+        while (L > 8 && (int64_t)n_streams * ((n_seg + L - 1) / L) < 8 * 512) L -= 8;
+        const int chunks = std::max(1, (n_seg + L - 1) / L);
+        return std::max(1, (n_seg + chunks - 1) / chunks);
+    }
+    const int N = QS ? 16 * QS : 256 * R3, GPW = block / (QS ? QS : 16 * R3);
+    // enough workgroups to fill 256 CUs several times over, halo overhead <= 1/L
+    int L = 32;
+    // ... but where the run-length pre-filter is possible with chunks of 32 (minimum duration >= 64 hops) the chunks
+    // stay that long for small batches too: its selectivity is p^L (a small batch is launch-bound anyway)
+    // (whatever the mode: the chunk length sets the order of the row sums' partial sums, and the modes return the same bits)
+    const bool keep_long = 2ll * L - 1 <= min_run_cells(N, fs, min_duration_s) && n_seg >= 2 * L;
+    while (L > 4 && !keep_long) {
+        const int64_t chunks = (n_seg + L - 1) / L;
+        const int64_t blocks = (int64_t)n_streams * ((chunks + GPW - 1) / GPW);
+        if (blocks >= 2048) break;
+        L >>= 1;
+    }
+    if (L == 32 && R3 < 4 && n_seg > 32 && !keep_long) {
+        // nperseg <= 512, a batch that fills the chip, no chunk bits to serve: a workgroup holds GPW chunks and its lane groups walk in
+        // step, so a stream costs (workgroups) x L steps whatever its last workgroup holds -- 1 171 segments (the reference's default
+        // geometry) are 37 chunks of 32 in three workgroups of 16, eleven lane groups idle, or 47 chunks of 25 in the same three, one
+        // idle: 22 % fewer steps (551 -> 636 k MS/s).  Among the lengths 20 .. 32 the one with the fewest steps, a step of overhead per
+        // workgroup, and 2 % against multiples of eight (a wave's four lane groups read four chunks L x 2 KiB apart: 32- and 64-KiB
+        // strides are the slowest per step in every sweep).  (The search itself does not read the number of streams; whether it runs
+        // does: only a batch that kept L = 32 through the halving above gets here.)
+        // Where the chunk bits exist (config 2 / 4 geometry) the chunks stay 32 long: at config 2 a length of 25 (20 full workgroups
+        // per stream instead of 15.6) makes the scan alone 1.5 - 5.5 % faster on four boxes and the uint8 path 2 %, the whole path with
+        // two lanes the same, and the chunk-bit and exact pre-filter levels 2 - 7 % slower (shorter chunks are less selective, more
+        // workgroups in the second scan); config 4 (2 048 segments = four full workgroups) is fastest at 32 anyway --
+        // profiles/r04_q_chunk_length_sweep_nperseg256.txt.
+        double best = 0.0;
+        for (int cand = 20; cand <= 32; ++cand) {
+            const int64_t chunks = (n_seg + cand - 1) / cand;
+            const int64_t wgs = (chunks + GPW - 1) / GPW;
+            const double cost = (double)wgs * (cand + 1.0) * (cand % 8 == 0 ? 1.02 : 1.0);
+            if (best == 0.0 || cost < best * (1.0 - 1e-9)) {
+                best = cost;
+                L = cand;
+            }
+        }
+    }
+    if (L == 32 && !keep_long && R3 >= 4) {
+        // nperseg >= 1024, a batch that fills the chip: the chunk length is chosen by what a workgroup costs.  All lane
+        // groups of a workgroup take L steps (a last chunk that is short leaves its group idle), and a workgroup pays
+        // c0 steps on top: tables into LDS, the first segment's HBM round trip with nothing to overlap it, the halo
+        // step (nperseg 4096), the row-sum epilogue.  Measured (profiles/r03_a_chunk_length_sweep.txt, one lane):
+        // nperseg 4096, 781 segments: L = 32 -> 71 (11 chunks, none short) takes 5.8 - 6.7 % less time at 1 024 and at
+        // 4 096 streams, L = 52 (a last chunk of one segment) 1.6 % more; that fits c0 = 3.8.  nperseg 1024, 2 343 segments,
+        // four chunks to a workgroup: L = 28 / 31 (84 / 76 chunks: 21 / 19 full workgroups) take 4 % less than 32 (19
+        // workgroups, three chunk slots idle), 36 and 64 more: c0 = 2.  (The cost has no term for the end of the launch, so that
+        // the winner does not move with the number of streams; the cut-off below does read it.)
+        // nperseg 2048 (no halo step: c0 = 2.8; 512 streams x 1 000 segments): L = 72 (7 workgroups per stream) 2 % less
+        // than 32, but 48 / 62 / 77 take 4 - 13 % more -- with 3 584 workgroups the launch is under five rounds of the
+        // chip's 768 slots and its last round counts: the search keeps at least eight rounds.
+        const double c0 = R3 >= 16 ? 3.8 : R3 >= 8 ? 2.8 : 2.0;
+        const int lo = 24, hi = R3 >= 8 ? 80 : 40;
+        double best = 0.0;
+        for (int cand = lo; cand <= hi; ++cand) {
+            const int64_t chunks = (n_seg + cand - 1) / cand;
+            const int64_t wgs = (chunks + GPW - 1) / GPW;
+            if ((int64_t)n_streams * wgs < 8 * 768) break;  // (nothing qualifies: L stays 32)
+            const double cost = (double)wgs * (cand + c0);
+            if (best == 0.0 || cost < best * (1.0 - 1e-9)) {
+                best = cost;
+                L = cand;
+            }
+        }
+    }
+    return L;
+}
+
+// Column rotation of exchange 1 in the fused scans with R3 > 1 (rt_kernels.h: "Exchange layouts"): s1(b) = (16 / R3 - 2) * b mod 16.
+// The kernel rotates by it; the host folds the phase that undoes it into the pass-2 twiddles (rt_tables.h: scan_twiddles).
+RT_HD int x1_rotation(int R3, int b) { return ((16 / R3 - 2) * b) & 15; }
 
 // `not (p < thr) and not (p / avg < snr)` in float32
 RT_HD bool cell_above(float p, float avg, float thr, float snr) {

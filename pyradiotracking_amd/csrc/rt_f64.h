@@ -18,9 +18,7 @@
 
 namespace rt {
 
-struct cd {
-    double x, y;
-};
+// (struct cd, two doubles: rt_core.h)
 __device__ __forceinline__ cd dadd(cd a, cd b) { return cd{a.x + b.x, a.y + b.y}; }
 __device__ __forceinline__ cd dsub(cd a, cd b) { return cd{a.x - b.x, a.y - b.y}; }
 __device__ __forceinline__ cd dmul(cd a, cd b) { return cd{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
@@ -40,7 +38,7 @@ struct F64StftParams {
     const double *window;    // [N] float64 window (powers of two)
     const cd *cwin;          // [N] window * exp(-i pi n^2 / N) (Bluestein)
     const cd *bfilt;         // [M] FFT_M of the chirp filter / M, bit-reversed order (Bluestein)
-    const cd *tw;            // [M / 2] W_M^j
+    const cd *tw;            // [M / 2] W_M^j  (these three: rt_tables.h, bluestein_tables / transform_twiddles in long double)
     double *spec;            // [S][T][N]
     double *tail;            // [S][K][N], or null
 };

@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rt_core.h"
+
 namespace rt {
 
 // Two forms of a complex value, the same IEEE operations in the same order (bit-identical spectra):
@@ -16,9 +18,7 @@ namespace rt {
 //        the SIMD ~1.45 x as long as a scalar one, so the step gains 1.7 %, and only where the registers are free: the
 //        complex64 kernels of nperseg 256 use it (stft_scan: PK), every other instantiation keeps the scalar form
 //        (spills at nperseg >= 512, the four-workgroup limit of the uint8 kernels; EXPERIMENTS.md, round 3, entry 20).
-struct cf {
-    float x, y;
-};
+// (struct cf: rt_core.h)
 typedef float cfv __attribute__((ext_vector_type(2)));
 template <class C> __device__ __forceinline__ C make_c(float x, float y);
 template <> __device__ __forceinline__ cf make_c<cf>(float x, float y) { return cf{x, y}; }

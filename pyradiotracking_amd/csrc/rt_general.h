@@ -37,7 +37,7 @@ struct GeneralParams {
 };
 
 constexpr int kGeneralBlock = 256;
-constexpr int kGeneralMaxN = 16384;  // 128 KiB of LDS for one segment
+// (kGeneralMaxN = 16 384, 128 KiB of LDS for one segment: rt_core.h)
 // (Measured and dropped early in round 5, while the accesses at bit-reversed places still bounded these kernels: workgroups of 1 024
 // threads beyond nperseg 1024 and W_(2 h)^k as the square of W_(4 h)^k instead of a second table load -- nperseg 8192 72 k -> 45 k
 // MS/s, 128 150 k -> 128 k, only 16 384 gained, 50 k -> 55 k.  With those accesses gone, 512 / 1 024 threads are what stft_big and the
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kGeneralBlock) void stft_general(const GeneralParam
 // algorithm on the same LDS transform.  With w[n] = exp(-i pi n^2 / N),
 //     X[k] = w[k] * sum_n (x[n] w[n]) conj(w[k - n]),
 // a circular convolution of length M = the power of two >= 2 N - 1 with a fixed filter: A = FFT_M(x w, zero-padded),
-// C = A * B (B = FFT_M of the filter, made on the host in double precision, 1 / M folded in), c = IFFT_M(C) = conj(FFT_M(conj(C))),
+// C = A * B (B = FFT_M of the filter, made on the host in double precision, 1 / M folded in: rt_tables.h, bluestein_tables), c = IFFT_M(C) = conj(FFT_M(conj(C))),
 // X[k] = w[k] c[k] -- and since |w[k]| = 1 the power is |FFT_M(conj(C))[k]|^2 for k < N.  Detrend and window are folded into the
 // first multiplication: the table `cwin` holds window[n] * sqrt(scale) * w[n].  One segment per workgroup, M complex values
 // of LDS (up to 128 KiB).  Two transforms of length M >= 2 N per segment and float32 throughout: the round-off of the strongest

@@ -1,16 +1,19 @@
-// rt_hostcheck.cpp -- HOST build of the scalar decision logic in rt_core.h, for
-// unit tests only (tests/test_host_core.py).  It lets the CPU test-suite drive
-// the exact functions the detect kernels execute (predicate, start walk,
-// float64 duration gate, statistics, microsecond rounding, ordering + shadow
-// verdict) against the oracle and the golden vectors without a GPU.
+// rt_hostcheck.cpp -- HOST build of the scalar decision logic in rt_core.h and of
+// the table builders in rt_tables.h, for unit tests only (tests/test_host_core.py,
+// tests/test_host_tables.py).  It lets the CPU test-suite drive the exact functions
+// the detect kernels execute (predicate, start walk, float64 duration gate,
+// statistics, microsecond rounding, ordering + shadow verdict) against the oracle
+// and the golden vectors, and read the geometry and the tables a handle hands its
+// kernels, without a GPU.
 // It is NOT a fallback: the product library (rt_analyze.hip) never links or
-// loads this file, and there is no FFT/STFT here at all.
+// loads this file, and there is no STFT here at all.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../include/rt_analyze.h"
 #include "rt_core.h"
+#include "rt_tables.h"
 
 using namespace rt;
 
@@ -22,10 +25,7 @@ int hc_probe_stride(int nperseg, double fs, double min_d) { return probe_stride(
 
 double hc_seg_time(int k, int nperseg, double fs) { return seg_time(k, nperseg, fs); }
 
-int hc_tail_cols(int nperseg, double fs, double max_d) {
-    const double hop = seg_time(1, nperseg, fs) - seg_time(0, nperseg, fs);
-    return (int)(max_d / hop) + 2;
-}
+int hc_tail_cols(int nperseg, double fs, double max_d) { return tail_cols(nperseg, fs, max_d); }
 
 // extract_signals + filter_shadow_signals for ONE stream on a dense,
 // segment-major power map: spec[t*F + f].  last = previous map
@@ -218,4 +218,69 @@ long long hc_record_cells_f64(const double *spec, int n_bins, const double *last
                               long long *offsets, double *cells, long long cap) {
     return record_cells_host(spec, n_bins, last, n_seg_last, rec, n, offsets, cells, cap);
 }
+}  // extern "C"
+
+// The geometry and the tables of a handle (rt_core.h, rt_tables.h): thin wrappers, the functions rt_create[_f64] call.
+extern "C" {
+
+// out[6]: R3, QS, big, general, bluestein, supported
+void hc_scan_family(int nperseg, int *out) {
+    const ScanFamily f = scan_family(nperseg);
+    const int v[6] = {f.R3, f.QS, f.big, f.general, f.bluestein, f.supported};
+    std::memcpy(out, v, sizeof v);
+}
+// `block`: threads of a scan workgroup (the product passes rt_kernels.h: scan_block(R3))
+int hc_choose_chunk(int nperseg, int block, double fs, double min_d, int segs_per_chunk, int n_streams, int n_seg) {
+    const ScanFamily f = scan_family(nperseg);
+    return choose_chunk(nperseg, f.R3, f.QS, block, fs, min_d, segs_per_chunk, n_streams, n_seg);
+}
+long long hc_min_run_cells(int nperseg, double fs, double min_d) { return min_run_cells(nperseg, fs, min_d); }
+int hc_key_tbits(int n_seg) { return key_tbits(n_seg); }
+int hc_next_pow2(int v) { return next_pow2(v); }
+
+// n[2]: entries of tw1 / tw2; the tables are copied where the pointers are not null
+void hc_scan_twiddles(int N, int R3, int QS, int big, int wave64, cf *tw1, cf *tw2, int *n) {
+    const ScanTwiddles t = scan_twiddles(N, R3, QS, big, wave64 != 0);
+    n[0] = (int)t.tw1.size();
+    n[1] = (int)t.tw2.size();
+    if (tw1) std::memcpy(tw1, t.tw1.data(), t.tw1.size() * sizeof(cf));
+    if (tw2) std::memcpy(tw2, t.tw2.data(), t.tw2.size() * sizeof(cf));
+}
+void hc_scaled_window(const float *window, int N, float scale, float *ws) {
+    const std::vector<float> v = scaled_window(window, N, scale);
+    std::memcpy(ws, v.data(), v.size() * sizeof(float));
+}
+void hc_window_thread_order(const float *ws, int N, int big, float *out) {
+    const std::vector<float> v = window_thread_order(std::vector<float>(ws, ws + N), N, big);
+    std::memcpy(out, v.data(), v.size() * sizeof(float));
+}
+void hc_window_lane_order(const float *ws, int N, int LG, int wave64, float *out) {
+    const std::vector<float> v = window_lane_order(std::vector<float>(ws, ws + N), N, LG, wave64 != 0);
+    std::memcpy(out, v.data(), v.size() * sizeof(float));
+}
+int hc_fit_cosine_window(const float *ws, int N, double *wr, double *wi) {
+    const CosineFit f = fit_cosine_window(std::vector<float>(ws, ws + N), N);
+    std::memcpy(wr, f.wr, sizeof f.wr);
+    std::memcpy(wi, f.wi, sizeof f.wi);
+    return f.cosine_sum ? 1 : 0;
+}
+void hc_transform_twiddles_f32(int M, cf *out) {
+    const std::vector<cf> v = transform_twiddles<cf, double>(M);
+    std::memcpy(out, v.data(), v.size() * sizeof(cf));
+}
+void hc_transform_twiddles_f64(int M, cd *out) {
+    const std::vector<cd> v = transform_twiddles<cd, long double>(M);
+    std::memcpy(out, v.data(), v.size() * sizeof(cd));
+}
+void hc_bluestein_tables_f32(const float *window, int N, int M, int log2m, float scale, cf *cwin, cf *bfilt) {
+    const BluesteinTables<cf> t = bluestein_tables<cf, double>(window, N, M, log2m, std::sqrt((double)scale));
+    std::memcpy(cwin, t.cwin.data(), t.cwin.size() * sizeof(cf));
+    std::memcpy(bfilt, t.bfilt.data(), t.bfilt.size() * sizeof(cf));
+}
+void hc_bluestein_tables_f64(const double *window, int N, int M, int log2m, cd *cwin, cd *bfilt) {
+    const BluesteinTables<cd> t = bluestein_tables<cd, long double>(window, N, M, log2m, 1.0L);
+    std::memcpy(cwin, t.cwin.data(), t.cwin.size() * sizeof(cd));
+    std::memcpy(bfilt, t.bfilt.data(), t.bfilt.size() * sizeof(cd));
+}
+
 }  // extern "C"

@@ -51,6 +51,8 @@ struct StftParams {
     int32_t chunks;          // ceil(T / L) chunks per stream
     int32_t blocks_per_stream;
     int32_t tail_cols;       // K
+    // (the five tables below are built on the host in rt_tables.h -- scaled_window, window_lane_order / window_thread_order, scan_twiddles --
+    // and checked entry by entry by the CPU suite, tests/test_host_tables.py)
     const float *window;     // [N] window coefficients times sqrt(scale)
     const float *window_t;   // nperseg 4096: the same in the order the lanes read it.  stft_scan64: [n0][jq][lane][e] = window[lane + 64 m],
                              // m = n0 + 4 (4 jq + e) (16-byte pieces of the quarter n0 of a lane's 64 elements); stft_scan<16>: [lane][m] = window[lane + 256 m]
@@ -308,12 +310,12 @@ __device__ __forceinline__ cf group_sum(cf v, cf *red /* [kBlock/64] LDS */) {
 // ds_read_b128 of both exchanges is conflict-free; the plain [row][column] layout was 2-way conflicted on every store).
 //   exchange 1: element (a = b + R3*c, k1) goes to row k1*R3 + b, physical column (c + s1(b)) & 15 with
 //               s1(b) = (16/R3 - 2) * b.  The reader takes the row as it lies: a sequence rotated by s is a phase
-//               W16^(s*q1) on its transform, and that phase is folded into the pass-2 twiddle table (host side).
+//               W16^(s*q1) on its transform, and that phase is folded into the pass-2 twiddle table (rt_tables.h: scan_twiddles).
 //   exchange 2: the R3-wide column groups u of the rows of one k1 are rotated by sh(k1) = (k1*R3/8) mod (16/R3);
 //               pass 3 transforms inside the groups, so the rotation only renumbers its output registers (bin_of).
 template <int R3>
 __device__ __forceinline__ int x1_rotation(int b) {
-    return ((16 / R3 - 2) * b) & 15;
+    return x1_rotation(R3, b);  // (rt_core.h: one definition for the kernel and the host's pass-2 twiddles)
 }
 template <int R3>
 __device__ __forceinline__ int x2_rotation(int k1) {
@@ -532,7 +534,7 @@ __host__ __device__ constexpr int scan_block(int R3) { return R3 <= RT_ONE_WAVE_
 // order <= 1 (hamming, hann, boxcar -- anything get_window() makes of them) W is real and zero outside bins 0 and +-1,
 // so "subtract the mean from every sample" (32 subtractions per lane and step, and the transform waiting for the
 // group-wide sum) becomes "subtract sum * W[k]/N from three output bins" (six fused multiply-adds, after pass 3).
-// The host picks LIN when the window qualifies (rt_create); other windows keep the subtract-first form.
+// The host picks LIN when the window qualifies (rt_tables.h: fit_cosine_window); other windows keep the subtract-first form.
 // Experiment (diagnostic builds, -DRT_EXP_DMA1024=1; round 6, the round-5 review's item 8): the complex64 kernels of nperseg 1024 take the
 // next segment through an LDS landing zone of 8 KiB per wave (eight `buffer_load_dwordx4 ... lds` instead of sixteen register loads, issued
 // as soon as the step's samples are out of the zone -- a whole transform ahead), at TWO workgroups per CU (the zones do not fit three
