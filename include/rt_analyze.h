@@ -443,6 +443,35 @@ int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const doubl
 int rt_set_stream_settings_f64(rt_handle *h, const double *snr_threshold, const double *min_duration_s,
                                const double *max_duration_s);  /* float64 handle */
 
+/*
+ * ---- streams that sit out a call (additive within ABI version 6) ----
+ * In the reference every SDR is a SignalAnalyzer of its own: its callback comes when ITS radio delivers, and its
+ * `_spectrogram_last` (analyze.py:268) is the buffer that radio delivered before, whatever the other radios did meanwhile.
+ * `present` is a HOST array of n_streams bytes, non-zero = the stream takes part; NULL = every stream.
+ *   - sticky: it applies to every rt_process* call enqueued afterwards, on float32 and float64 handles alike; with cfg.lanes > 1
+ *     every lane takes its slice.  It may be called while calls are pending: each call keeps the mask it was enqueued with, and
+ *     every re-analysis of that call inside rt_fetch* (AUTO's level-up, the partial dense re-run, stale thresholds, growth of the
+ *     record pool, the record capacity or the cell pool, the detrend guard) uses that snapshot.
+ *   - rt_extract*, rt_spectrogram* and rt_calibrate_read ignore the mask.
+ *   - a handle on which the entry was never called launches exactly what it launched before: no kernel, copy or allocation is
+ *     added and no kernel argument changes meaning.  The first call allocates the mask rows (RT_E_NOMEM if that fails).
+ * A stream that is ABSENT from a call:
+ *   - no effect from its row: its row of the IQ buffer is not read and has no effect on anything -- no records, no candidate
+ *     cells, no contribution to rt_call_info, to AUTO's level decisions, to the overflow or inconsistency marks or to the
+ *     detrend guard;
+ *   - state as if no call happened: its next present buffer is analysed exactly as by a reference analyzer that was not called
+ *     in between -- it looks back into its own last present buffer, and `start_min` (analyze.py:383) comes from THAT buffer's
+ *     segment count, not from the handle's latest call.  After any number of absent calls;
+ *   - deferred changes: a pending rt_reset_stream, or the restart a changed threshold or setting brings, takes effect at its
+ *     next present call;
+ *   - row means (RT_FLAG_ROW_MEANS): its [nperseg] entries for that call are NaN, as at T == 0;
+ *   - record cells (RT_FLAG_RECORD_CELLS): it has no records, hence no cells;
+ *   - whole-call errors stay: a call in which every stream is absent is legal (RT_OK, zero records), and what concerns the call
+ *     as a whole is unchanged -- RT_E_ONE_SEGMENT, the alignment of the pointer, max_samples.
+ * RT_E_INVALID: null handle.
+ */
+int rt_set_present(rt_handle *h, const uint8_t *present);
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

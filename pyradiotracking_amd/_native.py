@@ -159,6 +159,7 @@ ABI_SYMBOLS = (
     "rt_fetch_record_cells_f64",
     "rt_set_stream_settings",
     "rt_set_stream_settings_f64",
+    "rt_set_present",
 )
 
 _lib = None
@@ -227,6 +228,7 @@ def load_library(path: Optional[str] = None):
     lib.rt_fetch_record_cells_f64.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
     lib.rt_set_stream_settings.argtypes = [vp, vp, vp, vp]
     lib.rt_set_stream_settings_f64.argtypes = [vp, vp, vp, vp]
+    lib.rt_set_present.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -437,6 +439,18 @@ class NativeAnalyzer:
         lo, hi = arr(min_duration_s, np.float64), arr(max_duration_s, np.float64)
         fn = self._lib.rt_set_stream_settings_f64 if self.f64 else self._lib.rt_set_stream_settings
         self._check(fn(self._handle, *(a.ctypes.data if a is not None else None for a in (s, lo, hi))))
+
+    def set_present(self, present: Optional[np.ndarray]):
+        """``rt_set_present``: one flag per stream (non-zero = the stream takes part in the calls enqueued from now on), or None =
+        every stream.  A stream that sits a call out keeps its look-back, its pending reset and its previous segment count for
+        its next present buffer; may be called with calls pending."""
+        if present is None:
+            self._check(self._lib.rt_set_present(self._handle, None))
+            return
+        m = np.ascontiguousarray(np.asarray(present).astype(bool), dtype=np.uint8)
+        if m.shape != (self.n_streams,):
+            raise ValueError(f"expected {self.n_streams} flags")
+        self._check(self._lib.rt_set_present(self._handle, m.ctypes.data))
 
     # -- analysis ---------------------------------------------------------
     def process_device(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):

@@ -385,6 +385,8 @@ class BatchSignalAnalyzer:
             lanes = 1 if (hip_stream is not None or f64) else default_lanes(fft_nperseg, len(self.devices))
         if int(lanes) > 1 and hip_stream is not None:
             raise ValueError("lanes > 1 run on their own HIP streams: pass hip_stream=None")
+        self._present = None       # the presence mask in force (set_present): None = every stream ...
+        self._present_set = False  # ... and whether the native entry has been called at all
         self._native = _native.NativeAnalyzer(
             n_streams=len(self.devices),
             nperseg=fft_nperseg,
@@ -452,6 +454,29 @@ class BatchSignalAnalyzer:
         """``_spectrogram_last = None`` for one stream: its SDR was restarted, i.e. the reference would have
         replaced its analyzer by a fresh one (``__main__.py:185-190``)."""
         self._native.reset_stream(stream)
+
+    def set_present(self, present=None):
+        """Which streams take part in the buffers enqueued from now on (``rt_set_present``): one bool per device, or ``None`` =
+        all of them.  In the reference every SDR is a ``SignalAnalyzer`` of its own, whose callback comes when *its* radio
+        delivers; a stream that is absent from a call is not read, finds nothing and keeps its state -- its next present buffer
+        looks back into its own last present one, exactly as a reference analyzer that was not called in between, after any
+        number of absent calls; a pending :meth:`reset_stream` or changed setting takes effect then.  Sticky; may be called
+        with buffers in flight (each keeps the mask it was enqueued with); returns at once when the mask equals the one in
+        force.  An all-true mask on an analyzer that never had another one is such a case: the native entry is not called and the
+        handle stays on its one-count path (``native.set_present`` calls it regardless).  ``extract_signals`` and the spectrogram
+        entries ignore it."""
+        n = len(self.devices)
+        if present is not None:
+            present = tuple(bool(p) for p in present)
+            if len(present) != n:
+                raise ValueError(f"present {list(present)} does not match devices {list(self.devices)}.")
+            if all(present) and not self._present_set:
+                return  # (never masked, and every stream stays: the handle is left on its one-count path)
+        if self._present_set and present == self._present:
+            return
+        self._native.set_present(None if present is None else np.array(present, dtype=bool))
+        self._present = present
+        self._present_set = True
 
     def _push_stream_settings(self):
         """The per-stream attributes -> ``rt_set_stream_settings`` (scalars stay the handle's own: null arrays).  The SNR
@@ -649,7 +674,8 @@ class BatchSignalAnalyzer:
     def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
         """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
         reference's noise figure (analyze.py:373-375) -- over the buffer of the call :meth:`fetch_records` (or
-        :meth:`process_batch`) returned last, bins in fftfreq order; NaN for a buffer shorter than ``fft_nperseg``.  A record's
+        :meth:`process_batch`) returned last, bins in fftfreq order; NaN for a buffer shorter than ``fft_nperseg`` and for the rows
+        of a stream that sat the call out (:meth:`set_present`).  A record's
         ``row_mean`` equals its bin's entry bit for bit.  ``dbw=True``: in dBW as ``Signal.noise`` (uncalibrated, analyze.py:446).
         Needs ``row_means=True``; raises ``NativeError`` (``RT_E_INVALID``) once another buffer was enqueued or the analyzer
         reset, and after an ``extract_signals`` call."""

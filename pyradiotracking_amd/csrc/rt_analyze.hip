@@ -32,6 +32,7 @@
 #include "rt_general.h"
 #include "rt_f64.h"
 #include "rt_cells.h"
+#include "rt_present.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -86,6 +87,7 @@ struct CallCtx {
     bool ran_lin = false;     // its scans detrended by linearity (fetch_one: analysed again if the guard marks a stream)
     uint64_t sub_epoch = 0;   // rt_handle::sub_epoch when its kernels were enqueued
     int cells_grown = 0;      // times the slot's cell pool was enlarged for this call and the call analysed again (RT_FLAG_RECORD_CELLS)
+    bool masked = false;      // enqueued on a handle with a presence mask (rt_set_present): the slot's `pc` and mask arrays are this call's
     // handle state before this call (restored when the call is rolled back: a later lane failed to enqueue)
     int prev_tail_cur = 0, prev_n_seg_last = -1, prev_dense_sticky = 0, prev_minsum_slot = -1;
 };
@@ -132,8 +134,23 @@ struct Slot {
     uint32_t *d_hot_kept = nullptr;                            // [S][kBuckets] the candidate counters as they were in front of finalize_records
     long long *d_stream_cells = nullptr, *d_stream_base = nullptr;  // [S] cells of each stream's records / its first cell in the pool
     unsigned long long *h_cells_info = nullptr;                // pinned: [0] cells the call wants, [1] a record's cells were not all found
+    // rt_set_present only (allocated by the handle's first call of the entry).  The snapshot a call was enqueued with -- every
+    // analysis of the call inside rt_fetch uses it again -- and its device form, kMaskRows rows of [S] (pinned copy beside it):
+    PresenceCall pc;
+    int32_t *h_mask = nullptr, *d_mask = nullptr;
+    int n_lin_present = 0, n_sub_present = 0, n_absent = 0;  // entries of the rows kMaskLinList / kMaskSubList / kMaskAbsentList
     hipEvent_t ev_begin = nullptr, ev_first = nullptr, ev_scan = nullptr, ev_done = nullptr;  // first launch; end of the first scan; end of the scans; end of the call
     CallCtx call;
+};
+// rows of Slot::d_mask
+enum : int {
+    kMaskAbsent = 0,      // non-zero: the stream sits the call out (DetectArgs::absent and its like)
+    kMaskLinList = 1,     // the present streams the detrend guard has not marked, ascending (StftParams::stream_list of the LIN scan)
+    kMaskList = 2,        // the present streams, ascending (StftParams::stream_list of the other scans)
+    kMaskSubList = 3,     // the present ones among the marked streams (the subtract-first launch behind a LIN scan)
+    kMaskNSegLast = 4,    // columns of each stream's own previous buffer (DetectArgs::n_seg_last_s)
+    kMaskAbsentList = 5,  // the absent streams (carry_tails)
+    kMaskRows = 6
 };
 
 // A float64 handle (rt_create_f64; kernels: rt_f64.h).  Its own two call slots, three look-back tails in rotation as on the
@@ -164,6 +181,11 @@ struct F64Slot {
     int64_t cell_cap = 0;
     long long *d_stream_cells = nullptr, *d_stream_base = nullptr;
     unsigned long long *h_cells_info = nullptr;
+    // rt_set_present only, as in Slot (rows kMaskAbsent, kMaskNSegLast and kMaskAbsentList are used)
+    PresenceCall pc;
+    bool masked = false;
+    int32_t *h_mask = nullptr, *d_mask = nullptr;
+    int n_absent = 0;
     hipEvent_t ev_done = nullptr;
 };
 struct F64State {
@@ -187,6 +209,7 @@ struct F64State {
     int rm_slot = -1;  // the slot of the call rt_fetch_f64 delivered last, while its row means are valid (kRowMeansNone / kRowMeansExtract)
     bool cells_full = false;  // ... and that call was delivered in full (rt_fetch_record_cells_f64)
     int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
+    PresenceBook pres;        // rt_set_present: per-stream segment counts and the mask in force (inactive until the entry is called)
 };
 
 }  // namespace
@@ -289,6 +312,11 @@ struct rt_handle {
     int rm_slot = -1;
     bool cells_full = false;  // RT_FLAG_RECORD_CELLS: ... and that call was delivered in full: its cells can be fetched (rt_fetch_record_cells)
     int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
+
+    // rt_set_present (rt_core.h: PresenceBook): inactive -- and nothing below used -- until the entry is called
+    PresenceBook pres;
+    size_t chunk_min_bytes = 0;         // bytes of a slot's d_chunk_min (0: none)
+    const Slot *launch_mask = nullptr;  // while a masked call's kernels are being enqueued: the slot whose mask rows its scans take (launch_stft)
 
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
 };
@@ -414,6 +442,41 @@ void launch_stft_lin(rt_handle *h, const StftParams &p, int items, hipStream_t s
 template <int MODE, int FMT = kFmtC64>
 void launch_stft(rt_handle *h, const StftParams &p, int blocks, hipStream_t st) {
     constexpr bool U8 = (FMT == kFmtU8);
+    // A call with a presence mask (rt_set_present; not a launch over a list of its own): absent streams are left alone by what the
+    // kernels have for that already, StftParams::stream_list: every scan runs over a list of present streams, so that neither a
+    // launch nor its time grows with the absent ones -- the LIN scan over the present streams its guard has not marked, the
+    // subtract-first launch behind it over the marked ones that are present, every other scan over all present streams.  A launch
+    // holds no item of an absent stream, so no load and no store of any kind happens for it.  (Leaving the absent streams to
+    // StftParams::sub_first in a launch over all streams was measured first: their items end at once, but only behind the
+    // workgroup's tables -- profiles/present_bench_sub_first_variant.jsonl)
+    const Slot *const mk = (MODE != 3 && !p.stream_list) ? h->launch_mask : nullptr;
+    if (mk) {
+        const int S = h->cfg.n_streams;
+        const int n_present = mk->pc.n_present;
+        if (n_present == 0) return;
+        StftParams q = p;
+        if (h->lin && !U8) {
+            if (mk->n_lin_present > 0) {
+                q.sub_first = nullptr;
+                q.stream_list = mk->d_mask + (size_t)kMaskLinList * S;
+                q.n_streams = mk->n_lin_present;
+                q.spec_by_stream = 1;
+                launch_stft_lin<MODE, FMT, (MODE != 3 && !U8)>(h, q, q.n_streams * p.blocks_per_stream, st);
+            }
+            if (mk->n_sub_present == 0) return;
+            q = p;
+            q.stream_list = mk->d_mask + (size_t)kMaskSubList * S;
+            q.n_streams = mk->n_sub_present;
+        } else {
+            q.stream_list = mk->d_mask + (size_t)kMaskList * S;
+            q.n_streams = n_present;
+        }
+        q.sub_first = nullptr;
+        q.dc_flag = h->lin && !U8 ? nullptr : p.dc_flag;
+        q.spec_by_stream = 1;
+        launch_stft_lin<MODE, FMT, false>(h, q, q.n_streams * p.blocks_per_stream, st);
+        return;
+    }
     if (h->lin && MODE != 3 && !U8) {
         if (p.stream_list || h->n_sub == 0 || !p.sub_first) {
             // (a launch over a list of its own -- AUTO's dense re-run of a few streams -- keeps the linearity form for all of them: its
@@ -440,9 +503,10 @@ void launch_stft(rt_handle *h, const StftParams &p, int blocks, hipStream_t st) 
 
 // the general transform (rt_general.h): the dense spectrogram of an nperseg the fused scans do not cover (the caller runs
 // row_sums_dense over the map)
-void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_seg, float *spec, float *tail, int fmt) {
+void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_seg, float *spec, float *tail, int fmt, const int32_t *absent = nullptr) {
     if (h->bluestein) {
         BluesteinParams b{};
+        b.absent = absent;
         b.iq = iq;
         b.stream_stride = stream_stride;
         b.n_streams = h->cfg.n_streams;
@@ -477,6 +541,7 @@ void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_s
         return;
     }
     GeneralParams g{};
+    g.absent = absent;
     g.iq = iq;
     g.stream_stride = stream_stride;
     g.n_streams = h->cfg.n_streams;
@@ -599,6 +664,10 @@ DetectArgs make_detect_args(rt_handle *h, Slot &sl, int n_seg, int n_bins, int n
     a.cal_s = h->d_cal_s;
     a.set_s = h->d_set_s;
     a.no_last = sl.call.no_last ? sl.h_no_last : nullptr;
+    if (sl.call.masked) {  // rt_set_present: each stream's own previous segment count (a reset taken: -1), and who sits the call out
+        a.absent = sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams;
+        a.n_seg_last_s = sl.d_mask + (size_t)kMaskNSegLast * h->cfg.n_streams;
+    }
     a.stream_overflow = sl.h_overflow;
     a.stream_incons = sl.h_incons;
     return a;
@@ -622,7 +691,7 @@ int enqueue_row_means(rt_handle *h, Slot &sl, int chunks, int n_seg, hipStream_t
     if (!sl.d_row_means) return RT_OK;
     const int64_t cells = (int64_t)h->cfg.n_streams * h->N;
     hipLaunchKernelGGL(row_means_from_partials, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, sl.d_psum, chunks, h->cfg.n_streams, h->N,
-                       n_seg, sl.d_row_means);
+                       n_seg, sl.d_row_means, sl.call.masked ? sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams : nullptr);
     RT_HIP(h, hipGetLastError());
     return RT_OK;
 }
@@ -726,6 +795,52 @@ void launch_scan(rt_handle *h, const StftParams &sp, int blocks, int fmt, hipStr
     else launch_stft<MODE>(h, sp, blocks, st);
 }
 
+// ---- rt_set_present: a call's mask rows and the carry of the absent streams' look-back columns ----
+// The scans enqueued while one of these is alive take the slot's mask (launch_stft)
+struct MaskedLaunches {
+    rt_handle *h;
+    MaskedLaunches(rt_handle *h_, const Slot &sl) : h(h_) { h->launch_mask = sl.call.masked ? &sl : nullptr; }
+    ~MaskedLaunches() { h->launch_mask = nullptr; }
+};
+
+// the rows of kMask* from a call's snapshot; `sub_first` (or null): the streams the detrend guard has marked.  Returns the entries
+// of the rows kMaskLinList / kMaskSubList / kMaskAbsentList.
+void fill_mask_rows(const PresenceCall &pc, int S, const int32_t *sub_first, int32_t *rows, int *n_lin_present, int *n_sub_present, int *n_absent) {
+    int n_list = 0, n_lin = 0, n_sub = 0, n_abs = 0;
+    for (int s = 0; s < S; ++s) {
+        const bool gone = pc.absent[(size_t)s] != 0, marked = sub_first && sub_first[s] != 0;
+        rows[(size_t)kMaskAbsent * S + s] = gone ? 1 : 0;
+        rows[(size_t)kMaskNSegLast * S + s] = pc.n_seg_last[(size_t)s];
+        if (gone) rows[(size_t)kMaskAbsentList * S + n_abs++] = s;
+        else rows[(size_t)kMaskList * S + n_list++] = s;
+        if (!gone && marked) rows[(size_t)kMaskSubList * S + n_sub++] = s;
+        if (!gone && !marked) rows[(size_t)kMaskLinList * S + n_lin++] = s;
+    }
+    *n_lin_present = n_lin;
+    *n_sub_present = n_sub;
+    *n_absent = n_abs;
+}
+
+// (again when the detrend guard's set has changed: fetch_one).  Nothing of the slot is in flight: the pinned rows may be rewritten.
+int upload_mask(rt_handle *h, Slot &sl) {
+    const int S = h->cfg.n_streams;
+    fill_mask_rows(sl.pc, S, h->lin ? h->h_sub_first.data() : nullptr, sl.h_mask, &sl.n_lin_present, &sl.n_sub_present, &sl.n_absent);
+    RT_HIP(h, hipMemcpyAsync(sl.d_mask, sl.h_mask, (size_t)kMaskRows * S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
+    return RT_OK;
+}
+
+// The absent streams' K look-back columns from the rotation buffer the call reads to the one it writes, on the scan's stream, where
+// the scan's own tail stores are (rt_present.h).  Once per call: a re-analysis finds them in place.
+template <class P>
+int enqueue_carry(rt_handle *h, const int32_t *d_absent_list, int n_absent, const P *src, P *dst, int K, int N) {
+    const int64_t per = (int64_t)K * N;  // (K >= 1: rt_core.h tail_cols; N >= 8: rt_create)
+    if (n_absent == 0 || per <= 0) return RT_OK;
+    const int bps = carry_blocks(per);
+    hipLaunchKernelGGL((carry_tails<P>), dim3((unsigned)((int64_t)n_absent * bps)), dim3(kCarryBlock), 0, h->s_scan, d_absent_list, n_absent, bps, src, dst, per);
+    RT_HIP(h, hipGetLastError());
+    return RT_OK;
+}
+
 // enqueue scan + detect + readback for the call described by sl.call, analysed the way `mode` says.
 // `second_pass_only`: RT_MODE_PREFILTER for a call whose RT_MODE_SPARSE attempt has just overflowed -- that scan
 // wrote the chunk bits, row sums and tail columns already, only the selective pass and the detection are repeated.
@@ -740,13 +855,15 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
     // mean NaN, so every positive threshold fails; thousands of NaN records: the record room grows behind the re-run).
     if (mode == RT_MODE_RUNFILTER && c.thr_rerun && !second_pass_only) own_means = true;
     if (launched) *launched = false;
+    const MaskedLaunches masked_launches(h, sl);
+    const int32_t *const absent = c.masked ? sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams : nullptr;
     if (h->general) {
         // any other power-of-two nperseg: the general transform into the dense map, then the dense extractor (which sums the rows itself)
         int rc = ensure_dense_spec(h);
         if (rc != RT_OK) return rc;
         RT_HIP(h, hipEventRecord(sl.ev_begin, h->s_scan));
         if (launched) *launched = true;
-        launch_general(h, c.iq, c.stream_stride, c.n_seg, h->d_spec, h->d_tail[c.tail_write], c.fmt);
+        launch_general(h, c.iq, c.stream_stride, c.n_seg, h->d_spec, h->d_tail[c.tail_write], c.fmt, absent);
         {
             const int64_t cells = (int64_t)h->cfg.n_streams * h->N;
             hipLaunchKernelGGL(row_sums_dense, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->s_scan, h->d_spec, sl.d_psum, h->cfg.n_streams, c.n_seg, h->N);
@@ -866,7 +983,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
             const int64_t cells = (int64_t)S * h->N;
             hipLaunchKernelGGL(after_bit_scan, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s2, sl.d_abs_hot, sl.h_abs_hot, sl.d_thr_nat, sl.d_psum, S, h->N,
                                sp.blocks_per_stream, c.n_seg, h->cfg.snr_threshold, h->d_set_s, sl.h_overflow, sl.d_counters, kFlagHotOverflow | kFlagThrStale,
-                               const_cast<int32_t *>(sp.seg_count));
+                               const_cast<int32_t *>(sp.seg_count), absent);
         }
         sl.call.abs_counted = true;
         {
@@ -878,7 +995,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
             const size_t plan_lds = ((size_t)tpw * tile + 3) & ~(size_t)3;
             auto *kern = r <= 16 ? plan_runs<4> : r <= 256 ? plan_runs<8> : plan_runs<16>;
             hipLaunchKernelGGL(kern, dim3(S, waves), dim3(64), plan_lds, s2, sp.cell_hot, sl.d_cell_need,
-                               sl.d_seg_list, const_cast<int32_t *>(sp.seg_count), c.n_seg, h->LG, r, tile);
+                               sl.d_seg_list, const_cast<int32_t *>(sp.seg_count), c.n_seg, h->LG, r, tile, absent);
         }
         launch_scan<7>(h, sp, blocks, c.fmt, s2);
     } else if (mode == RT_MODE_PREFILTER) {
@@ -893,7 +1010,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
             sl.call.abs_counted = true;
         }
         hipLaunchKernelGGL(plan_pass_b, dim3(S), dim3(256), sizeof(uint32_t) * ((sp.chunks + 31) / 32), s2, sp.full, sp.first,
-                           sp.item_chunks, sp.item_count, h->LG, sp.segs_per_chunk, c.n_seg, sp.chunks, sp.blocks_per_stream, h->GPW);
+                           sp.item_chunks, sp.item_count, h->LG, sp.segs_per_chunk, c.n_seg, sp.chunks, sp.blocks_per_stream, h->GPW, absent);
         launch_scan<5>(h, sp, blocks, c.fmt, s2);
     } else {
 #ifdef RT_STAMPS  // diagnostic build: per-stage cycle sums of every wave of the sparse scan, averaged and printed (stderr)
@@ -1127,6 +1244,10 @@ void rollback_newest(rt_handle *h) {
                 if (best->h_no_last[s]) h->reset_pending[(size_t)s] = 1;
             h->any_reset_pending = true;
         }
+        if (c.masked) {
+            h->pres.rollback(best->pc, h->reset_pending);
+            h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
+        }
     }
     best->call = CallCtx{};
     h->n_calls--;
@@ -1325,6 +1446,8 @@ void rt_destroy(rt_handle *h) {
         (void)hipHostFree(sl.h_rec_count);
         (void)hipHostFree(sl.h_records);
         (void)hipHostFree(sl.h_no_last);
+        (void)hipHostFree(sl.h_mask);
+        (void)hipFree(sl.d_mask);
         (void)hipHostFree(sl.h_overflow);
         (void)hipHostFree(sl.h_incons);
         (void)hipHostFree(sl.h_dc_flag);
@@ -1637,6 +1760,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
             RT_CREATE_HIP(hipMalloc(&sl.d_cell_hot, cells * sizeof(uint16_t)));
             RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_cell_need, cells * sizeof(uint16_t));  // (all zeros between calls: plan_runs writes only the words that keep anything)
             RT_CREATE_HIP(hipMalloc(&sl.d_chunk_min, std::max<size_t>(psum_bytes, 4)));  // (a row per work item, like psum)
+            h->chunk_min_bytes = std::max<size_t>(psum_bytes, 4);
             RT_CREATE_HIP(hipMalloc(&sl.d_thr_bin, (size_t)S * N * sizeof(float)));
             RT_CREATE_HIP(hipMalloc(&sl.d_thr_nat, (size_t)S * N * sizeof(float)));
             RT_CREATE_HIP(hipMalloc(&sl.d_seg_list, ((size_t)S * std::max(h->max_seg, 1) + S + 1) * sizeof(int32_t)));
@@ -1713,12 +1837,14 @@ int rt_reset(rt_handle *h) {
     forget_row_means(h);
     if (h->f64) {
         h->f64->n_seg_last = -1;
+        if (h->f64->pres.active) h->f64->pres.forget_all();
         std::fill(h->f64->reset_pending.begin(), h->f64->reset_pending.end(), (uint8_t)0);
         h->f64->any_reset = false;
         return RT_OK;
     }
     for (rt_handle *k : h->kids) rt_reset(k);
     h->n_seg_last = -1;
+    if (h->pres.active) h->pres.forget_all();
     std::fill(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)0);
     h->any_reset_pending = false;
     return RT_OK;
@@ -1841,6 +1967,52 @@ int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const doubl
     return set_stream_settings_lane(h, snr_threshold, min_duration_s, max_duration_s);
 }
 
+// rt_set_present (include/rt_analyze.h).  The first call on a handle allocates the two call slots' mask rows and moves the handle
+// to per-stream segment counts (rt_core.h: PresenceBook), every stream starting from the handle's one count; calls already
+// enqueued keep that count.  Later calls only change the mask in force: host memory, no copy, no launch, no synchronisation.
+int rt_set_present(rt_handle *h, const uint8_t *present) {
+    if (!h) return RT_E_INVALID;
+    if (!h->kids.empty())
+        return for_each_lane(h, [&](rt_handle *k, int64_t s0) { return rt_set_present(k, present ? present + s0 : nullptr); });
+    const int S = h->cfg.n_streams;
+    PresenceBook &book = h->f64 ? h->f64->pres : h->pres;
+    if (!book.active) {
+        RT_HIP(h, hipSetDevice(h->cfg.device));
+        const size_t bytes = (size_t)kMaskRows * (size_t)S * sizeof(int32_t);
+        int32_t *hm[kSlots] = {nullptr, nullptr}, *dm[kSlots] = {nullptr, nullptr};
+        bool ok = true;
+        for (int i = 0; i < kSlots && ok; ++i) ok = hipHostMalloc(&hm[i], bytes) == hipSuccess && hipMalloc(&dm[i], bytes) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (int i = 0; i < kSlots; ++i) {
+                (void)hipHostFree(hm[i]);
+                (void)hipFree(dm[i]);
+            }
+            h->err = "rt_set_present: no memory for the mask rows";
+            return RT_E_NOMEM;
+        }
+        for (int i = 0; i < kSlots; ++i) {
+            std::memset(hm[i], 0, bytes);
+            if (h->f64) {
+                h->f64->slot[i].h_mask = hm[i];
+                h->f64->slot[i].d_mask = dm[i];
+            } else {
+                h->slot[i].h_mask = hm[i];
+                h->slot[i].d_mask = dm[i];
+            }
+        }
+        // RT_MODE_RUNFILTER's quiet levels are not carried across a gap: a stream's thresholds behind one come from
+        // whatever rows of chunk minima the slots still hold.  From here on those are minima some scan wrote or "none" (0x7f7f7f7f:
+        // no estimate, the absolute threshold alone), never what the allocation happened to hold.  Behind everything enqueued.
+        if (!h->f64)
+            for (int i = 0; i < kSlots; ++i)
+                if (h->slot[i].d_chunk_min && h->chunk_min_bytes) RT_HIP(h, hipMemsetAsync(h->slot[i].d_chunk_min, 0x7f, h->chunk_min_bytes, h->s_scan));
+        book.activate(S, h->f64 ? h->f64->n_seg_last : h->n_seg_last);
+    }
+    book.set_mask(present);
+    return RT_OK;
+}
+
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, int fmt);
 
 int rt_process(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride) {
@@ -1912,7 +2084,21 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     // held (possibly still unfetched) is put back unless a launch has already rewritten its scratch (include/rt_analyze.h).
     bool launched = false;
     auto enqueue = [&]() -> int {
-        if (h->any_reset_pending) {
+        if (h->pres.active) {
+            // rt_set_present: the call keeps the mask in force, every stream's own previous segment count and the resets it takes in
+            // its slot (absent streams keep theirs pending), and carries the absent streams' look-back columns along the rotation.
+            // (The slot's previous call -- two calls back -- may still be reading the rows if it was never fetched.)
+            if (sl.ev_done && h->n_calls >= (uint64_t)kSlots) RT_HIP(h, hipEventSynchronize(sl.ev_done));
+            launched = true;  // (the slot's snapshot is rewritten from here on)
+            h->pres.begin_call(T, h->tail_cur, h->reset_pending, sl.pc);
+            c.masked = true;
+            h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
+            int rcm = upload_mask(h, sl);
+            if (rcm == RT_OK)
+                rcm = enqueue_carry<float>(h, sl.d_mask + (size_t)kMaskAbsentList * h->cfg.n_streams, sl.n_absent, h->d_tail[c.tail_read], h->d_tail[c.tail_write],
+                                           h->K, h->N);
+            if (rcm != RT_OK) return rcm;
+        } else if (h->any_reset_pending) {
             // the slot's previous call (two calls back) may still be reading its flags if it was never fetched
             if (sl.ev_done && h->n_calls >= (uint64_t)kSlots) RT_HIP(h, hipEventSynchronize(sl.ev_done));
             for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_no_last[s] = h->reset_pending[(size_t)s];
@@ -1962,6 +2148,10 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             for (int s = 0; s < h->cfg.n_streams; ++s)
                 if (sl.h_no_last[s]) h->reset_pending[(size_t)s] = 1;
             h->any_reset_pending = true;
+        }
+        if (c.masked) {
+            h->pres.rollback(sl.pc, h->reset_pending);
+            h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
         }
         if (launched) {
             (void)hipStreamSynchronize(h->s_scan);
@@ -2162,6 +2352,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
             for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
             c.n_dense_streams = 0;
             int rc = before_rerun(h, sl);
+            if (rc == RT_OK && c.masked) rc = upload_mask(h, sl);  // (the marked streams are part of the rows the scans take)
             if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used);  // (takes the current epoch)
             if (rc != RT_OK) return rc;
             // The call enqueued behind this one (at most one is in flight) was analysed under the old set as well, and the next
@@ -2174,6 +2365,13 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
                     continue;
                 RT_HIP(h, hipEventSynchronize(o.ev_done));
                 for (int s = 0; s < h->cfg.n_streams; ++s) o.h_overflow[s] = o.h_incons[s] = o.h_dc_flag[s] = 0;
+                // (its absent streams' look-back columns again as well: the re-run in front of it has rewritten the marked streams' columns
+                // in the buffer they were carried from)
+                if (o.call.masked) rc = upload_mask(h, o);
+                if (rc == RT_OK && o.call.masked)
+                    rc = enqueue_carry<float>(h, o.d_mask + (size_t)kMaskAbsentList * h->cfg.n_streams, o.n_absent, h->d_tail[o.call.tail_read],
+                                              h->d_tail[o.call.tail_write], h->K, h->N);
+                if (rc != RT_OK) return rc;
                 rc = enqueue_analysis(h, o, o.call.mode_used);  // (behind this call's re-run on s_scan; its scratch is its slot's)
                 if (rc != RT_OK) return rc;
             }
@@ -2330,15 +2528,17 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
         for (int s = 0; s < h->cfg.n_streams; ++s) h->info.n_hot += sl.h_hot_total[s];
     // one wave per stream in the next calls' sparse detection while a stream holds half of what such a wave takes on average (heavier
     // batches -- BASELINE config 4: 1 500 cells per stream -- are faster with the per-list waves: most of their streams would be left to them anyway)
-    if (c.mode_used != RT_MODE_DENSE && !c.is_extract && c.n_seg > 0) h->group_light = h->info.n_hot * 2 <= (int64_t)kGroupCells * h->cfg.n_streams;
+    // (a call with a presence mask: the streams that took part -- an absent one adds nothing to either side of these ratios)
+    const int64_t n_took_part = c.masked ? sl.pc.n_present : h->cfg.n_streams;
+    if (c.mode_used != RT_MODE_DENSE && !c.is_extract && c.n_seg > 0) h->group_light = h->info.n_hot * 2 <= (int64_t)kGroupCells * n_took_part;
     // (the exact pre-filter on input where it is not selective: see below)
     bool unselective = h->cfg.mode == RT_MODE_AUTO && c.mode_used == RT_MODE_RUNFILTER && !c.is_extract && c.n_seg > 0 && sl.h_seg_total &&
-                       (int64_t)*sl.h_seg_total * 2 > (int64_t)h->cfg.n_streams * c.n_seg;
+                       (int64_t)*sl.h_seg_total * 2 > n_took_part * c.n_seg;
     // ... or a pre-filter level that went through with more than 1/32 of all cells on its candidate lists (possible where
     // hot_capacity was raised: signals whose side lobes fill every bin put 9 % of the cells there, and ordering lists of
     // 16 k cells per bucket took 14 - 18 ms per call where the dense path takes 1.9)
     if (h->cfg.mode == RT_MODE_AUTO && (c.mode_used == RT_MODE_RUNFILTER || c.mode_used == RT_MODE_PREFILTER) && !c.is_extract && c.n_seg > 0 &&
-        h->info.n_hot * 32 > (int64_t)h->cfg.n_streams * c.n_seg * h->N)
+        h->info.n_hot * 32 > n_took_part * c.n_seg * h->N)
         unselective = true;
     if (c.level_settled) {
         unselective = false;  // (settled on the first pass: the probe interval doubles once per call, not once per pass)
@@ -2807,6 +3007,11 @@ F64DetectArgs f64_detect_args(rt_handle *h, F64Slot &sl) {
         a.dp.n_seg_last = sl.n_seg_last;
         a.dp.tail_cols = sl.n_seg_last < 0 ? 0 : std::min(f->K, sl.n_seg_last);
         a.no_last = sl.no_last ? sl.d_no_last : nullptr;
+        if (sl.masked) {  // rt_set_present: each stream's own previous segment count, and who sits the call out
+            a.absent = sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams;
+            a.n_seg_last_s = sl.d_mask + (size_t)kMaskNSegLast * h->cfg.n_streams;
+            a.tail_k = f->K;
+        }
     }
     a.thr_s = f->d_thr_s;
     a.cal_s = f->d_cal_s;
@@ -2843,6 +3048,7 @@ int f64_enqueue(rt_handle *h, F64Slot &sl) {
         p.tw = f->d_tw;
         p.spec = f->d_map;
         p.tail = f->d_tail[sl.tail_write];
+        p.absent = sl.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr;
         const int64_t grid = (int64_t)S * ((sl.n_seg + f->SPB - 1) / f->SPB);
         const size_t lds = (size_t)f->SPB * f->M * sizeof(cd);
         if (sl.fmt == kFmtU8) {
@@ -2919,6 +3125,8 @@ static void destroy_f64(rt_handle *h) {
         (void)hipFree(sl.d_raw);
         (void)hipFree(sl.d_raw_count);
         (void)hipFree(sl.d_no_last);
+        (void)hipHostFree(sl.h_mask);
+        (void)hipFree(sl.d_mask);
         (void)hipFree(sl.d_stage);
         (void)hipHostFree(sl.h_out);
         (void)hipHostFree(sl.h_meta);
@@ -2984,6 +3192,36 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
         RT_HIP(h, hipMemcpyAsync(sl.d_stage, iq, bytes, hipMemcpyHostToDevice, h->s_scan));
         RT_HIP(h, hipStreamSynchronize(h->s_scan));  // (blocking: the caller may reuse its buffer when this returns)
         sl.iq = sl.d_stage;
+    }
+    sl.masked = f->pres.active;
+    const auto any_pending = [&]() { return std::find(f->reset_pending.begin(), f->reset_pending.end(), (uint8_t)1) != f->reset_pending.end(); };
+    if (sl.masked) {
+        // rt_set_present: as on a float32 handle (process_impl) -- the snapshot into the slot, the rows to the device, the absent
+        // streams' look-back columns carried from the buffer the call reads to the one it writes
+        int n_sub = 0, n_lin = 0;
+        f->pres.begin_call(T, f->tail_cur, f->reset_pending, sl.pc);
+        f->any_reset = any_pending();
+        sl.no_last = false;
+        fill_mask_rows(sl.pc, S, nullptr, sl.h_mask, &n_lin, &n_sub, &sl.n_absent);
+        int rcm = RT_OK;
+        const auto upload = [&]() -> int {
+            RT_HIP(h, hipMemcpyAsync(sl.d_mask, sl.h_mask, (size_t)kMaskRows * S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
+            // (Blocking, like the upload of a pending reset's flags just below: a float64 handle picks any free slot for a call, so
+            // no event of the slot's says when the copy has left the pinned rows.  The float32 path waits for its slot's ev_done.)
+            RT_HIP(h, hipStreamSynchronize(h->s_scan));
+            return enqueue_carry<double>(h, sl.d_mask + (size_t)kMaskAbsentList * S, sl.n_absent, f->d_tail[sl.tail_read], f->d_tail[sl.tail_write], f->K, f->N);
+        };
+        rcm = upload();
+        if (rcm == RT_OK) rcm = f64_start(h, sl);
+        if (rcm != RT_OK) {
+            f->pres.rollback(sl.pc, f->reset_pending);
+            f->any_reset = any_pending();
+            sl.masked = false;
+            return rcm;
+        }
+        f->tail_cur = sl.tail_write;
+        f->n_seg_last = T;
+        return RT_OK;
     }
     sl.no_last = f->any_reset;
     if (f->any_reset) {
@@ -3210,6 +3448,7 @@ int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t 
     sl.ex_last = last_dev;
     sl.ex_last_cols = last_dev ? n_seg_last : 0;
     sl.no_last = false;
+    sl.masked = false;  // (rt_extract_f64 ignores the presence mask)
     return f64_start(h, sl);
 }
 

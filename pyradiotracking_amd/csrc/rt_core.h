@@ -12,7 +12,8 @@
 //   * timedelta microsecond rounding   CPython Modules/_datetimemodule.c
 //                                      (delta_new / accum), used by the shadow
 //                                      filter analyze.py:300-311 (T16)
-// and the geometry a handle derives from its configuration on the host (look-back columns, chunk length, kernel family).
+// and the geometry a handle derives from its configuration on the host (look-back columns, chunk length, kernel family),
+// and the per-stream bookkeeping of a handle whose streams may sit out a call (rt_set_present: PresenceBook).
 #ifndef RT_CORE_H
 #define RT_CORE_H
 
@@ -24,6 +25,7 @@
 #include <initializer_list>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #if defined(__HIP__)  // HIP translation units only (hipcc also compiles the plain C++ ones)
 #define RT_HD __host__ __device__ __forceinline__
@@ -316,6 +318,79 @@ inline int choose_chunk(int nperseg, int R3, int QS, int block, double fs, doubl
     }
     return L;
 }
+
+// ---- Streams that sit out a call (rt_set_present; host side of rt_analyze.hip, here so that the CPU suite can drive it) ----
+// In the reference every SDR is a SignalAnalyzer of its own: `_spectrogram_last` is the buffer ITS radio delivered before, whatever
+// the other radios did meanwhile.  A handle keeps three look-back tails in rotation for all streams in lock-step (call k reads
+// buffer tail_cur and writes the next one), so a stream that is absent from a call has its K columns CARRIED from the buffer the
+// call reads to the one it writes (rt_present.h: carry_tails) -- after any number of absent calls the buffer the next call reads
+// holds the columns of the stream's last present buffer -- and what the rotation cannot carry is kept here, per stream:
+//   * the segment count of the stream's own previous buffer (`start_min`, analyze.py:383: -1 = none);
+//   * its pending reset (rt_reset_stream, a changed threshold or setting): taken by its next PRESENT call;
+//   * per call, in the call's slot, the snapshot every re-analysis of that call inside rt_fetch uses again (PresenceCall).
+constexpr int kTailBuffers = 3;
+struct PresenceCall {
+    int n_present = 0;
+    int tail_read = 0, tail_write = 0;  // the rotation's buffers this call reads / writes (absent streams: carried read -> write)
+    std::vector<uint8_t> absent;        // [S] 1 = the stream sits this call out
+    std::vector<int32_t> n_seg_last;    // [S] present: columns of its own previous buffer as this call sees it (-1: none, or its
+                                        //     reset was taken); absent: what it keeps for its next present call
+    std::vector<int32_t> before;        // [S] the book's count before the call      } put back when the call is rolled back
+    std::vector<uint8_t> took_reset;    // [S] the call consumed the stream's reset  }
+};
+struct PresenceBook {
+    int S = 0;
+    bool active = false;               // rt_set_present has been called on the handle (it then stays on the per-stream path)
+    std::vector<uint8_t> present;      // [S] the mask in force, 1 = present (sticky)
+    std::vector<int32_t> n_seg_last;   // [S] columns of each stream's own latest present buffer, -1: none
+    // first use: every stream inherits the handle's one count (`all` = -1: no buffer yet)
+    void activate(int n_streams, int all) {
+        S = n_streams;
+        active = true;
+        present.assign((size_t)S, (uint8_t)1);
+        n_seg_last.assign((size_t)S, (int32_t)all);
+    }
+    // `mask` = null: every stream.  Returns whether the mask in force changed.
+    bool set_mask(const uint8_t *mask) {
+        bool changed = false;
+        for (int s = 0; s < S; ++s) {
+            const uint8_t v = (!mask || mask[s]) ? 1 : 0;
+            changed = changed || v != present[(size_t)s];
+            present[(size_t)s] = v;
+        }
+        return changed;
+    }
+    void forget_all() { std::fill(n_seg_last.begin(), n_seg_last.end(), (int32_t)-1); }  // rt_reset
+    // A call of T segments is enqueued with the mask in force; `tail_cur` = the rotation's buffer the call before wrote.
+    void begin_call(int T, int tail_cur, std::vector<uint8_t> &reset_pending, PresenceCall &c) {
+        c.n_present = 0;
+        c.tail_read = tail_cur;
+        c.tail_write = (tail_cur + 1) % kTailBuffers;
+        c.absent.assign((size_t)S, (uint8_t)0);
+        c.n_seg_last.assign((size_t)S, (int32_t)-1);
+        c.before = n_seg_last;
+        c.took_reset.assign((size_t)S, (uint8_t)0);
+        for (int s = 0; s < S; ++s) {
+            const size_t i = (size_t)s;
+            if (!present[i]) {
+                c.absent[i] = 1;
+                c.n_seg_last[i] = n_seg_last[i];  // state as if no call happened; a pending reset stays pending
+                continue;
+            }
+            ++c.n_present;
+            c.took_reset[i] = reset_pending[i];
+            c.n_seg_last[i] = reset_pending[i] ? -1 : n_seg_last[i];
+            reset_pending[i] = 0;
+            n_seg_last[i] = T;
+        }
+    }
+    // The newest call is undone (it failed to enqueue, or a later lane did): counts and resets as before it.
+    void rollback(const PresenceCall &c, std::vector<uint8_t> &reset_pending) {
+        n_seg_last = c.before;
+        for (int s = 0; s < S; ++s)
+            if (c.took_reset[(size_t)s]) reset_pending[(size_t)s] = 1;
+    }
+};
 
 // Column rotation of exchange 1 in the fused scans with R3 > 1 (rt_kernels.h: "Exchange layouts"): s1(b) = (16 / R3 - 2) * b mod 16.
 // The kernel rotates by it; the host folds the phase that undoes it into the pass-2 twiddles (rt_tables.h: scan_twiddles).

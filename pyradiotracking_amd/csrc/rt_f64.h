@@ -41,6 +41,7 @@ struct F64StftParams {
     const cd *tw;            // [M / 2] W_M^j  (these three: rt_tables.h, bluestein_tables / transform_twiddles in long double)
     double *spec;            // [S][T][N]
     double *tail;            // [S][K][N], or null
+    const int32_t *absent;   // [S] non-zero: the stream sits this call out (rt_set_present) -- its workgroups end at once; or null
 };
 
 // One segment's sample n in float64: complex128 as it is; a wire-format byte pair as pyrtlsdr converts it (packed_bytes_to_iq:
@@ -105,6 +106,7 @@ __global__ __launch_bounds__(kF64Block) void stft_f64(const F64StftParams p) {
     const int s = blockIdx.x / blocks_per_stream;
     const int seg0 = (blockIdx.x % blocks_per_stream) * SPB;
     if (s >= p.n_streams) return;
+    if (p.absent && p.absent[s] != 0) return;  // (workgroup-uniform, ahead of the first barrier)
     const int TPS = kF64Block / SPB;
     const int q = tid / TPS, lt = tid % TPS;
     cd *const xs = x + (int64_t)q * M;
@@ -187,6 +189,10 @@ struct F64DetectArgs {
     int32_t *out_off;           // [S + 1] each stream's first record in `out`, and the total
     int32_t *out_count;         // [S] records each stream wanted (copied to the host behind the call)
     double *row_means;          // RT_FLAG_ROW_MEANS: [S][F] every row's mean (the call slot's device buffer), written by detect_f64<true> only
+    // a handle whose streams may sit out a call (rt_set_present; null on every other handle)
+    const int32_t *absent;        // [S] non-zero: the stream is absent from this call -- no records, NaN row means
+    const int32_t *n_seg_last_s;  // [S] columns of each stream's OWN previous buffer (-1: none -- takes no_last's place)
+    int32_t tail_k;               // ... and K, the columns the look-back tail holds
 };
 
 __device__ __forceinline__ DetectParams64 f64_stream_params(const F64DetectArgs &a, int s) {
@@ -194,6 +200,11 @@ __device__ __forceinline__ DetectParams64 f64_stream_params(const F64DetectArgs 
     if (a.no_last && a.no_last[s]) {
         dp.n_seg_last = -1;
         dp.tail_cols = 0;
+    }
+    if (a.n_seg_last_s) {
+        const int32_t n = a.n_seg_last_s[s];
+        dp.n_seg_last = n;
+        dp.tail_cols = n < 0 ? 0 : (n < a.tail_k ? n : a.tail_k);
     }
     if (a.thr_s) dp.thr = a.thr_s[s];
     if (a.cal_s) dp.cal_db = a.cal_s[s];
@@ -216,6 +227,10 @@ __global__ __launch_bounds__(256) void detect_f64(const F64DetectArgs a) {
     if (i >= (int64_t)a.n_streams * a.n_bins) return;
     const int s = (int)(i / a.n_bins), fi = (int)(i % a.n_bins);
     const int F = a.n_bins;
+    if (a.absent && a.absent[s] != 0) {  // the stream sat this call out: no row (its raw counter stays zero), NaN as at T == 0
+        if constexpr (ROW_MEANS) a.row_means[i] = NAN;
+        return;
+    }
     const DetectParams64 dp = f64_stream_params(a, s);
     const double *row = a.spec + (int64_t)s * dp.n_seg * F + fi;
     const F64Prev prev{a.prev ? a.prev + ((int64_t)s * a.prev_cols + a.prev_cols) * F + fi : nullptr, F};

@@ -34,6 +34,7 @@ struct GeneralParams {
     const cf *tw;            // [N / 2] W_N^m
     float *spec;             // [S][T][N]
     float *tail;             // [S][K][N], or null
+    const int32_t *absent;   // [S] non-zero: the stream sits this call out (rt_set_present) -- its workgroups end at once; or null
 };
 
 constexpr int kGeneralBlock = 256;
@@ -216,6 +217,7 @@ __global__ __launch_bounds__(kGeneralBlock) void stft_general(const GeneralParam
     const int s = blockIdx.x / blocks_per_stream;
     const int seg0 = (blockIdx.x % blocks_per_stream) * SPB;
     if (s >= p.n_streams) return;
+    if (p.absent && p.absent[s] != 0) return;  // (workgroup-uniform, ahead of the first barrier)
     const raw_t *src = reinterpret_cast<const raw_t *>(p.iq) + (int64_t)s * p.stream_stride + (int64_t)seg0 * N;
     const int n_here = (T - seg0 < SPB) ? (T - seg0) : SPB;  // segments of this block inside the buffer
     // threads per segment: TPS = 256 / SPB (SPB divides 256: both powers of two, SPB <= 64)
@@ -290,6 +292,7 @@ struct BluesteinParams {
     const cf *bfilt;  // [M] FFT_M of the filter, divided by M, in BIT-REVERSED order (entry i = the transform's value at rev i)
     const cf *tw;     // [M / 2] W_M^j
     float *spec, *tail;
+    const int32_t *absent;  // [S] non-zero: the stream sits this call out (rt_set_present) -- its workgroups end at once; or null
 };
 
 template <int FMT, int U = 1, int BLK = kGeneralBlock>
@@ -305,6 +308,7 @@ __global__ __launch_bounds__(BLK) void stft_bluestein(const BluesteinParams p) {
     if constexpr (U > 1) fft_stage_tables(tw_hi, tw_lo, p.tw, M, tid, BLK);
     const int s = blockIdx.x / T, seg = blockIdx.x % T;
     if (s >= p.n_streams) return;
+    if (p.absent && p.absent[s] != 0) return;  // (workgroup-uniform)
     const raw_t *src = reinterpret_cast<const raw_t *>(p.iq) + (int64_t)s * p.stream_stride + (int64_t)seg * N;
     // the samples' sum (float64, a fixed order: a thread's samples, the wave's lanes by butterflies, the four waves); zero padding
     for (int j = N + tid; j < M; j += BLK) xs[j] = cf{0.f, 0.f};
@@ -385,10 +389,16 @@ __global__ __launch_bounds__(256) void row_sums_dense(const float *spec, float *
 // own expression (row_sum_from_partials, rounded once, / T in float32) -- so every record's row_mean is its entry bit for bit.
 // A thread per (stream, bin), neighbouring threads on neighbouring bins: each partial row is read in whole lines.  `out` is the
 // call slot's device buffer [S][N] (include/rt_analyze.h: rt_fetch_row_means copies it).
-__global__ __launch_bounds__(256) void row_means_from_partials(const float *psum, int chunks, int n_streams, int n_bins, int n_seg, float *out) {
+// `absent` ([S], or null): a stream that sat the call out (rt_set_present) has no row -- NaN, as at T == 0.
+__global__ __launch_bounds__(256) void row_means_from_partials(const float *psum, int chunks, int n_streams, int n_bins, int n_seg, float *out,
+                                                              const int32_t *absent) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)n_streams * n_bins) return;
     const int s = (int)(i / n_bins), bin = (int)(i % n_bins);
+    if (absent && absent[s] != 0) {
+        out[i] = NAN;
+        return;
+    }
     out[i] = (float)row_sum_from_partials(psum + (int64_t)s * chunks * n_bins + bin, chunks, n_bins) / (float)n_seg;
 }
 

@@ -283,4 +283,69 @@ void hc_bluestein_tables_f64(const double *window, int N, int M, int log2m, cd *
     std::memcpy(bfilt, t.bfilt.data(), t.bfilt.size() * sizeof(cd));
 }
 
+// ---- streams that sit out a call (rt_core.h: PresenceBook) ----
+// The bookkeeping as a handle drives it: one book, the pending resets, the rotation of the look-back tails, and the two call
+// slots' snapshots (call k in slot k % 2).  `all`: the one segment count the handle had when rt_set_present was first called.
+struct HcPresence {
+    PresenceBook book;
+    std::vector<uint8_t> reset_pending;
+    int tail_cur = 0;
+    unsigned long long n_calls = 0;
+    PresenceCall slot[2];
+};
+static void hc_presence_copy(const PresenceCall &c, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
+    if (absent) std::memcpy(absent, c.absent.data(), c.absent.size());
+    if (n_seg_last) std::memcpy(n_seg_last, c.n_seg_last.data(), c.n_seg_last.size() * sizeof(int32_t));
+    if (tails) {
+        tails[0] = c.tail_read;
+        tails[1] = c.tail_write;
+    }
+}
+void *hc_presence_new(int n_streams, int all) {
+    HcPresence *p = new HcPresence();
+    p->book.activate(n_streams, all);
+    p->reset_pending.assign((size_t)n_streams, (uint8_t)0);
+    return p;
+}
+void hc_presence_free(void *h) { delete static_cast<HcPresence *>(h); }
+int hc_presence_set(void *h, const uint8_t *mask) { return static_cast<HcPresence *>(h)->book.set_mask(mask) ? 1 : 0; }
+void hc_presence_reset_stream(void *h, int s) { static_cast<HcPresence *>(h)->reset_pending[(size_t)s] = 1; }
+void hc_presence_reset_all(void *h) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    p->book.forget_all();
+    std::fill(p->reset_pending.begin(), p->reset_pending.end(), (uint8_t)0);
+}
+// one call of T segments: its snapshot (absent[S], n_seg_last[S], tails[2] = buffer read / written); returns the streams present
+int hc_presence_call(void *h, int T, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    PresenceCall &c = p->slot[p->n_calls % 2];
+    p->book.begin_call(T, p->tail_cur, p->reset_pending, c);
+    p->tail_cur = c.tail_write;
+    ++p->n_calls;
+    hc_presence_copy(c, absent, n_seg_last, tails);
+    return c.n_present;
+}
+// the snapshot call number `k` (0-based; one of the latest two) was enqueued with: what a re-analysis inside rt_fetch reads
+int hc_presence_snapshot(void *h, unsigned long long k, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    if (k >= p->n_calls || k + 2 < p->n_calls) return -1;
+    hc_presence_copy(p->slot[k % 2], absent, n_seg_last, tails);
+    return p->slot[k % 2].n_present;
+}
+// the newest call is undone
+void hc_presence_rollback(void *h) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    if (p->n_calls == 0) return;
+    --p->n_calls;
+    const PresenceCall &c = p->slot[p->n_calls % 2];
+    p->book.rollback(c, p->reset_pending);
+    p->tail_cur = c.tail_read;
+}
+void hc_presence_state(void *h, int32_t *n_seg_last, uint8_t *reset_pending, uint8_t *present) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    std::memcpy(n_seg_last, p->book.n_seg_last.data(), p->book.n_seg_last.size() * sizeof(int32_t));
+    std::memcpy(reset_pending, p->reset_pending.data(), p->reset_pending.size());
+    std::memcpy(present, p->book.present.data(), p->book.present.size());
+}
+
 }  // extern "C"

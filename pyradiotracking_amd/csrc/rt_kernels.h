@@ -1656,11 +1656,16 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
 //     so that most workgroups of a one-to-one launch would keep one wave busy and three idle.
 // Dynamic LDS: one bit per chunk.
 __global__ __launch_bounds__(256) void plan_pass_b(const uint16_t *full, uint16_t *first, int32_t *item_chunks, int32_t *item_count,
-                                                   int lg, int segs_per_chunk, int n_seg, int chunks, int blocks_per_stream, int gpw) {
+                                                   int lg, int segs_per_chunk, int n_seg, int chunks, int blocks_per_stream, int gpw,
+                                                   const int32_t *absent /* [S] rt_set_present, or null */) {
     extern __shared__ uint32_t plan_lds[];
     uint32_t *const any_w = plan_lds;  // [(chunks + 31) / 32]
     __shared__ uint32_t first_any, wave_cnt[4];
     const int s = blockIdx.x, tid = threadIdx.x;
+    if (absent && absent[s] != 0) {  // (workgroup-uniform, ahead of the first barrier: pass A wrote no bits for this stream)
+        if (tid == 0) item_count[s] = 0;
+        return;
+    }
     const int words = (chunks + 31) / 32;
     for (int i = tid; i < words; i += 256) any_w[i] = 0u;
     if (tid == 0) first_any = 0u;
@@ -1737,10 +1742,11 @@ __global__ __launch_bounds__(256) void plan_pass_b(const uint16_t *full, uint16_
 // (kPlanRowsPerWave, kPlanMaxRun, RunPlanner, plan_tile_rows: rt_core.h -- shared with the host check of the CPU test-suite)
 template <int K>
 __global__ __launch_bounds__(64) void plan_runs(const uint16_t *hot, uint16_t *need, int32_t *seg_list, int32_t *seg_count,
-                                                int n_seg, int lg, int r, int tile_rows) {
+                                                int n_seg, int lg, int r, int tile_rows, const int32_t *absent /* [S] rt_set_present, or null */) {
     extern __shared__ unsigned char plan_any[];  // [64 / w * tile_rows]
     using u64 = unsigned long long;
     const int s = blockIdx.x, lane = threadIdx.x;  // (streams along x: a grid's y extent ends at 65 535)
+    if (absent && absent[s] != 0) return;  // (the whole wave: the bit scan left this stream alone, its segment count stays zero)
     const int w = lg / 4;                     // 64-bit words per row (4 .. 64)
     const int tpw = 64 / w;                   // tiles per wave
     const int c = lane % w, tj = lane / w;
@@ -1953,7 +1959,7 @@ __global__ __launch_bounds__(256) void check_bin_thresholds(const float *thr_nat
 // `seg_count`); and, by workgroup 0, max_abs_hot's job.
 __global__ __launch_bounds__(256) void after_bit_scan(uint32_t *abs_hot, uint32_t *host_max, const float *thr_nat, const float *psum, int n_streams, int N,
                                                      int items_per_stream, int n_seg, float snr, const StreamSettings *set_s, int32_t *stream_overflow, unsigned long long *counters,
-                                                     unsigned long long flag, int32_t *seg_count) {
+                                                     unsigned long long flag, int32_t *seg_count, const int32_t *absent /* [S] rt_set_present, or null */) {
     __shared__ uint32_t wave_max[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i <= n_streams) seg_count[i] = 0;
@@ -1973,6 +1979,7 @@ __global__ __launch_bounds__(256) void after_bit_scan(uint32_t *abs_hot, uint32_
     const float th = thr_nat[i];
     if (!(th > 0.f)) return;
     const int s = (int)(i / N), bin = (int)(i % N);
+    if (absent && absent[s] != 0) return;  // (no row sums of this call to hold its thresholds against: nothing of it is analysed)
     double sum = 0.0;
     for (int c = 0; c < items_per_stream; ++c) sum += (double)psum[((int64_t)s * items_per_stream + c) * N + bin];
     const float avg = (float)sum / (float)n_seg;
@@ -2051,6 +2058,9 @@ struct DetectArgs {
     int32_t filtered;          // the candidate lists come from the run-length pre-filter (stft_scan MODE 5): a run whose
                                //     preceding cell is missing lies across the edge of the emitted chunks, is too short
                                //     to pass the duration gate and is dropped (without the filter that is an internal error)
+    // a handle whose streams may sit out a call (rt_set_present; null on every other handle)
+    const int32_t *absent;        // [S] non-zero: the stream is absent from this call -- no records (the scans left it alone)
+    const int32_t *n_seg_last_s;  // [S] columns of each stream's OWN previous buffer (-1: none -- takes no_last's place)
 };
 
 // the detect parameters as stream `s` sees them (s is workgroup- or wave-uniform: scalar loads)
@@ -2060,6 +2070,7 @@ __device__ __forceinline__ DetectParams stream_params(const DetectArgs &a, int s
     if (a.cal_s) dp.cal_db = a.cal_s[s];
     if (a.set_s) apply_stream_settings(dp, a.set_s[s]);
     if (a.no_last && a.no_last[s]) dp.n_seg_last = -1;
+    if (a.n_seg_last_s) dp.n_seg_last = a.n_seg_last_s[s];
     return dp;
 }
 
@@ -3267,7 +3278,10 @@ __global__ __launch_bounds__(kDetBlock) void detect_dense(const DetectArgs a) {
     if (a.psum)
         while (F * Q * 2 <= kDetBlock && Q * 2 * 64 <= T) Q *= 2;
     const int span = (T + Q - 1) / Q;
-    for (int item = tid; item < F * Q; item += kDetBlock) {
+    // (a stream that sits this call out, rt_set_present: no rows to scan -- its workgroup still publishes zero records and takes
+    // its part in closing the call)
+    const int n_items = (a.absent && a.absent[s] != 0) ? 0 : F * Q;
+    for (int item = tid; item < n_items; item += kDetBlock) {
         const int fi = item % F, q = item / F;
         const int t_begin = q * span;
         const int t_end = (t_begin + span < T) ? t_begin + span : T;

@@ -89,6 +89,7 @@ class BatchRunner:
         signal_queue=None,
         analyzer_factory: Optional[Callable] = None,
         clock: Callable[[], float] = time.time,
+        skip_absent: bool = False,
         **analysis_kwargs,
     ):
         """``device`` / ``calibration`` / ``sdr_*`` / ``state_update_s`` are the reference's command-line
@@ -97,7 +98,12 @@ class BatchRunner:
         calibration_db=[...], gpu=..., **analysis_kwargs)`` defaults to ``BatchSignalAnalyzer``; ``clock``
         returns seconds since the epoch (tests pass their own).  The detection keywords an analyzer takes per stream
         (``PER_DEVICE_KWARGS``) may be sequences with one value per ``device`` entry: every GPU's analyzer then gets the
-        values of its own devices, in slot order, like ``calibration``; scalars go to every analyzer as they are."""
+        values of its own devices, in slot order, like ``calibration``; scalars go to every analyzer as they are.
+        ``skip_absent=True``: the caller states that an SDR's buffers are contiguous whenever they arrive (a callback that is
+        merely late).  An SDR without a buffer in a step then sits that step out (``BatchSignalAnalyzer.set_present``): its row is
+        not read, on the host and on the device-tensor path alike, and its next buffer looks back into its own last one -- as
+        the reference's analyzer of that SDR, which was simply not called.  Default: such a row is analysed as zeros and the
+        stream starts its next buffer without look-back."""
         self.devices = [str(d) for d in device]
         for name in self.PER_DEVICE_KWARGS:
             v = analysis_kwargs.get(name)
@@ -122,6 +128,7 @@ class BatchRunner:
             analyzer_factory = BatchSignalAnalyzer
         self._factory = analyzer_factory
         self._clock = clock
+        self.skip_absent = bool(skip_absent)
         self.running = True
         self.streams: List[StreamState] = []
         self.analyzers: Dict[int, object] = {}   # gpu -> batch analyzer
@@ -252,6 +259,8 @@ class BatchRunner:
         enqueued = []
         try:
             for gpu, members in self._members.items():
+                if self.skip_absent:
+                    self.analyzers[gpu].set_present([active[i] for i in members])
                 if per_gpu is not None:
                     self.analyzers[gpu].enqueue(per_gpu[gpu])
                 else:
@@ -259,7 +268,7 @@ class BatchRunner:
                     cdt = np.complex128 if getattr(self.analyzers[gpu], "precision", "float32") == "float64" else np.complex64
                     chunk = np.ascontiguousarray(host[members], dtype=cdt)
                     for k, i in enumerate(members):
-                        if not active[i]:
+                        if not active[i] and not self.skip_absent:
                             chunk[k] = 0  # no samples: zero power, below every threshold
                     self.analyzers[gpu].enqueue(chunk)
                 enqueued.append(gpu)
@@ -279,7 +288,8 @@ class BatchRunner:
         ts_starts: List[Optional[datetime.datetime]] = [None] * n
         for i, st in enumerate(self.streams):
             if not active[i]:
-                st.stale = True
+                # (skip_absent: the stream sat the step out and keeps its look-back -- and a staleness it had before)
+                st.stale = st.stale if self.skip_absent else True
                 continue
             st.stale = False
             n_samples = host.shape[1] if host is not None else int(per_gpu[st.gpu].shape[1])
