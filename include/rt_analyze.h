@@ -198,8 +198,8 @@ int rt_set_stream_params(rt_handle *h, const float *threshold, const float *cali
  * each other); a third rt_process without
  * an rt_fetch drops the oldest unfetched result.  `iq_dev` must stay valid and
  * unchanged until the call has been fetched.  `iq_dev` must be 8-byte aligned (whole complex64
- * samples; rt_process_u8: 2-byte aligned; rt_process_i16: 4-byte aligned) -- anything else is refused with
- * RT_E_INVALID, not launched.
+ * samples; rt_process_u8 and rt_process_i8: 2-byte aligned; rt_process_i16: 4-byte aligned) -- anything else is
+ * refused with RT_E_INVALID, not launched.
  */
 int rt_process(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride);
 
@@ -227,16 +227,32 @@ int rt_process_u8(rt_handle *h, const void *iq_u8_dev, int64_t n_samples, int64_
 int rt_process_i16(rt_handle *h, const void *iq_i16_dev, int64_t n_samples, int64_t stream_stride);
 
 /*
+ * Same for 8-bit signed IQ (HackRF's native format, SoapySDR CS8, UHD sc8, SigMF ci8): `iq_i8_dev` is a DEVICE pointer
+ * to S*stream_stride samples of interleaved two's-complement int8 (I, Q) -- 2 bytes per sample, 2-byte aligned (whole
+ * I,Q pairs; anything else is refused with RT_E_INVALID, not launched).  A component's value is (float)i * 2^-7
+ * ((double)i * 2^-7 on a float64 handle): range [-1, 1 - 2^-7], -128 is legal and maps to -1.  Both the conversion and
+ * the multiplication are exact and happen in the scan kernel's load; everything after it is the complex64 path, detrend
+ * by linearity and RT_FLAG_NO_LIN_DETREND included (unlike rt_process_u8, whose b / 127.5 - 1 lies half a step away
+ * from these values and which always subtracts the mean first).  So the call delivers, byte for byte, the records, row
+ * means and record cells of rt_process on the complex64 (float64 handle: complex128) array q * 2^-7 -- with 2 bytes of
+ * memory traffic a sample instead of 8 (16).  No other scale is offered: a radio whose full scale sits elsewhere
+ * differs by a constant, which calibration_db takes.  n_samples / stream_stride count samples.
+ */
+int rt_process_i8(rt_handle *h, const void *iq_i8_dev, int64_t n_samples, int64_t stream_stride);
+
+/*
  * Same with IQ in host memory: copied (blocking) to an internal device buffer first -- one per call in flight, so
  * the caller may reuse its buffer as soon as the call returns and a call's samples stay in place until it is
  * fetched.  rt_process_u8_host takes what librtlsdr's read callback delivers (interleaved uint8 I,Q in host
  * memory): the direct replacement of `sdr.read_samples_async(self.process_samples, ...)` + packed_bytes_to_iq
  * (analyze.py:157) for a binding that registers a bytes callback instead.  rt_process_i16_host takes interleaved
- * int16 I,Q in host memory (what a CS16 / sc16 stream or a ci16_le recording delivers), 4 bytes a sample.
+ * int16 I,Q in host memory (what a CS16 / sc16 stream or a ci16_le recording delivers), 4 bytes a sample;
+ * rt_process_i8_host interleaved int8 I,Q (a HackRF transfer, a CS8 / sc8 stream, a ci8 recording), 2 bytes a sample.
  */
 int rt_process_host(rt_handle *h, const void *iq_host, int64_t n_samples, int64_t stream_stride);
 int rt_process_u8_host(rt_handle *h, const void *iq_u8_host, int64_t n_samples, int64_t stream_stride);
 int rt_process_i16_host(rt_handle *h, const void *iq_i16_host, int64_t n_samples, int64_t stream_stride);
+int rt_process_i8_host(rt_handle *h, const void *iq_i8_host, int64_t n_samples, int64_t stream_stride);
 
 /*
  * Wait for the OLDEST unfetched rt_process / rt_extract and copy its records, ordered by
@@ -321,7 +337,8 @@ const char *rt_last_error(rt_handle *h);
  *   - the native sinks of rt_format.h / rt_match.h take float32 rt_record arrays only.
  * rt_process / rt_process_host take complex128 (interleaved float64 I,Q; 16-byte aligned) on such a handle;
  * rt_process_u8 / rt_process_u8_host take the wire format and convert it as pyrtlsdr does, (double)b / 127.5 - 1.0;
- * rt_process_i16 / rt_process_i16_host take int16 pairs as (double)i * 2^-15 (exact).
+ * rt_process_i16 / rt_process_i16_host take int16 pairs as (double)i * 2^-15 (exact), rt_process_i8 / rt_process_i8_host
+ * int8 pairs as (double)i * 2^-7 (exact).
  * Every other rt_config field keeps its meaning (two calls in flight, record_capacity a starting size that grows,
  * rt_reset / rt_reset_stream, hip_stream); the float32 fields window / scale / threshold / snr_threshold /
  * calibration_db are replaced by rt_config_f64.  A float32 entry point that has a float64 twin (rt_fetch,

@@ -137,6 +137,8 @@ ABI_SYMBOLS = (
     "rt_process_u8_host",
     "rt_process_i16",
     "rt_process_i16_host",
+    "rt_process_i8",
+    "rt_process_i8_host",
     "rt_fetch",
     "rt_extract",
     "rt_spectrogram",
@@ -205,6 +207,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_process_u8_host.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.rt_process_i16.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.rt_process_i16_host.argtypes = [vp, vp, C.c_int64, C.c_int64]
+    lib.rt_process_i8.argtypes = [vp, vp, C.c_int64, C.c_int64]
+    lib.rt_process_i8_host.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.rt_fetch.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.rt_extract.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int32]
     lib.rt_spectrogram.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
@@ -462,6 +466,9 @@ class NativeAnalyzer:
     def process_device_i16(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):
         self._check(self._lib.rt_process_i16(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
 
+    def process_device_i8(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):
+        self._check(self._lib.rt_process_i8(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
+
     def process_host(self, iq: np.ndarray):
         """``[S, B]`` complex IQ in host memory: complex64 (complex128 on a float64 handle, where complex64 is widened exactly)."""
         a = np.ascontiguousarray(iq, dtype=np.complex128 if self.f64 else np.complex64)
@@ -492,6 +499,18 @@ class NativeAnalyzer:
         if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % 2:
             raise ValueError(f"expected int16 [{self.n_streams}, 2*B]")
         self._check(self._lib.rt_process_i16_host(self._handle, a.ctypes.data, a.shape[1] // 2, a.shape[1] // 2))
+
+    def process_host_i8(self, raw: np.ndarray):
+        """``[S, 2*B]`` int8 (interleaved I, Q) in host memory; staged by the library (one buffer per call in flight)."""
+        a = np.asarray(raw)
+        if a.dtype != np.int8:
+            raise TypeError("expected int8 (interleaved I, Q)")
+        a = np.ascontiguousarray(a)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % 2:
+            raise ValueError(f"expected int8 [{self.n_streams}, 2*B]")
+        self._check(self._lib.rt_process_i8_host(self._handle, a.ctypes.data, a.shape[1] // 2, a.shape[1] // 2))
 
     def fetch(self, allow_truncated: bool = False) -> np.ndarray:
         """Records of the oldest enqueued call.  A call whose records were truncated (``RT_E_CAPACITY``: an ``rt_extract``

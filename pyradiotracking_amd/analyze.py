@@ -535,8 +535,10 @@ class BatchSignalAnalyzer:
         """Figures of the last fetched call (with lanes: counts and times summed over the lanes' launches)."""
         return self._native.call_info()
 
-    def _process_device(self, ptr: int, n_samples: int, stride: Optional[int], bytes_per_sample: int, u8: bool, i16: bool = False):
-        if i16:
+    def _process_device(self, ptr: int, n_samples: int, stride: Optional[int], bytes_per_sample: int, u8: bool, i16: bool = False, i8: bool = False):
+        if i8:
+            self._native.process_device_i8(ptr, n_samples, stride)
+        elif i16:
             self._native.process_device_i16(ptr, n_samples, stride)
         elif u8:
             self._native.process_device_u8(ptr, n_samples, stride)
@@ -653,6 +655,46 @@ class BatchSignalAnalyzer:
             torch.cuda.current_stream(raw.device).synchronize()
         stride = (raw.stride(0) if raw.shape[0] > 1 else raw.shape[1]) // 2
         self._process_device(raw.data_ptr(), raw.shape[1] // 2, stride, 4, False, True)
+
+    def enqueue_int8(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None):
+        """Same as :meth:`enqueue` for 8-bit signed IQ (HackRF's native format, SoapySDR ``CS8``, UHD ``sc8``, SigMF ``ci8``):
+        interleaved two's-complement int8 I, Q, a component's value ``i * 2**-7``.  ``raw``: host ndarray / CUDA torch tensor of int8
+        shaped ``[S, 2*B]`` (or ``[2*B]`` for one stream), or a raw device pointer (2-byte aligned) with ``n_samples``.  The conversion
+        is exact and fused into the scan kernel's load: the results are those of :meth:`enqueue` on
+        ``synth.i8_to_complex64(raw)`` (``i8_to_complex128`` on a float64 analyzer), byte for byte."""
+        if isinstance(raw, int):
+            if n_samples is None:
+                raise ValueError("n_samples is required with a raw device pointer")
+            self._process_device(raw, n_samples, stream_stride, 2, False, False, True)
+            return
+        if isinstance(raw, np.ndarray):
+            if raw.dtype != np.int8:
+                raise TypeError("expected an int8 array (interleaved I, Q)")
+            a = np.ascontiguousarray(raw)
+            if a.ndim == 1:
+                a = a[None, :]
+            if a.ndim != 2 or a.shape[0] != len(self.devices) or a.shape[1] % 2:
+                raise ValueError("expected int8 [S, 2*B]")
+            if a.shape[1] // 2 > self.sdr_callback_length:
+                raise ValueError("buffer longer than sdr_callback_length")
+            # staged by the library: one device buffer per call in flight, kept until the call is fetched
+            self._native.process_host_i8(a)
+            return
+        if raw.dim() == 1:
+            raw = raw[None, :]
+        if str(raw.dtype) != "torch.int8" or not raw.is_cuda or raw.dim() != 2 or raw.stride(1) != 1 or raw.shape[1] % 2:
+            raise TypeError("device samples must be a CUDA int8 tensor [S, 2*B] with unit stride")
+        if raw.shape[0] != len(self.devices) or (raw.shape[0] > 1 and raw.stride(0) % 2):
+            raise ValueError("device samples must be int8 [S, 2*B], a whole number of samples from stream to stream")
+        if raw.shape[1] // 2 > self.sdr_callback_length:
+            raise ValueError("buffer longer than sdr_callback_length")
+        self._hold(raw)
+        if self._hip_stream is None:
+            import torch
+
+            torch.cuda.current_stream(raw.device).synchronize()
+        stride = (raw.stride(0) if raw.shape[0] > 1 else raw.shape[1]) // 2
+        self._process_device(raw.data_ptr(), raw.shape[1] // 2, stride, 2, False, False, True)
 
     def fetch_records(self, allow_truncated: bool = False) -> np.ndarray:
         """Wait for the oldest enqueued call; structured array of ``rt_record`` ordered by stream.  The reference
@@ -896,6 +938,30 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         self.noise_dbw = self.signal_data = None
         self._batch.enqueue_int16(raw.reshape(1, -1))
+        rec = self._batch.fetch_records()
+        self._keep_noise()
+        self._keep_cells(rec["shadowed"] == 0)
+        rec = rec[rec["shadowed"] == 0]
+        [self.consume_signal(s) for s in self._decoder.signals(rec, [self.device], [ts_start])]
+        return None
+
+    def process_int8(self, raw: np.ndarray, context=None):
+        """The callback for an 8-bit signed source (a HackRF, SoapySDR ``CS8``, UHD ``sc8``, a ``ci8`` recording): ``raw`` is the interleaved
+        int8 I/Q buffer (2 bytes per sample, value ``i * 2**-7``).  Same bookkeeping and queue contract as
+        :meth:`process_samples`, and the signals of ``process_samples(synth.i8_to_complex64(raw))``; the conversion happens
+        in the scan kernel's load."""
+        raw = np.asarray(raw)
+        if raw.dtype != np.int8:
+            raise TypeError("expected an int8 array (interleaved I, Q)")
+        raw = np.ascontiguousarray(raw).reshape(-1)
+        if raw.size % 2:
+            raise ValueError("expected int8 [2*B]: an I and a Q for every sample")
+        n = raw.size // 2
+        if n > self._batch.sdr_callback_length:
+            raise ValueError("buffer longer than sdr_callback_length")
+        ts_start = self._clock(n)
+        self.noise_dbw = self.signal_data = None
+        self._batch.enqueue_int8(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
         self._keep_cells(rec["shadowed"] == 0)

@@ -53,7 +53,7 @@ constexpr uint32_t kFlagLaneOfLargeBatch = 0x40000000u;  // rt_config.flags of a
 thread_local bool g_creating_lane = false;  // rt_create of a laned handle is creating one of its lanes
 
 // bytes of a sample on a float32 handle, by input format (rt_kernels.h: kFmt*)
-constexpr size_t fmt_sample_bytes(int fmt) { return fmt == kFmtU8 ? 2u : fmt == kFmtI16 ? 4u : sizeof(cf); }
+constexpr size_t fmt_sample_bytes(int fmt) { return (fmt == kFmtU8 || fmt == kFmtI8) ? 2u : fmt == kFmtI16 ? 4u : sizeof(cf); }
 constexpr int kSlots = 2;
 constexpr int kTails = 3;
 constexpr int64_t kInitialPoolRecords = 4 << 20;  // pinned record pool per slot at rt_create unless rt_config.record_pool says otherwise
@@ -75,7 +75,7 @@ struct CallCtx {
     int mode_used = 0;
     bool fell_back = false;
     bool is_extract = false;
-    int fmt = kFmtC64;      // the format the IQ was enqueued in: complex64, interleaved uint8 (RTL-SDR wire format) or interleaved int16 (CS16)
+    int fmt = kFmtC64;      // the format the IQ was enqueued in: complex64, interleaved uint8 (RTL-SDR wire format), int16 (CS16) or int8 (CS8)
     bool no_last = false;   // the slot's h_no_last flags apply (some stream was reset, rt_reset_stream)
     int n_dense_streams = 0;  // streams of this call that were re-run dense on their own (AUTO, partial fall-back)
     int pool_grown = 0;       // times the record pool was enlarged for this call and the call analysed again (fetch_one)
@@ -174,7 +174,7 @@ struct F64Slot {
     rt_record_f64 *h_out = nullptr;                    // pinned, device-visible: [S * rec_cap] the call's records
     double *d_row_means = nullptr;                     // [S][N] the call's row means (RT_FLAG_ROW_MEANS only; rt_fetch_row_means_f64 copies them)
     int32_t *h_meta = nullptr;                         // pinned, device-visible: [S + 1] offsets + total, then [S] wanted
-    void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host / rt_process_i16_host
+    void *d_stage = nullptr;                           // rt_process_host / rt_process_u8_host / rt_process_i16_host / rt_process_i8_host
     size_t stage_bytes = 0;
     // RT_FLAG_RECORD_CELLS only, as in Slot:
     double *d_cells = nullptr;
@@ -384,12 +384,12 @@ void launch_detect_dense(rt_handle *h, int grid, hipStream_t st, const DetectArg
 // that just fills the chip: CUs x the workgroups of this instantiation a CU holds (its __launch_bounds__), each
 // workgroup drawing further items from p.work (rt_kernels.h: "Work items") -- more workgroups than that would only
 // queue in the dispatcher and find the counter exhausted.
-// the fused scans' template arguments of an input format (rt_kernels.h, scan_fmt): <.., MODE | kModeI16, false, ..> is int16 input
+// the fused scans' template arguments of an input format (rt_kernels.h, scan_fmt): <.., MODE | kModeI16, false, ..> is int16 input, <.., MODE | kModeI8, false, ..> int8
 #define RT_SCAN_KERNEL(R3_, QS_) (stft_scan<R3_, MODEF, FMT == kFmtU8, LIN, QS_>)
 #define RT_WG_KERNEL(B_, W_) (stft_wg<B_, MODEF, FMT == kFmtU8, W_>)
 template <int MODE, int FMT, bool LIN>
 void launch_stft_lin(rt_handle *h, const StftParams &p, int items, hipStream_t st) {
-    constexpr int MODEF = MODE | (FMT == kFmtI16 ? kModeI16 : 0);
+    constexpr int MODEF = MODE | (FMT == kFmtI16 ? kModeI16 : FMT == kFmtI8 ? kModeI8 : 0);
     if (h->big) {
         // nperseg 8192 / 16 384: one workgroup per item (a chunk of one stream), a segment per step (rt_scan_wg.h)
         if constexpr (MODE <= 2) {
@@ -530,6 +530,7 @@ void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_s
     do {                                                                                                                          \
         if (fmt == kFmtU8) hipLaunchKernelGGL((stft_bluestein<kFmtU8, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);        \
         else if (fmt == kFmtI16) hipLaunchKernelGGL((stft_bluestein<kFmtI16, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b); \
+        else if (fmt == kFmtI8) hipLaunchKernelGGL((stft_bluestein<kFmtI8, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);   \
         else hipLaunchKernelGGL((stft_bluestein<kFmtC64, U_, B_>), dim3(blocks), dim3(B_), lds, h->s_scan, b);                     \
     } while (0)
         if (h->gen_m >= 16384) RT_BLU(4, 1024);
@@ -558,6 +559,7 @@ void launch_general(rt_handle *h, const void *iq, int64_t stream_stride, int n_s
     const size_t lds = (size_t)g.segs_per_block * h->N * sizeof(cf);
     if (fmt == kFmtU8) hipLaunchKernelGGL((stft_general<kFmtU8>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
     else if (fmt == kFmtI16) hipLaunchKernelGGL((stft_general<kFmtI16>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
+    else if (fmt == kFmtI8) hipLaunchKernelGGL((stft_general<kFmtI8>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
     else hipLaunchKernelGGL((stft_general<kFmtC64>), dim3(blocks), dim3(kGeneralBlock), lds, h->s_scan, g);
 }
 
@@ -792,6 +794,7 @@ void launch_scan(rt_handle *h, const StftParams &sp, int blocks, int fmt, hipStr
     if (!st) st = h->s_scan;
     if (fmt == kFmtU8) launch_stft<MODE, kFmtU8>(h, sp, blocks, st);
     else if (fmt == kFmtI16) launch_stft<MODE, kFmtI16>(h, sp, blocks, st);
+    else if (fmt == kFmtI8) launch_stft<MODE, kFmtI8>(h, sp, blocks, st);
     else launch_stft<MODE>(h, sp, blocks, st);
 }
 
@@ -1696,6 +1699,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
             RT_BIG_LDS(kFmtC64);
             RT_BIG_LDS(kFmtU8);
             RT_BIG_LDS(kFmtI16);
+            RT_BIG_LDS(kFmtI8);
 #undef RT_BIG_LDS
             for (const void *f : big_lds) RT_CREATE_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, padded_len(kGeneralMaxN, 14) * (int)sizeof(cf)));
         }
@@ -1813,7 +1817,8 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     if (big) {
 #define RT_WG_SET(B_, M_, U_, W_) RT_CREATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(stft_wg<B_, M_, U_, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_bytes(B_)))
 #define RT_WG_SET4(B_, M_) RT_WG_SET(B_, M_, false, false); RT_WG_SET(B_, M_, false, true); RT_WG_SET(B_, M_, true, false); RT_WG_SET(B_, M_, true, true); \
-    RT_WG_SET(B_, M_ | kModeI16, false, false); RT_WG_SET(B_, M_ | kModeI16, false, true)
+    RT_WG_SET(B_, M_ | kModeI16, false, false); RT_WG_SET(B_, M_ | kModeI16, false, true); \
+    RT_WG_SET(B_, M_ | kModeI8, false, false); RT_WG_SET(B_, M_ | kModeI8, false, true)
         RT_WG_SET4(256, 0); RT_WG_SET4(256, 1); RT_WG_SET4(256, 2);
         RT_WG_SET4(512, 0); RT_WG_SET4(512, 1); RT_WG_SET4(512, 2);
 #undef RT_WG_SET4
@@ -2027,6 +2032,10 @@ int rt_process_i16(rt_handle *h, const void *iq_i16_dev, int64_t n_samples, int6
     return process_impl(h, iq_i16_dev, n_samples, stream_stride, kFmtI16);
 }
 
+int rt_process_i8(rt_handle *h, const void *iq_i8_dev, int64_t n_samples, int64_t stream_stride) {
+    return process_impl(h, iq_i8_dev, n_samples, stream_stride, kFmtI8);
+}
+
 static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, int fmt, bool host);
 
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, int fmt) {
@@ -2048,11 +2057,12 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
         h->err = "n_samples/stream_stride out of range for this handle";
         return RT_E_INVALID;
     }
-    // the scan kernel loads whole samples (8-byte complex64 / 2-byte uint8 / 4-byte int16 I,Q pairs): a misaligned pointer
+    // the scan kernel loads whole samples (8-byte complex64 / 2-byte uint8 or int8 / 4-byte int16 I,Q pairs): a misaligned pointer
     // would fault on the device, so it is refused here
     if (reinterpret_cast<uintptr_t>(iq_dev) % fmt_sample_bytes(fmt) != 0) {
         h->err = fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
-                 : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)" : "IQ pointer must be 8-byte aligned (complex64)";
+                 : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)"
+                 : fmt == kFmtI8 ? "IQ pointer must be 2-byte aligned (int8 I,Q pairs)" : "IQ pointer must be 8-byte aligned (complex64)";
         return RT_E_INVALID;
     }
     RT_HIP(h, hipSetDevice(h->cfg.device));
@@ -2217,6 +2227,10 @@ int rt_process_u8_host(rt_handle *h, const void *iq_u8_host, int64_t n_samples, 
 
 int rt_process_i16_host(rt_handle *h, const void *iq_i16_host, int64_t n_samples, int64_t stream_stride) {
     return process_host_impl(h, iq_i16_host, n_samples, stream_stride, kFmtI16);
+}
+
+int rt_process_i8_host(rt_handle *h, const void *iq_i8_host, int64_t n_samples, int64_t stream_stride) {
+    return process_host_impl(h, iq_i8_host, n_samples, stream_stride, kFmtI8);
 }
 
 int rt_extract(rt_handle *h, const float *spec_dev, int32_t n_seg, int32_t n_bins, const float *last_dev,
@@ -3057,6 +3071,9 @@ int f64_enqueue(rt_handle *h, F64Slot &sl) {
         } else if (sl.fmt == kFmtI16) {
             if (f->blu) stft_f64<kFmtI16, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
             else stft_f64<kFmtI16, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+        } else if (sl.fmt == kFmtI8) {
+            if (f->blu) stft_f64<kFmtI8, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
+            else stft_f64<kFmtI8, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
         } else {
             if (f->blu) stft_f64<kFmtC64, true><<<(unsigned)grid, kF64Block, lds, st>>>(p);
             else stft_f64<kFmtC64, false><<<(unsigned)grid, kF64Block, lds, st>>>(p);
@@ -3161,6 +3178,7 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
     if (!host && reinterpret_cast<uintptr_t>(iq) % sample_bytes != 0)
         return f64_err(h, RT_E_INVALID, fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
                                         : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)"
+                                        : fmt == kFmtI8  ? "IQ pointer must be 2-byte aligned (int8 I,Q pairs)"
                                                          : "IQ pointer must be 16-byte aligned (complex128 on a float64 handle)");
     const int T = (int)(n_samples / f->N);
     if (T == 1) return f64_err(h, RT_E_ONE_SEGMENT, "exactly one segment: the reference raises IndexError (times[1])");
@@ -3322,7 +3340,8 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     const int lds = f->SPB * f->M * (int)sizeof(cd);
     if (lds > 64 * 1024) {
         const void *fns[] = {(const void *)stft_f64<kFmtC64, false>, (const void *)stft_f64<kFmtC64, true>, (const void *)stft_f64<kFmtU8, false>,
-                             (const void *)stft_f64<kFmtU8, true>, (const void *)stft_f64<kFmtI16, false>, (const void *)stft_f64<kFmtI16, true>};
+                             (const void *)stft_f64<kFmtU8, true>, (const void *)stft_f64<kFmtI16, false>, (const void *)stft_f64<kFmtI16, true>,
+                             (const void *)stft_f64<kFmtI8, false>, (const void *)stft_f64<kFmtI8, true>};
         for (const void *fn : fns) RT_F64_CREATE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     // the float64 map (S T N 8 bytes) and the look-back tails

@@ -46,7 +46,7 @@ struct F64StftParams {
 
 // One segment's sample n in float64: complex128 as it is; a wire-format byte pair as pyrtlsdr converts it (packed_bytes_to_iq:
 // `iq /= 127.5; iq -= 1 + 1j` -- a division by (127.5 + 0j) is the real division, then the subtraction; no fma, -ffp-contract=off)
-// An int16 pair is component / 32768: the conversion and the multiplication by 2^-15 are exact.
+// An int16 pair is component / 32768: the conversion and the multiplication by 2^-15 are exact.  An int8 pair is component / 128, as exact.
 template <int FMT>
 __device__ __forceinline__ cd load_f64(const void *base, int64_t i) {
     if constexpr (FMT == kFmtU8) {
@@ -55,6 +55,9 @@ __device__ __forceinline__ cd load_f64(const void *base, int64_t i) {
     } else if constexpr (FMT == kFmtI16) {
         const uint32_t b = reinterpret_cast<const uint32_t *>(base)[i];  // low half I, high half Q
         return cd{(double)(int16_t)(b & 0xFFFFu) * (1.0 / 32768.0), (double)((int32_t)b >> 16) * (1.0 / 32768.0)};
+    } else if constexpr (FMT == kFmtI8) {
+        const uint16_t b = reinterpret_cast<const uint16_t *>(base)[i];  // low byte I, high byte Q
+        return cd{(double)(int8_t)(b & 0xFFu) * (1.0 / 128.0), (double)((int16_t)b >> 8) * (1.0 / 128.0)};
     } else {
         const double2 v = reinterpret_cast<const double2 *>(base)[i];
         return cd{v.x, v.y};

@@ -387,18 +387,23 @@ constexpr int kStamps = 16;  // 0 .. 10 stage sums, 11 steps, 12 / 13 shader-clo
         continue;                                                       \
     }
 
-// raw sample as it sits in HBM: complex64, the RTL-SDR wire format (interleaved uint8 I, Q), or CS16 (interleaved little-endian int16 I, Q)
+// raw sample as it sits in HBM: complex64, the RTL-SDR wire format (interleaved uint8 I, Q), CS16 (interleaved little-endian int16 I, Q),
+// or CS8 (interleaved two's-complement int8 I, Q)
 struct iq_u8 {
     uint16_t iq;  // low byte I, high byte Q
 };
 struct iq_i16 {
     uint32_t iq;  // low half I, high half Q
 };
+struct iq_i8 {
+    uint16_t iq;  // low byte I, high byte Q
+};
 // the input format of a kernel instantiation (the FMT template parameter) and its raw type
-constexpr int kFmtC64 = 0, kFmtU8 = 1, kFmtI16 = 2;
+constexpr int kFmtC64 = 0, kFmtU8 = 1, kFmtI16 = 2, kFmtI8 = 3;
 template <int FMT> struct raw_of { using type = cf; };
 template <> struct raw_of<kFmtU8> { using type = iq_u8; };
 template <> struct raw_of<kFmtI16> { using type = iq_i16; };
+template <> struct raw_of<kFmtI8> { using type = iq_i8; };
 
 // IQ is read exactly once: the loads carry the non-temporal hint (load-only instantiation +4..9 %)
 __device__ __forceinline__ cf load_iq(const cf *p) {
@@ -408,6 +413,7 @@ __device__ __forceinline__ cf load_iq(const cf *p) {
 }
 __device__ __forceinline__ iq_u8 load_iq(const iq_u8 *p) { return iq_u8{__builtin_nontemporal_load(&p->iq)}; }
 __device__ __forceinline__ iq_i16 load_iq(const iq_i16 *p) { return iq_i16{__builtin_nontemporal_load(&p->iq)}; }
+__device__ __forceinline__ iq_i8 load_iq(const iq_i8 *p) { return iq_i8{__builtin_nontemporal_load(&p->iq)}; }
 
 // Buffer loads (wave-uniform descriptor in SGPRs + one 32-bit lane offset + a scalar offset): the 16 loads of a
 // segment share ONE address VGPR.  With flat addresses hipcc keeps a 64-bit pointer per 4 KiB of immediate range
@@ -443,6 +449,9 @@ __device__ __forceinline__ iq_u8 buf_load_iq(rsrc_t r, int voff, int soff, iq_u8
 __device__ __forceinline__ iq_i16 buf_load_iq(rsrc_t r, int voff, int soff, iq_i16) {
     return iq_i16{(uint32_t)raw_buffer_load_i32(r, voff, soff, kAuxNT)};
 }
+__device__ __forceinline__ iq_i8 buf_load_iq(rsrc_t r, int voff, int soff, iq_i8) {
+    return iq_i8{(uint16_t)raw_buffer_load_i16(r, voff, soff, kAuxNT)};
+}
 
 // pyrtlsdr's packed_bytes_to_iq is (byte / 127.5) - 1 per component (in float64); here one
 // float32 fma per component, at most one float32 ulp away, then float32 like complex64 input
@@ -457,9 +466,14 @@ __device__ __forceinline__ cf to_cf(iq_i16 x) {
     constexpr float c = 1.0f / 32768.0f;
     return cf{(float)(int16_t)(x.iq & 0xFFFFu) * c, (float)((int32_t)x.iq >> 16) * c};
 }
+// CS8: component / 128.  int8 -> float32 and the multiplication by 2^-7 are both exact: the same identity
+__device__ __forceinline__ cf to_cf(iq_i8 x) {
+    constexpr float c = 1.0f / 128.0f;
+    return cf{(float)(int8_t)(x.iq & 0xFFu) * c, (float)((int16_t)x.iq >> 8) * c};
+}
 
 // stft_scan<.., QS>: the PER = 16 / QS consecutive samples a lane holds of one sixteenth of its segment, as 16-byte loads (complex64:
-// two samples each; uint8 I/Q: 4 / 8 / 16 bytes in one load; int16 I/Q: 8 bytes, or 16-byte loads of four samples) into the registers e QS + m, e < PER.  The stream bases the host passes
+// two samples each; uint8 and int8 I/Q: 4 / 8 / 16 bytes in one load; int16 I/Q: 8 bytes, or 16-byte loads of four samples) into the registers e QS + m, e < PER.  The stream bases the host passes
 // are aligned to these loads (rt_analyze.hip: process_impl); segments are 16 QS samples long, so every run is.
 template <int PER, int QS>
 __device__ __forceinline__ void load_iq_run(const cf *p, cf (&dst)[16], int m) {
@@ -489,6 +503,27 @@ __device__ __forceinline__ void load_iq_run(const iq_u8 *p, iq_u8 (&dst)[16], in
     for (int h = 0; h < PER / 2; ++h) {
         dst[(2 * h) * QS + m] = iq_u8{(uint16_t)(w[h] & 0xFFFFu)};
         dst[(2 * h + 1) * QS + m] = iq_u8{(uint16_t)(w[h] >> 16)};
+    }
+}
+
+template <int PER, int QS>
+__device__ __forceinline__ void load_iq_run(const iq_i8 *p, iq_i8 (&dst)[16], int m) {
+    uint32_t w[PER / 2];
+    if constexpr (PER == 2) {
+        w[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p));
+    } else if constexpr (PER == 4) {
+        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+        const u2 v = __builtin_nontemporal_load(reinterpret_cast<const u2 *>(p));
+        w[0] = v.x;  w[1] = v.y;
+    } else {
+        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+        const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(p));
+        w[0] = v.x;  w[1] = v.y;  w[2] = v.z;  w[3] = v.w;
+    }
+#pragma unroll
+    for (int h = 0; h < PER / 2; ++h) {
+        dst[(2 * h) * QS + m] = iq_i8{(uint16_t)(w[h] & 0xFFFFu)};
+        dst[(2 * h + 1) * QS + m] = iq_i8{(uint16_t)(w[h] >> 16)};
     }
 }
 
@@ -544,9 +579,9 @@ __host__ __device__ constexpr int scan_block(int R3) { return R3 <= RT_ONE_WAVE_
 #endif
 // The fused scans (stft_scan, stft_scan64, stft_wg) keep the template signatures <.., MODE, bool U8, ..> -- and so the symbol names -- they
 // had before there was a third input format: the benchmark's PMC bookkeeping and the tools name instantiations by symbol.  int16 input
-// is MODE | kModeI16 with U8 = false.
-constexpr int kModeI16 = 16;
-__host__ __device__ constexpr int scan_fmt(int modef, bool u8) { return (modef & kModeI16) ? kFmtI16 : u8 ? kFmtU8 : kFmtC64; }
+// is MODE | kModeI16 with U8 = false, int8 input MODE | kModeI8 with U8 = false (the mask kModeI16 - 1 gives MODE back from either).
+constexpr int kModeI16 = 16, kModeI8 = 32;
+__host__ __device__ constexpr int scan_fmt(int modef, bool u8) { return (modef & kModeI8) ? kFmtI8 : (modef & kModeI16) ? kFmtI16 : u8 ? kFmtU8 : kFmtC64; }
 __host__ __device__ constexpr bool scan_dma(int r3, int fmt, int qs) { return RT_EXP_DMA1024 && r3 == 4 && fmt == kFmtC64 && qs == 0; }  // (the landing zone holds complex64)
 __device__ void raw_buffer_load_lds_fwd(rsrc_t rsrc, __attribute__((address_space(3))) void *lds, int size, int voffset, int soffset, int offset, int aux)
     __asm("llvm.amdgcn.raw.buffer.load.lds");
@@ -586,7 +621,7 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
  void stft_scan(const StftParams p) {
     constexpr int MODE = MODEF & (kModeI16 - 1);
     constexpr int FMT = scan_fmt(MODEF, U8);
-    using raw_t = typename raw_of<FMT>::type;  // (int16 input takes complex64's answer in every `U8 ? :` below: DESIGN 4.13)
+    using raw_t = typename raw_of<FMT>::type;  // (int16 and int8 input take complex64's answer in every `U8 ? :` below: DESIGN 4.13, 4.16)
     static_assert(QS == 0 || (R3 == 1 && (QS == 2 || QS == 4 || QS == 8)), "QS: lane groups of 2 / 4 / 8 lanes, R3 = 1");
     constexpr int N = QS ? 16 * QS : 256 * R3;
     constexpr int LG = QS ? QS : 16 * R3;

@@ -72,7 +72,7 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t x) {
 __device__ void raw_buffer_load_lds(rsrc_t rsrc, __attribute__((address_space(3))) void *lds, int size, int voffset, int soffset, int offset, int aux)
     __asm("llvm.amdgcn.raw.buffer.load.lds");
 
-// Quarters 0 and 1 of a segment (pieces m = 4 j and 4 j + 1: runs of two pieces, 1 KiB of complex64 / 256 B of uint8 pairs)
+// Quarters 0 and 1 of a segment (pieces m = 4 j and 4 j + 1: runs of two pieces, 1 KiB of complex64 / 256 B of uint8 or int8 pairs)
 // into a wave's area, piece (2 j + n0) at element offset 64 (2 j + n0): sixteen instructions, nothing to wait for here.
 // int16 pairs (256 B a piece): a run of two pieces is 8 bytes a lane, a size the LDS-DMA does not have (1 / 2 / 4 / 12 / 16), so an
 // instruction takes TWO runs at 16 bytes a lane -- lanes 0 .. 31 pieces 8 j, 8 j + 1, lanes 32 .. 63 pieces 8 j + 4, 8 j + 5 (the lane
@@ -136,7 +136,7 @@ __device__ __forceinline__ bool bit_of(uint32_t lo, uint32_t hi, int r) { return
 // register allocation from 2 spilled registers outside the step to 53 / 152 inside it.)
 
 
-template <int MODEF, bool U8, bool LIN>  // (MODEF: MODE, | kModeI16 for int16 input -- rt_kernels.h, scan_fmt)
+template <int MODEF, bool U8, bool LIN>  // (MODEF: MODE, | kModeI16 for int16, | kModeI8 for int8 input -- rt_kernels.h, scan_fmt)
 __global__ __launch_bounds__(kW64Block, 1) void stft_scan64(const StftParams p) {
     constexpr int MODE = MODEF & (kModeI16 - 1);
     constexpr int FMT = scan_fmt(MODEF, U8);

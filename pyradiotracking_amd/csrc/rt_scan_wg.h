@@ -131,7 +131,7 @@ __device__ __forceinline__ void wg_emit(const StftParams &p, int s, int seg, con
 // for the detrend by linearity): w[t + BLK j] = c0 + c1 cos(alpha_t + beta_j), alpha_t = 2 pi t / N (the thread's own W_N^t holds its
 // cosine and sine), beta_j = 2 pi j / 32 (constants) -- two fused multiply-adds per sample instead of a table in registers: the table's
 // 32 registers, live from the request to the multiplication, were what made the kernel spill.  Other windows keep the table (from L2).
-template <int BLK, int MODEF, bool U8, bool WCOS>  // (MODEF: MODE, | kModeI16 for int16 input -- rt_kernels.h, scan_fmt)
+template <int BLK, int MODEF, bool U8, bool WCOS>  // (MODEF: MODE, | kModeI16 for int16, | kModeI8 for int8 input -- rt_kernels.h, scan_fmt)
 __global__ __launch_bounds__(BLK, wg_half(BLK) ? 3 : (BLK == 256 ? 2 : 1)) void stft_wg(const StftParams p) {
     constexpr int MODE = MODEF & (kModeI16 - 1);
     constexpr int FMT = scan_fmt(MODEF, U8);

@@ -138,6 +138,39 @@ def i16_to_complex128(raw: np.ndarray) -> np.ndarray:
     return out
 
 
+I8_SCALE = 2.0 ** -7
+
+
+def quantize_i8(x: np.ndarray, gain: float = 1.0) -> np.ndarray:
+    """complex IQ -> 8-bit signed IQ (CS8 / sc8 / ci8): interleaved int8 (I, Q), value = rint(v*gain*128) clipped to
+    -128..127 -- the inverse of :func:`i8_to_complex64`."""
+    z = np.asarray(x, dtype=np.complex128) * gain
+    out = np.empty(z.shape + (2,), dtype=np.float64)
+    out[..., 0] = z.real
+    out[..., 1] = z.imag
+    q = np.clip(np.rint(out * 128.0), -128, 127).astype(np.int8)
+    return q.reshape(z.shape[:-1] + (2 * z.shape[-1],))
+
+
+def i8_to_complex64(raw: np.ndarray) -> np.ndarray:
+    """What the library makes of int8 pairs: component * 2**-7 in float32 -- exact (8 bits fit the 24 of a float32, the scale
+    is a power of two)."""
+    v = np.asarray(raw, dtype=np.int8).astype(np.float32) * np.float32(I8_SCALE)
+    out = np.empty(v.shape[:-1] + (v.shape[-1] // 2,), dtype=np.complex64)
+    out.real = v[..., 0::2]
+    out.imag = v[..., 1::2]
+    return out
+
+
+def i8_to_complex128(raw: np.ndarray) -> np.ndarray:
+    """The same in float64 (what a float64 handle makes of int8 pairs): exact as well."""
+    v = np.asarray(raw, dtype=np.int8).astype(np.float64) * I8_SCALE
+    out = np.empty(v.shape[:-1] + (v.shape[-1] // 2,), dtype=np.complex128)
+    out.real = v[..., 0::2]
+    out.imag = v[..., 1::2]
+    return out
+
+
 def random_pulses(
     rng: np.random.Generator,
     n_samples: int,
@@ -304,4 +337,13 @@ def quantize_i16_device(iq, gain: float = 1.0):
 
     v = torch.view_as_real(iq)  # [S, B, 2]
     q = torch.clamp(torch.round(v * (gain * 32768.0)), -32768, 32767).to(torch.int16)
+    return q.reshape(iq.shape[0], 2 * iq.shape[1]).contiguous()
+
+
+def quantize_i8_device(iq, gain: float = 1.0):
+    """``[S, B]`` complex64 CUDA tensor -> ``[S, 2*B]`` int8 (interleaved I, Q, value * 128 rounded and clipped; on device)."""
+    import torch
+
+    v = torch.view_as_real(iq)  # [S, B, 2]
+    q = torch.clamp(torch.round(v * (gain * 128.0)), -128, 127).to(torch.int8)
     return q.reshape(iq.shape[0], 2 * iq.shape[1]).contiguous()
