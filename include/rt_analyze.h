@@ -49,9 +49,9 @@ typedef enum rt_status {
     RT_E_ONE_SEGMENT = -6,  /* exactly one segment: the reference raises
                                IndexError there (analyze.py:354, times[1])      */
     RT_E_NOMEM = -7,
-    RT_E_HOT_OVERFLOW = -8  /* RT_MODE_SPARSE only: a candidate list overflowed (hot_capacity); the
-                               call produced NO result and has been dropped -- unlike RT_E_CAPACITY,
-                               which hands out a truncated result                                  */
+    RT_E_HOT_OVERFLOW = -8  /* RT_MODE_SPARSE, and a float64 handle made with RT_FLAG_F64_SPARSE, only: a candidate
+                               list overflowed (hot_capacity); the call produced NO result and has been dropped --
+                               unlike RT_E_CAPACITY, which hands out a truncated result                            */
 } rt_status;
 
 /* how the batch is analysed */
@@ -88,10 +88,11 @@ typedef struct rt_config {
     int32_t device;             /* HIP device ordinal                                    */
     int32_t n_streams;          /* S: independent streams analysed per call              */
     int32_t nperseg;            /* fft_nperseg (analyze.py:111; the reference passes any integer on to SciPy, __main__.py:59):
-                                   any size from 8 to 8192, or a power of two up to 16384.  The powers of two 256 ... 4096 run the
-                                   fused scan kernels (every rt_mode); every other size runs a general transform on the dense path
-                                   (other powers of two: radix-2 in LDS; the rest: Bluestein's algorithm on it) -- RT_MODE_AUTO or
-                                   RT_MODE_DENSE only, 16 bytes of traffic per sample; anything else: RT_E_UNSUPPORTED */
+                                   any size from 8 to 8192, or a power of two up to 16384.  The powers of two 32 ... 16384 run the
+                                   fused scan kernels (every rt_mode up to 4096; 8192 and 16384: RT_MODE_AUTO, RT_MODE_SPARSE and
+                                   RT_MODE_DENSE); every other size runs a general transform on the dense path (8 and 16: radix-2
+                                   in LDS; the rest: Bluestein's algorithm on it) -- RT_MODE_AUTO or RT_MODE_DENSE only, 16 bytes of
+                                   traffic per sample; anything else: RT_E_UNSUPPORTED */
     int32_t mode;               /* rt_mode                                               */
     int64_t max_samples;        /* largest per-stream buffer length B accepted           */
     double sample_rate;         /* fs (analyze.py:101)                                   */
@@ -137,6 +138,7 @@ typedef struct rt_config {
 #define RT_FLAG_NO_GROUP_DETECT 8u /* ... never */
 #define RT_FLAG_ROW_MEANS 16u      /* keep each call's row means for rt_fetch_row_means[_f64] (rt_create and rt_create_f64) */
 #define RT_FLAG_RECORD_CELLS 32u   /* keep the cells of every record of a call for rt_fetch_record_cells[_f64] (rt_create and rt_create_f64) */
+#define RT_FLAG_F64_SPARSE 64u     /* rt_create_f64 only (rt_create: RT_E_INVALID): the map-free float64 path, see "float64 handles" below */
 
 /*
  * One extracted plateau, before it becomes a Signal (analyze.py:442-449).
@@ -329,8 +331,23 @@ const char *rt_last_error(rt_handle *h);
  * pyrtlsdr delivers complex128 buffers and the reference then runs the whole path in float64 (SciPy keeps the input
  * dtype; thresholds and statistics are Python floats).  A handle made by rt_create_f64 does the same on the
  * GPU: the dense map in double precision, thresholds and statistics in float64.  Its limits:
- *   - dense path only: RT_MODE_AUTO means dense (rt_call_info.mode_used = RT_MODE_DENSE); RT_MODE_SPARSE,
- *     RT_MODE_PREFILTER and RT_MODE_RUNFILTER are RT_E_UNSUPPORTED;
+ *   - rt_config.mode selects the dense path only: RT_MODE_AUTO means dense (rt_call_info.mode_used = RT_MODE_DENSE);
+ *     RT_MODE_SPARSE, RT_MODE_PREFILTER and RT_MODE_RUNFILTER are RT_E_UNSUPPORTED.  The map-free path is opt-in by flag:
+ *     RT_FLAG_F64_SPARSE (with RT_MODE_AUTO; any other mode: RT_E_INVALID) runs every call through a fused scan that
+ *     transforms, sums the rows, keeps the look-back tail and emits only candidate cells (a cell not below the stream's
+ *     absolute threshold, NaN included, or whose successor in time is one), and a detection that works from those lists:
+ *     rt_call_info.mode_used = RT_MODE_SPARSE, no n_streams * T * nperseg * 8 byte map is allocated, the records are the
+ *     dense path's (keys and verdicts; figures within float64 round-off of another summation order).  nperseg: a power of
+ *     two 32 ... 4096 (else RT_E_UNSUPPORTED); max_samples / nperseg <= 2^20; not with RT_FLAG_RECORD_CELLS
+ *     (RT_E_UNSUPPORTED).  On such a handle rt_config.hot_capacity counts candidate cells per stream and call: 0 = 4096,
+ *     else 1024 ... 8192 (what one workgroup sorts in LDS; outside: RT_E_INVALID); a stream that emits more ends the call
+ *     as RT_MODE_SPARSE does on a float32 handle -- rt_fetch_f64 returns RT_E_HOT_OVERFLOW, delivers nothing and consumes
+ *     the call, whose look-back tail stays the next call's; there is no map to fall back to (create a dense handle).
+ *     rt_config.segs_per_chunk: segments of one stream a scan workgroup walks (0 = a default from the geometry); it sets
+ *     the order of the row sums' partial sums, nothing else.  Everything listed below keeps its meaning, the four input
+ *     formats, rt_set_present, rt_set_stream_params_f64 (the emission uses the stream's own threshold),
+ *     rt_set_stream_settings_f64 and RT_FLAG_ROW_MEANS (every row's mean from the scan's sums) included; rt_extract_f64 and
+ *     rt_spectrogram_f64 work on caller-supplied memory and are unchanged;
  *   - nperseg 8 ... 4096, or a power of two up to 8192 (a segment's transform in LDS: Bluestein's padded length M <= 8192
  *     complex doubles = 128 KiB); anything else is RT_E_UNSUPPORTED;
  *   - cfg->lanes must be 0 or 1 (RT_E_UNSUPPORTED otherwise): one launch sequence per call;

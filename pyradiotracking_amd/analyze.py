@@ -293,6 +293,7 @@ class BatchSignalAnalyzer:
         precision: str = "float32",
         row_means: bool = False,
         record_cells: bool = False,
+        f64_sparse: bool = False,
         **kwargs,
     ):
         """``record_cells`` (``RT_FLAG_RECORD_CELLS``): keep the spectrogram cells every record of a call consists of -- the
@@ -308,6 +309,12 @@ class BatchSignalAnalyzer:
         4096 or a power of two up to 8192, one lane; ``enqueue`` takes complex128 device tensors, host complex arrays
         (complex64 widened exactly) and uint8 (converted as pyrtlsdr does, in float64); ``fetch_records`` returns
         ``RECORD_F64_DTYPE``.
+
+        ``f64_sparse`` (``RT_FLAG_F64_SPARSE``; needs ``precision="float64"``, ``mode="auto"`` and no ``record_cells``, else
+        ``ValueError``): the float64 analyzer without its float64 map -- a fused scan emits only candidate cells and the
+        detection works from those lists; nperseg a power of two 32 ... 4096.  ``hot_capacity`` then
+        counts candidate cells per stream and call (0: 4096; 1024 ... 8192); a stream that emits more makes
+        ``fetch_records`` raise ``RT_E_HOT_OVERFLOW`` for that call.  ``segs_per_chunk``: segments a scan workgroup walks.
 
         ``mode`` (``rt_config.mode``): ``"auto"`` (default) analyses on the fused sparse path and, when an input's noise
         crosses the thresholds, climbs by itself -- chunk-bit pre-filter, exact SNR-aware pre-filter, dense spectrogram; the
@@ -354,6 +361,14 @@ class BatchSignalAnalyzer:
             raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
         self.precision = precision
         f64 = precision == "float64"
+        if f64_sparse:
+            if not f64:
+                raise ValueError("f64_sparse needs precision='float64'")
+            if mode != "auto":
+                raise ValueError("f64_sparse selects the path by itself: mode must be 'auto'")
+            if record_cells:
+                raise ValueError("f64_sparse keeps no map: record_cells is not available with it")
+        self.f64_sparse = bool(f64_sparse)
         per_stream_cal = None
         if np.ndim(calibration_db):
             per_stream_cal = [float(c) for c in calibration_db]
@@ -415,6 +430,7 @@ class BatchSignalAnalyzer:
             precision=precision,
             row_means=bool(row_means),
             record_cells=bool(record_cells),
+            f64_sparse=self.f64_sparse,
         )
         if per_stream_cal is not None or per_thr is not None:
             n = len(self.devices)
@@ -785,12 +801,14 @@ class SignalAnalyzer:
         precision: str = "float32",
         row_means: bool = False,
         record_cells: bool = False,
+        f64_sparse: bool = False,
         **kwargs,
     ):
         """``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
 
-        ``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer).
+        ``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer);
+        ``f64_sparse=True`` with it: on the map-free float64 path (same ``Signal``s).
         ``row_means=True``: after every buffer ``noise_dbw`` holds the noise level of every bin (``[fft_nperseg]``, dBW, fftfreq
         order) -- what the reference prints as the ``noise`` of a Signal (analyze.py:446), for all bins."""
         self.device = device
@@ -849,6 +867,7 @@ class SignalAnalyzer:
             precision=precision,
             row_means=self.row_means,
             record_cells=self.record_cells,
+            f64_sparse=bool(f64_sparse),
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
             **{k: kwargs[k] for k in ("record_capacity", "record_pool", "hot_capacity", "group_detect") if k in kwargs},
         )

@@ -31,6 +31,7 @@
 #include "rt_kernels.h"
 #include "rt_general.h"
 #include "rt_f64.h"
+#include "rt_f64_sparse.h"
 #include "rt_cells.h"
 #include "rt_present.h"
 #include "rt_tables.h"
@@ -186,6 +187,11 @@ struct F64Slot {
     bool masked = false;
     int32_t *h_mask = nullptr, *d_mask = nullptr;
     int n_absent = 0;
+    // RT_FLAG_F64_SPARSE only: the call's candidate lists (rt_f64_sparse.h)
+    uint32_t *d_keys = nullptr;    // [S][hot_cap]
+    double *d_vals = nullptr;      // [S][hot_cap]
+    int32_t *d_cell_count = nullptr;  // [S], zero between calls
+    int32_t *h_hot = nullptr;      // pinned, device-visible: [S] cells each stream emitted
     hipEvent_t ev_done = nullptr;
 };
 struct F64State {
@@ -210,6 +216,11 @@ struct F64State {
     bool cells_full = false;  // ... and that call was delivered in full (rt_fetch_record_cells_f64)
     int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
     PresenceBook pres;        // rt_set_present: per-stream segment counts and the mask in force (inactive until the entry is called)
+    // RT_FLAG_F64_SPARSE: no d_map; the scan's chunk geometry, the partial row sums (rewritten by every call) and the folded sums
+    bool sparse = false;
+    int group = 1, chunk = 1, chunk_cap = 0, hot_cap = 0, sort_cap = 0;
+    double *d_partial = nullptr;   // [S][chunk_cap][N]
+    double *d_row_sums = nullptr;  // [S][N]
 };
 
 }  // namespace
@@ -1489,6 +1500,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     const int R3 = fam.R3, QS = fam.QS, big = fam.big;
     const bool general = fam.general, bluestein = fam.bluestein;
     if (cfg->mode < RT_MODE_AUTO || cfg->mode > RT_MODE_RUNFILTER) return fail_create(RT_E_INVALID, "bad mode");
+    if (cfg->flags & RT_FLAG_F64_SPARSE) return fail_create(RT_E_INVALID, "RT_FLAG_F64_SPARSE is a flag of float64 handles (rt_create_f64)");
     if (general && cfg->mode != RT_MODE_AUTO && cfg->mode != RT_MODE_DENSE)
         return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(cfg->nperseg) + " runs on the dense path only: mode must be RT_MODE_AUTO or RT_MODE_DENSE");
     if (big && (cfg->mode == RT_MODE_PREFILTER || cfg->mode == RT_MODE_RUNFILTER))
@@ -3040,8 +3052,83 @@ F64DetectArgs f64_detect_args(rt_handle *h, F64Slot &sl) {
 }
 
 // the call's kernels on the handle's stream: the transform (not for rt_extract_f64), detection, records, then the call's event
+template <int FMT>
+void launch_scan_f64(const F64ScanParams &p, int nb, unsigned grid, size_t lds, hipStream_t st) {
+    if (nb == 4) scan_f64<FMT, 4><<<grid, kF64ScanBlock, lds, st>>>(p);
+    else if (nb == 8) scan_f64<FMT, 8><<<grid, kF64ScanBlock, lds, st>>>(p);
+    else scan_f64<FMT, 16><<<grid, kF64ScanBlock, lds, st>>>(p);
+}
+size_t f64_scan_lds(const F64State *f) { return (size_t)16 * f->N * (f->group + 1); }
+size_t f64_sort_lds(const F64State *f) { return (size_t)f->sort_cap * (sizeof(double) + sizeof(uint32_t)); }
+
+// RT_FLAG_F64_SPARSE: the call's kernels -- the fused scan, detection from the lists, records, the counters back to zero
+int f64_enqueue_sparse(rt_handle *h, F64Slot &sl) {
+    F64State *f = h->f64;
+    const int S = h->cfg.n_streams;
+    hipStream_t st = h->s_scan;
+    const int n_chunks = f64_sparse_chunks(sl.n_seg, f->chunk);
+    if (sl.n_seg > 0) {
+        F64ScanParams p{};
+        p.iq = sl.iq;
+        p.stream_stride = sl.stream_stride;
+        p.n_streams = S;
+        p.n_seg = sl.n_seg;
+        p.nperseg = f->N;
+        p.group = f->group;
+        p.chunk = f->chunk;
+        p.n_chunks = n_chunks;
+        p.chunk_cap = f->chunk_cap;
+        p.tail_cols = f->K;
+        p.hot_cap = f->hot_cap;
+        p.scale = f->c.scale;
+        p.thr = f->c.threshold;
+        p.thr_s = f->d_thr_s;
+        p.window = f->d_window;
+        p.tw = f->d_tw;
+        p.tail = f->d_tail[sl.tail_write];
+        p.absent = sl.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr;
+        p.partial = f->d_partial;
+        p.keys = sl.d_keys;
+        p.vals = sl.d_vals;
+        p.count = sl.d_cell_count;
+        const unsigned grid = (unsigned)((int64_t)S * n_chunks);
+        const int nb = f->N * f->group / kF64ScanBlock;
+        const size_t lds = f64_scan_lds(f);
+        if (sl.fmt == kFmtU8) launch_scan_f64<kFmtU8>(p, nb, grid, lds, st);
+        else if (sl.fmt == kFmtI16) launch_scan_f64<kFmtI16>(p, nb, grid, lds, st);
+        else if (sl.fmt == kFmtI8) launch_scan_f64<kFmtI8>(p, nb, grid, lds, st);
+        else launch_scan_f64<kFmtC64>(p, nb, grid, lds, st);
+        RT_HIP(h, hipGetLastError());
+    }
+    F64SparseArgs sa{};
+    sa.a = f64_detect_args(h, sl);
+    sa.a.spec = nullptr;
+    sa.partial = f->d_partial;
+    sa.n_chunks = n_chunks;
+    sa.chunk_cap = f->chunk_cap;
+    sa.row_sums = f->d_row_sums;
+    sa.keys = sl.d_keys;
+    sa.vals = sl.d_vals;
+    sa.count = sl.d_cell_count;
+    sa.hot_cap = f->hot_cap;
+    sa.sort_cap = f->sort_cap;
+    sa.hot_out = sl.h_hot;
+    if (sl.d_row_means) {
+        sa.a.row_means = sl.d_row_means;
+        detect_sparse_f64<true><<<(unsigned)S, 256, f64_sort_lds(f), st>>>(sa);
+    } else {
+        detect_sparse_f64<false><<<(unsigned)S, 256, f64_sort_lds(f), st>>>(sa);
+    }
+    finalize_sparse_f64<<<(unsigned)S, 256, 0, st>>>(sa.a);
+    clear_counts_sparse_f64<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(sl.d_raw_count, sl.d_cell_count, S);
+    RT_HIP(h, hipGetLastError());
+    RT_HIP(h, hipEventRecord(sl.ev_done, st));
+    return RT_OK;
+}
+
 int f64_enqueue(rt_handle *h, F64Slot &sl) {
     F64State *f = h->f64;
+    if (f->sparse && !sl.is_extract) return f64_enqueue_sparse(h, sl);
     const int S = h->cfg.n_streams;
     hipStream_t st = h->s_scan;
     if (!sl.is_extract && sl.n_seg > 0) {
@@ -3152,8 +3239,14 @@ static void destroy_f64(rt_handle *h) {
         (void)hipFree(sl.d_stream_cells);
         (void)hipFree(sl.d_stream_base);
         (void)hipHostFree(sl.h_cells_info);
+        (void)hipFree(sl.d_keys);
+        (void)hipFree(sl.d_vals);
+        (void)hipFree(sl.d_cell_count);
+        (void)hipHostFree(sl.h_hot);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     }
+    (void)hipFree(f->d_partial);
+    (void)hipFree(f->d_row_sums);
     (void)hipFree(f->d_window);
     (void)hipFree(f->d_cwin);
     (void)hipFree(f->d_bfilt);
@@ -3271,9 +3364,23 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     if (n < 8 || (pow2 && n > kF64MaxM) || (!pow2 && n > kF64MaxN))
         return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(n) + " is not supported by a float64 handle: 8 ... 4096, or a power of two up to 8192");
     if (cfg->mode < RT_MODE_AUTO || cfg->mode > RT_MODE_RUNFILTER) return fail_create(RT_E_INVALID, "bad mode");
+    const bool sparse = (cfg->flags & RT_FLAG_F64_SPARSE) != 0;
+    if (sparse && cfg->mode != RT_MODE_AUTO)
+        return fail_create(RT_E_INVALID, "RT_FLAG_F64_SPARSE on a float64 handle selects the path by itself: mode must be RT_MODE_AUTO");
     if (cfg->mode != RT_MODE_AUTO && cfg->mode != RT_MODE_DENSE)
         return fail_create(RT_E_UNSUPPORTED, "a float64 handle runs the dense path only: mode must be RT_MODE_AUTO or RT_MODE_DENSE");
     if (cfg->lanes > 1) return fail_create(RT_E_UNSUPPORTED, "a float64 handle has one launch sequence per call: lanes must be 0 or 1");
+    if (sparse) {  // the map-free path (rt_f64_sparse.h): its own limits, the arithmetic in rt_core.h
+        if (!f64_sparse_nperseg_ok(n))
+            return fail_create(RT_E_UNSUPPORTED, "RT_FLAG_F64_SPARSE: fft_nperseg " + std::to_string(n) + " has no map-free float64 path (a power of two, 32 ... 4096)");
+        if (cfg->flags & RT_FLAG_RECORD_CELLS)
+            return fail_create(RT_E_UNSUPPORTED, "RT_FLAG_F64_SPARSE with RT_FLAG_RECORD_CELLS: a float64 handle without a map keeps no record cells");
+        if (f64_sparse_hot_capacity(cfg->hot_capacity) < 0)
+            return fail_create(RT_E_INVALID, "RT_FLAG_F64_SPARSE on a float64 handle: hot_capacity must be 0 or 1024 ... 8192 cells per stream");
+        if (cfg->segs_per_chunk < 0) return fail_create(RT_E_INVALID, "RT_FLAG_F64_SPARSE on a float64 handle: segs_per_chunk must not be negative");
+        if (cfg->max_samples / n > kF64KeyMaxSeg)
+            return fail_create(RT_E_UNSUPPORTED, "RT_FLAG_F64_SPARSE on a float64 handle: max_samples / fft_nperseg exceeds 2^20 segments (the cell keys)");
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1)
@@ -3308,6 +3415,15 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     f->rec_cap = cfg->record_capacity > 0 ? cfg->record_capacity : 1024;
     f->reset_pending.assign((size_t)cfg->n_streams, 0);
     const size_t S = (size_t)cfg->n_streams;
+    if (sparse) {
+        f->sparse = true;
+        h->cfg.mode = RT_MODE_SPARSE;
+        f->group = f64_sparse_group(n);
+        f->chunk = f64_sparse_chunk(n, cfg->segs_per_chunk, cfg->n_streams, f->max_seg);
+        f->chunk_cap = std::max(1, f64_sparse_chunks(f->max_seg, f->chunk));
+        f->hot_cap = f64_sparse_hot_capacity(cfg->hot_capacity);
+        f->sort_cap = next_pow2(f->hot_cap);
+    }
 #define RT_F64_CREATE(expr)                                                               \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
@@ -3344,8 +3460,24 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
                              (const void *)stft_f64<kFmtI8, false>, (const void *)stft_f64<kFmtI8, true>};
         for (const void *fn : fns) RT_F64_CREATE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
-    // the float64 map (S T N 8 bytes) and the look-back tails
-    RT_F64_CREATE(hipMalloc(&f->d_map, std::max<size_t>(8, S * (size_t)f->max_seg * (size_t)n * sizeof(double))));
+    // the float64 map (S T N 8 bytes) and the look-back tails; RT_FLAG_F64_SPARSE: no map (rt_extract_f64 and rt_spectrogram_f64
+    // work on the caller's memory), the per-chunk row sums instead
+    if (f->sparse) {
+        const void *scans[] = {(const void *)scan_f64<kFmtC64, 4>, (const void *)scan_f64<kFmtC64, 8>, (const void *)scan_f64<kFmtC64, 16>,
+                               (const void *)scan_f64<kFmtU8, 4>,  (const void *)scan_f64<kFmtU8, 8>,  (const void *)scan_f64<kFmtU8, 16>,
+                               (const void *)scan_f64<kFmtI16, 4>, (const void *)scan_f64<kFmtI16, 8>, (const void *)scan_f64<kFmtI16, 16>,
+                               (const void *)scan_f64<kFmtI8, 4>,  (const void *)scan_f64<kFmtI8, 8>,  (const void *)scan_f64<kFmtI8, 16>};
+        if (f64_scan_lds(f) > 64 * 1024)
+            for (const void *fn : scans) RT_F64_CREATE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f64_scan_lds(f)));
+        if (f64_sort_lds(f) > 64 * 1024) {
+            RT_F64_CREATE(hipFuncSetAttribute((const void *)detect_sparse_f64<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f64_sort_lds(f)));
+            RT_F64_CREATE(hipFuncSetAttribute((const void *)detect_sparse_f64<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f64_sort_lds(f)));
+        }
+        RT_F64_CREATE(hipMalloc(&f->d_partial, S * (size_t)f->chunk_cap * (size_t)n * sizeof(double)));
+        RT_F64_CREATE(hipMalloc(&f->d_row_sums, S * (size_t)n * sizeof(double)));
+    } else {
+        RT_F64_CREATE(hipMalloc(&f->d_map, std::max<size_t>(8, S * (size_t)f->max_seg * (size_t)n * sizeof(double))));
+    }
     for (double *&t : f->d_tail) {
         RT_DEVICE_ZEROS(RT_F64_CREATE, t, S * (size_t)f->K * (size_t)n * sizeof(double));
     }
@@ -3361,6 +3493,12 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
             RT_F64_CREATE(hipMalloc(&sl.d_stream_base, S * sizeof(long long)));
             RT_F64_CREATE(hipHostMalloc(&sl.h_cells_info, 2 * sizeof(unsigned long long)));
             sl.h_cells_info[0] = sl.h_cells_info[1] = 0ull;
+        }
+        if (f->sparse) {
+            RT_F64_CREATE(hipMalloc(&sl.d_keys, S * (size_t)f->hot_cap * sizeof(uint32_t)));
+            RT_F64_CREATE(hipMalloc(&sl.d_vals, S * (size_t)f->hot_cap * sizeof(double)));
+            RT_DEVICE_ZEROS(RT_F64_CREATE, sl.d_cell_count, S * sizeof(int32_t));
+            RT_F64_CREATE(hipHostMalloc(&sl.h_hot, S * sizeof(int32_t)));
         }
         RT_F64_CREATE(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
         if (f64_slot_areas(h, sl, f->rec_cap) != RT_OK) {
@@ -3485,6 +3623,18 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     const int S = h->cfg.n_streams;
     RT_HIP(h, hipSetDevice(h->cfg.device));
     RT_HIP(h, hipEventSynchronize(sl.ev_done));
+    const bool sparse_call = f->sparse && !sl.is_extract;
+    if (sparse_call) {
+        // RT_FLAG_F64_SPARSE: a stream emitted more cells than its list holds -- no result, the call is consumed (as
+        // RT_MODE_SPARSE on a float32 handle); the look-back tail the call wrote stays the next call's
+        for (int s = 0; s < S; ++s)
+            if (sl.h_hot[s] > f->hot_cap) {
+                sl.pending = false;
+                f->rm_slot = kRowMeansNone;
+                return f64_err(h, RT_E_HOT_OVERFLOW, "candidate-cell capacity exceeded (hot_capacity) on a float64 handle: stream " + std::to_string(s) +
+                                                         " emitted " + std::to_string(sl.h_hot[s]) + " cells");
+            }
+    }
     bool truncated = false;
     for (;;) {
         int wanted = 0;
@@ -3528,7 +3678,7 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     *n_out = total;
     h->info = rt_call_info{};
     h->info.n_seg = sl.n_seg;
-    h->info.mode_used = RT_MODE_DENSE;
+    h->info.mode_used = sparse_call ? RT_MODE_SPARSE : RT_MODE_DENSE;
     h->info.n_records = (int64_t)total;
     if (total && (!out || !cap)) return truncated ? RT_E_CAPACITY : RT_OK;  // size query: the call stays pending
     const size_t n = std::min(total, cap);

@@ -319,6 +319,42 @@ inline int choose_chunk(int nperseg, int R3, int QS, int block, double fs, doubl
     return L;
 }
 
+// ---- The map-free float64 path (RT_FLAG_F64_SPARSE; kernels: rt_f64_sparse.h; host side here so that the CPU suite can test it) ----
+// A candidate cell's key: the bin above the segment, so that the unsigned order of the keys is the (bin, segment) order the
+// detection sorts by.  20 bits of segment: a handle's max_samples / nperseg may not exceed kF64KeyMaxSeg; 12 bits of bin: nperseg
+// up to 4096.
+constexpr int kF64KeySegBits = 20;
+constexpr int kF64KeyMaxSeg = 1 << kF64KeySegBits;
+constexpr int kF64SparseMinN = 32, kF64SparseMaxN = 4096;
+constexpr int kF64ScanBlock = 256;  // threads of a scan_f64 workgroup
+RT_HD uint32_t f64_cell_key(int32_t fi, int32_t t) { return ((uint32_t)fi << kF64KeySegBits) | (uint32_t)t; }
+RT_HD int32_t f64_key_bin(uint32_t key) { return (int32_t)(key >> kF64KeySegBits); }
+RT_HD int32_t f64_key_seg(uint32_t key) { return (int32_t)(key & (uint32_t)(kF64KeyMaxSeg - 1)); }
+inline bool f64_sparse_nperseg_ok(int n) { return n >= kF64SparseMinN && n <= kF64SparseMaxN && (n & (n - 1)) == 0; }
+// rt_config.hot_capacity on such a handle: candidate cells per stream and call, what one workgroup sorts in LDS (12 bytes a cell:
+// 8192 cells = 96 KiB).  0 = the default, 4096 (a full column of NaN cells at nperseg 2048 with its predecessor column; 48 KiB of
+// LDS, so that three streams' detections share a CU); out of range: -1 (RT_E_INVALID).
+constexpr int kF64HotMin = 1024, kF64HotMax = 8192, kF64HotDefault = 4096;
+inline int f64_sparse_hot_capacity(int hot_capacity) {
+    if (hot_capacity == 0) return kF64HotDefault;
+    return (hot_capacity < kF64HotMin || hot_capacity > kF64HotMax) ? -1 : hot_capacity;
+}
+// Segments a scan_f64 workgroup transforms side by side: 1024 samples' worth, at most 32 (nperseg 32: 8 threads a segment)
+inline int f64_sparse_group(int nperseg) { return std::max(1, std::min(32, 1024 / nperseg)); }
+// Segments per chunk (L): rt_config.segs_per_chunk where set.  Else L + 1 (the chunk and its halo segment) is a whole number of
+// groups -- 32 segments or eight groups, whichever is more, so the halo costs 3 % at most -- halved while the handle's largest call
+// has fewer than 2048 workgroups.  L is fixed when the handle is made (from max_samples), not per call: it sets the order in which
+// a row's partial sums are added.
+inline int f64_sparse_chunk(int nperseg, int segs_per_chunk, int n_streams, int max_seg) {
+    if (segs_per_chunk > 0) return segs_per_chunk;
+    const int g = f64_sparse_group(nperseg);
+    int l1 = std::max(32, 8 * g);
+    while (l1 > std::max(4, g) && (int64_t)n_streams * ((max_seg + l1 - 2) / (l1 - 1)) < 2048) l1 >>= 1;
+    return l1 - 1;
+}
+inline int f64_sparse_chunks(int n_seg, int L) { return n_seg <= 0 ? 0 : (n_seg + L - 1) / L; }
+inline int f64_sparse_last_chunk(int n_seg, int L) { return n_seg <= 0 ? 0 : n_seg - (f64_sparse_chunks(n_seg, L) - 1) * L; }
+
 // ---- Streams that sit out a call (rt_set_present; host side of rt_analyze.hip, here so that the CPU suite can drive it) ----
 // In the reference every SDR is a SignalAnalyzer of its own: `_spectrogram_last` is the buffer ITS radio delivered before, whatever
 // the other radios did meanwhile.  A handle keeps three look-back tails in rotation for all streams in lock-step (call k reads
@@ -657,6 +693,28 @@ RT_HD void rank_and_shadow(int32_t i, int32_t n, const Rec *rec, const long long
     }
     *rank_out = rank;
     *shadow_out = shadow;
+}
+
+// ---- records from a float64 cell list (RT_FLAG_F64_SPARSE: detect_sparse_f64 in rt_f64_sparse.h, hc_extract_sparse_f64) ----
+// A stream's list holds every cell at or above the absolute threshold (NaN included) and every cell whose successor in time is
+// one (the scan's emission rule), so a cell that is missing is below the threshold.  Sorted by key (f64_cell_key), the cells
+// [start, end) of a plateau that lie in this buffer are neighbours in the list: the run's cells are above, the one before it
+// has a hot successor.
+// Entry j of the sorted list (keys(j), vals(j); n entries): does a maximal run of above-cells begin on it?  Then [*b, *e).
+template <class Keys, class Vals>
+RT_HD bool sparse_run_at(const DetectParamsT<double> &p, Keys keys, Vals vals, int32_t n, int32_t j, double avg, int32_t *b, int32_t *e) {
+    const uint32_t key = keys(j);
+    const int32_t t = f64_key_seg(key);
+    if (!cell_above(vals(j), avg, p.thr, p.snr)) return false;
+    if (t > 0 && j > 0 && keys(j - 1) == key - 1u && cell_above(vals(j - 1), avg, p.thr, p.snr)) return false;  // inside a run
+    int32_t jj = j, tt = t;
+    while (jj + 1 < n && tt + 1 < p.n_seg && keys(jj + 1) == keys(jj) + 1u && cell_above(vals(jj + 1), avg, p.thr, p.snr)) {
+        ++jj;
+        ++tt;
+    }
+    *b = t;
+    *e = tt + 1;
+    return true;
 }
 
 // ---- exact run-length pre-filter: the planner's arithmetic (rt_kernels.h: plan_runs; host copy in rt_hostcheck.cpp) ----

@@ -7,8 +7,10 @@
 // kernels, without a GPU.
 // It is NOT a fallback: the product library (rt_analyze.hip) never links or
 // loads this file, and there is no STFT here at all.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "../../include/rt_analyze.h"
@@ -347,5 +349,86 @@ void hc_presence_state(void *h, int32_t *n_seg_last, uint8_t *reset_pending, uin
     std::memcpy(reset_pending, p->reset_pending.data(), p->reset_pending.size());
     std::memcpy(present, p->book.present.data(), p->book.present.size());
 }
+
+}  // extern "C"
+
+// ---- the map-free float64 path (RT_FLAG_F64_SPARSE; rt_core.h, kernels in rt_f64_sparse.h) ----
+extern "C" {
+
+// The sequential twin of detect_sparse_f64 + finalize_sparse_f64 for ONE stream: records from a cell list.  keys[n] / vals[n]:
+// the stream's candidate cells (f64_cell_key, power) in any order; row_sums[n_bins]: every row's float64 sum; last /
+// n_seg_last / tail_cols as in hc_extract_f64.  Returns the number of records (written up to cap, ordered by (fi, start)).
+int hc_extract_sparse_f64(const uint32_t *keys_in, const double *vals_in, int n, const double *row_sums, int n_seg, int n_bins,
+                          const double *last, int n_seg_last, int tail_cols, int nperseg, double fs, double thr, double snr,
+                          double cal_db, double min_d, double max_d, rt_record_f64 *out, int cap) {
+    DetectParams64 p;
+    p.n_seg = n_seg;
+    p.n_seg_last = last ? n_seg_last : -1;
+    p.tail_cols = last ? tail_cols : 0;
+    p.stride = probe_stride(nperseg, fs, min_d);
+    p.nperseg = nperseg;
+    p.thr = thr;
+    p.snr = snr;
+    p.cal_db = cal_db;
+    p.fs = fs;
+    p.min_d = min_d;
+    p.max_d = max_d;
+    std::vector<int> order((size_t)n);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return keys_in[a] < keys_in[b]; });
+    auto keys = [&](int j) -> uint32_t { return keys_in[order[(size_t)j]]; };
+    auto vals = [&](int j) -> double { return vals_in[order[(size_t)j]]; };
+    std::vector<rt_record_f64> rec;
+    std::vector<long long> ts, du;
+    for (int j = 0; j < n; ++j) {
+        const int fi = f64_key_bin(keys(j));
+        if (fi >= n_bins) continue;
+        const double avg = row_mean_of(row_sums[fi], n_seg, double());
+        int b, e, start;
+        if (!sparse_run_at(p, keys, vals, n, j, avg, &b, &e)) continue;
+        auto prev = [&](int d) -> double { return last[(size_t)(n_seg_last - d) * n_bins + fi]; };
+        if (!gate_run(p, b, e, avg, prev, &start)) continue;
+        const int at0 = j - b;  // the list entry of the bin's segment 0, were it there
+        auto cell = [&](int32_t k) -> double {
+            const int32_t t = start + k;
+            return t < 0 ? prev(-t) : vals(at0 + t);
+        };
+        const RunStatsT<double> st = run_stats(e - start, cell);
+        rt_record_f64 r;
+        std::memset(&r, 0, sizeof r);
+        r.fi = fi;
+        r.start = start;
+        r.end = e;
+        r.max_p = st.max_p;
+        r.mean_p = st.mean_p;
+        r.std_db = st.std_db;
+        r.row_mean = avg;
+        rec.push_back(r);
+        ts.push_back(timedelta_us(start_time(p, start)));
+        du.push_back(timedelta_us(run_duration(p, start, e)));
+    }
+    const int m = (int)rec.size();
+    std::vector<rt_record_f64> ordered((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        int rank, shadow;
+        rank_and_shadow(i, m, rec.data(), ts.data(), du.data(), cal_db, &rank, &shadow);
+        ordered[(size_t)rank] = rec[(size_t)i];
+        ordered[(size_t)rank].shadowed = shadow;
+    }
+    for (int i = 0; i < m && i < cap; ++i) out[i] = ordered[(size_t)i];
+    return m;
+}
+
+// the geometry rt_create_f64 derives for such a handle
+unsigned hc_f64_cell_key(int fi, int t) { return f64_cell_key(fi, t); }
+int hc_f64_key_bin(unsigned key) { return f64_key_bin(key); }
+int hc_f64_key_seg(unsigned key) { return f64_key_seg(key); }
+int hc_f64_key_max_seg(void) { return kF64KeyMaxSeg; }
+int hc_f64_sparse_nperseg_ok(int n) { return f64_sparse_nperseg_ok(n) ? 1 : 0; }
+int hc_f64_sparse_hot_capacity(int hot_capacity) { return f64_sparse_hot_capacity(hot_capacity); }
+int hc_f64_sparse_group(int nperseg) { return f64_sparse_group(nperseg); }
+int hc_f64_sparse_chunk(int nperseg, int segs_per_chunk, int n_streams, int max_seg) { return f64_sparse_chunk(nperseg, segs_per_chunk, n_streams, max_seg); }
+int hc_f64_sparse_chunks(int n_seg, int L) { return f64_sparse_chunks(n_seg, L); }
+int hc_f64_sparse_last_chunk(int n_seg, int L) { return f64_sparse_last_chunk(n_seg, L); }
 
 }  // extern "C"
