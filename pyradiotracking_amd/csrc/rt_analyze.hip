@@ -2647,6 +2647,7 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
     int truncated = RT_OK;
     size_t total = 0;
     int failed = RT_OK;
+    std::vector<size_t> lane_records;  // what every lane holds for this call
     for (rt_handle *k : h->kids) {
         size_t n = 0;
         const int rc = fetch_one(k, nullptr, 0, &n, true);
@@ -2655,6 +2656,7 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
             failed = (rc == kCallFailed) ? RT_E_HOT_OVERFLOW : (rc == kCallFailedInternal) ? RT_E_HIP : rc;
         }
         total += n;
+        lane_records.push_back(n);
     }
     if (failed != RT_OK) {
         // one lane has no result for this call: the call is dropped in every lane, so that the lanes stay in step
@@ -2669,9 +2671,10 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
     size_t w = 0;
     for (size_t i = 0; i < h->kids.size(); ++i) {
         rt_handle *k = h->kids[i];
-        if (deliver && total && cap <= w) {
+        if (deliver && total && cap <= w && lane_records[i]) {
             // the caller's buffer is full: this lane's records are lost, but the call is consumed here as in the
-            // lanes before it -- otherwise the lanes would be out of step from the next rt_fetch on
+            // lanes before it -- otherwise the lanes would be out of step from the next rt_fetch on.  (A lane WITHOUT records
+            // behind a buffer of exactly the call's size loses nothing: it is delivered in full below, and its cells stand.)
             if (const Slot *o = oldest_pending(k)) keep_row_means(k, *o);  // (delivered, if not in full: its row means stand)
             k->cells_full = false;
             discard_oldest(k);

@@ -7,7 +7,12 @@ summary.  usage: soak_parity.py [--long] [seconds] [seed]
 --long: 4 .. 9 consecutive buffers per case instead of 2 .. 3, ragged lengths in two thirds of the cases instead of a third.  Three
 look-back tails rotate, so only from the fourth call on does a scan write a tail that was written before
 (tests/test_gpu_sequences.py).  The option's draws come from a random stream of their own, behind all others: without it every
-recorded (seed, case) is the case it was."""
+recorded (seed, case) is the case it was.
+
+SOAK_FEATURES=1 (its own random stream as well, ``default_rng([seed, case, 19])``): a third of the cases that are not uint8 are fed
+as int16 or int8 (the oracle sees the conversion, the threshold is raised as for uint8); 40 % have a random presence table
+(``set_present`` ahead of every buffer, the absent rows poisoned; the stream's oracle is simply not called, as in
+tests/combo_cases.py: ``oracle_run``); 40 % have the SNR threshold, the duration gates and the absolute threshold drawn per stream."""
 import datetime
 import os
 import sys
@@ -98,7 +103,15 @@ while time.time() < t_end:
         vary_len = vary_len or bool(rng_long.random() < 0.5)
     resets = bool(rng.random() < 0.3)      # single streams restarted between buffers (rt_reset_stream)
     u8 = bool(rng.random() < 0.2)          # RTL-SDR wire format: uint8 I/Q converted in the scan kernel's load
-    if u8:
+    # SOAK_FEATURES=1: the features merged since round 6, from a random stream of their own
+    rng_f = np.random.default_rng([seed0, case, 19])
+    features = os.environ.get("SOAK_FEATURES") == "1"
+    ints = None  # "i16" / "i8": signed integer IQ, converted in the scan kernel's load like uint8
+    if features and not u8 and rng_f.random() < 1.0 / 3.0:
+        ints = str(rng_f.choice(["i16", "i8"]))
+    gapped = features and bool(rng_f.random() < 0.4)
+    per_stream = features and bool(rng_f.random() < 0.4)
+    if u8 or ints:
         thr = -70.0
     dev_tensor = bool(rng.random() < 0.3)  # torch CUDA tensors (rows padded: stream_stride > n_samples) instead of host arrays
     chunking = int(rng.choice([0, 0, 4, 8, 16]))  # segments per lane-group chunk (0 = the library's choice)
@@ -126,7 +139,7 @@ while time.time() < t_end:
         k0 = int(rng_step.integers(1, n_buf))
         who = np.arange(n_streams) if rng_step.random() < 0.5 else rng_step.choice(n_streams, size=max(1, n_streams // 4), replace=False)
         iq[who, k0 * blen:] *= np.complex64(0.5)
-    poison = os.environ.get("SOAK_POISON") == "1" and not u8 and rng.random() < 0.5
+    poison = os.environ.get("SOAK_POISON") == "1" and not u8 and not ints and rng.random() < 0.5
     crash_only = False
     counted = (n_unexplained, n_field)
     if poison:
@@ -144,6 +157,19 @@ while time.time() < t_end:
             iq[int(rng.integers(0, n_streams)), int(rng.integers(0, iq.shape[1]))] = v
     kw = dict(sample_rate=fs, fft_nperseg=nperseg, fft_window=window, signal_min_duration_ms=min_ms, signal_max_duration_ms=max_ms,
               signal_threshold_dbw=thr, snr_threshold_db=snr)
+    # per-stream settings: every stream its own SNR threshold, duration gates (inside the case's, which stay the handle's envelope
+    # where a stream draws them) and absolute threshold; the oracle of stream s is built with kws[s]
+    kws = [dict(kw) for _ in range(n_streams)]
+    if per_stream:
+        for s in range(n_streams):
+            lo = min_ms + float(rng_f.choice([0.0, 0.0, 2.0, 5.0])) * hop * 1e3
+            hi = max_ms - float(rng_f.choice([0.0, 0.0, 3.0, 10.0])) * hop * 1e3
+            if hi < lo + 3 * hop * 1e3:  # (the case's own gates where the draws leave no room between them)
+                lo, hi = min_ms, max_ms
+            kws[s].update(signal_min_duration_ms=lo, signal_max_duration_ms=hi, snr_threshold_db=float(rng_f.choice([5.0, 0.0, 8.0, 3.0])),
+                          signal_threshold_dbw=thr + float(rng_f.choice([0.0, 0.0, 5.0, -5.0])))
+        for name in ("signal_min_duration_ms", "signal_max_duration_ms", "snr_threshold_db", "signal_threshold_dbw"):
+            kw[name] = [k_[name] for k_ in kws]
     # (round 6: the per-stream record capacity STARTS small -- a stream that needs more grows it inside rt_fetch, so no buffer is
     # skipped for its record count any more; a mode the geometry does not have -- the chunk-bit pre-filter with a short minimum
     # duration, the exact one beyond its planner's counters or at nperseg 32 / 8192 / 16384 -- falls back to AUTO instead of
@@ -163,7 +189,8 @@ while time.time() < t_end:
     if b is None:
         continue
     cals = cal if isinstance(cal, list) else [cal] * n_streams
-    oas = [oracle.OracleAnalyzer(device=str(s), calibration_db=cals[s], **kw) for s in range(n_streams)]
+    oas = [oracle.OracleAnalyzer(device=str(s), calibration_db=cals[s], **kws[s]) for s in range(n_streams)]
+    thrs, snrs = [k_["signal_threshold_dbw"] for k_ in kws], [k_["snr_threshold_db"] for k_ in kws]
     bad = 0
     nrec = 0
     # the case as a list of events, then one pass over the GPU (fetches lag one call behind the enqueues when
@@ -176,9 +203,23 @@ while time.time() < t_end:
         if u8:
             raw = synth.quantize_u8(chunk, gain=float(rng.choice([300.0, 2000.0])))
             chunk = synth.u8_to_complex64_like_kernel(raw)  # what the kernel makes of the bytes: the oracle's input
+        elif ints:
+            gain = float(rng_f.choice([300.0, 2000.0]))
+            raw = synth.quantize_i16(chunk, gain=gain) if ints == "i16" else synth.quantize_i8(chunk, gain=gain)
+            chunk = synth.i16_to_complex64(raw) if ints == "i16" else synth.i8_to_complex64(raw)
         if resets and k > 0:
             events += [("reset", s) for s in range(n_streams) if rng.random() < 0.3]
-        events.append(("buffer", chunk, raw))
+        mask = None
+        if gapped:
+            # a stream sits the buffer out with probability 1 / 4: the handle must not read its row (NaN, or a full-scale square on
+            # the integer formats), its oracle is not called and keeps its previous map
+            mask = rng_f.random(n_streams) >= 0.25
+            if raw is None:
+                chunk[~mask] = np.nan + 1j * np.nan
+            else:
+                hi_, lo_ = np.iinfo(raw.dtype).max, np.iinfo(raw.dtype).min
+                raw[~mask] = np.where(np.arange(raw.shape[1]) % 4 < 2, hi_, lo_).astype(raw.dtype)
+        events.append(("buffer", chunk, raw, mask))
     in_flight, results = [], []
 
     def fetch_one():
@@ -195,18 +236,21 @@ while time.time() < t_end:
             b.reset_stream(ev[1])
             results.append(("reset", ev[1]))
             continue
+        if ev[3] is not None:
+            b.set_present(ev[3])
+        feed = b.enqueue_bytes if u8 else b.enqueue_int16 if ints == "i16" else b.enqueue_int8 if ints == "i8" else b.enqueue
         if dev_tensor:
             import torch
 
             pad = int(rng.integers(0, 5)) * 8
-            src = ev[2] if u8 else ev[1]
-            wide = torch.zeros((src.shape[0], src.shape[1] + (2 * pad if u8 else pad)), dtype=torch.uint8 if u8 else torch.complex64, device="cuda")
+            src = ev[2] if (u8 or ints) else ev[1]
+            wide = torch.zeros((src.shape[0], src.shape[1] + (2 * pad if (u8 or ints) else pad)), dtype=torch.from_numpy(src[:0]).dtype, device="cuda")
             view = wide[:, : src.shape[1]]
             view.copy_(torch.from_numpy(src))
-            (b.enqueue_bytes(view) if u8 else b.enqueue(view))
+            feed(view)
         else:
-            (b.enqueue_bytes(ev[2]) if u8 else b.enqueue(ev[1]))
-        in_flight.append(ev[1])
+            feed(ev[2] if (u8 or ints) else ev[1])
+        in_flight.append((ev[1], ev[3]))
         if len(in_flight) > (1 if pipelined else 0):
             fetch_one()
     while in_flight:
@@ -221,17 +265,24 @@ while time.time() < t_end:
             oas[res[1]].reset()
             continue
         k += 1
-        chunk = res[2]
+        chunk, mask = res[2]
+        here = [s for s in range(n_streams) if mask is None or mask[s]]
         if res[0] == "skipped":  # (a sparse-mode handle whose candidate lists overflowed: no result by contract)
             print(f"case {case}: buffer {k} skipped: {res[1]}")
             try:
-                for s in range(n_streams):
+                for s in here:
                     oas[s].process(chunk[s], TS0)  # both sides keep this buffer as their look-back
             except IndexError:
                 abandoned = True
             continue
         rec = res[1]
         for s in range(n_streams):
+            if s not in here:
+                if (rec["stream"] == s).any():
+                    bad += 1
+                    n_unexplained += 1
+                    print(f"  MISMATCH (UNEXPLAINED) case {case} buf {k} stream {s}: {int((rec['stream'] == s).sum())} records of a stream that sat the buffer out")
+                continue
             try:
                 want, kept = oas[s].process(chunk[s], TS0)
             except IndexError:
@@ -249,8 +300,8 @@ while time.time() < t_end:
                 extra, missing = sorted(set(got) - set(exp)), sorted(set(exp) - set(got))
                 # margin of the decisions behind the differing runs: the cells at their ends against both thresholds
                 spec = oas[s].spec_last  # [F, T] float32 of this buffer (just stored by process())
-                thr_lin = np.float32(oracle.db_to_linear(thr + cals[s]))
-                snr_lin = np.float32(oracle.db_to_linear(snr))
+                thr_lin = np.float32(oracle.db_to_linear(thrs[s] + cals[s]))
+                snr_lin = np.float32(oracle.db_to_linear(snrs[s]))
                 margins = []
                 for fi, st, en in (extra + missing)[:16]:
                     avg = spec[fi].mean()
@@ -307,6 +358,6 @@ while time.time() < t_end:
     if crash_only:
         n_unexplained, n_field = counted
     print(f"case {case}: N={nperseg} fs={fs} {window} T={n_seg} S={n_streams} bufs={n_buf} min/max={min_ms:.2f}/{max_ms:.1f} ms thr={thr} snr={snr} "
-          f"mode={mode} lanes={lanes} cal={'per-stream' if isinstance(cal, list) else cal}{' pipelined' if pipelined else ''}{' ragged' if vary_len else ''}{' restarts' if resets else ''}{' uint8' if u8 else ''}{' device-tensors' if dev_tensor else ''}{' poisoned' if poison else ''}{' (crash-only: a huge finite sample)' if crash_only else ''}{' noisy' if noisy else ''}{' floor-step' if floor_step else ''}{' noisy-streams=' + str(sorted(noisy_some)) if noisy_some else ''}{' subtract-first' if subtract_first else ''}{' wave-per-stream' if whole_stream else ''} chunk={chunking}: {nrec} records, {bad} mismatching stream-buffers", flush=True)
+          f"mode={mode} lanes={lanes} cal={'per-stream' if isinstance(cal, list) else cal}{' pipelined' if pipelined else ''}{' ragged' if vary_len else ''}{' restarts' if resets else ''}{' uint8' if u8 else ''}{' ' + ints if ints else ''}{' gaps' if gapped else ''}{' per-stream-settings' if per_stream else ''}{' device-tensors' if dev_tensor else ''}{' poisoned' if poison else ''}{' (crash-only: a huge finite sample)' if crash_only else ''}{' noisy' if noisy else ''}{' floor-step' if floor_step else ''}{' noisy-streams=' + str(sorted(noisy_some)) if noisy_some else ''}{' subtract-first' if subtract_first else ''}{' wave-per-stream' if whole_stream else ''} chunk={chunking}: {nrec} records, {bad} mismatching stream-buffers", flush=True)
 print(f"SOAK: {n_cases} cases, {n_records} oracle records, {n_bad} mismatching stream-buffers "
       f"({n_unexplained} not explained by a float32 round-off margin, {n_field} with a field beyond 0.1 dB)")

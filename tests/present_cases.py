@@ -56,6 +56,29 @@ def _table_a():
     return p
 
 
+# Schedule P: 10 calls of T = 47 47 47 33 35 9 47 0 41 47 segments (tests/combo_cases.py).  Every gap ends on call 2, 4, 6, 8 or 9:
+# 41 or 47 segments hold the stop cell of the deepest reach-back (33) whatever buffer lies before the gap, and the 35 of call 4
+# that of a gap from call 1 or 2 (at most 33 cells deep: times[34]):
+#   stream 0  always present (but for the call every stream sits out);
+#   stream 1  absent on single calls: 1, (3,) 7 -- the empty call;
+#   stream 2  absent three calls running (3, 4, 5), then two (7, 8);
+#   stream 3  absent on the first call and on the call of 9 segments (5);
+#   stream 4  absent whenever (k + 1) % 3 == 0 (2, 5, 8): its last gap looks back into its own empty buffer of call 7;
+#   call 3    every stream absent.
+# combo_cases.EVENTS: stream 2's SNR threshold changes before call 4, which it sits out; stream 1 is reset before call 6, present.
+P_ALL_ABSENT_CALL = 3
+
+
+def _table_p():
+    p = np.ones((len(sq.SCHEDULES["P"].T), 5), bool)
+    p[[1, 7], 1] = False
+    p[[3, 4, 5, 7, 8], 2] = False
+    p[[0, 5], 3] = False
+    p[[2, 5, 8], 4] = False
+    p[P_ALL_ABSENT_CALL, :] = False
+    return p
+
+
 def _table_regular(n, S):
     """Schedules of equal lengths (B, B10): stream 0 always present, 1 absent on single calls, 2 two / three / four running,
     3 on the first call and two in the middle, 4 whenever (k + 1) % 3 == 0; the last call but one with every stream absent."""
@@ -98,6 +121,8 @@ def table(name, S=5):
         t = _table_a()
     elif name == "C":
         t = _table_c()
+    elif name == "P":
+        t = _table_p()
     else:
         t = _table_regular(len(sq.SCHEDULES[name].T), 5)
     t = t[:, :S].copy()
@@ -134,6 +159,9 @@ def poisoned(x, present_k, fmt):
             if fmt in ("u8", "u8f64"):
                 feed[s, 0::2] = np.where(re > 0, 255, np.where(re < 0, 0, 128))
                 feed[s, 1::2] = np.where(im > 0, 255, np.where(im < 0, 0, 128))
+            elif fmt in ("i8", "i8f64"):
+                feed[s, 0::2] = np.where(re > 0, 127, np.where(re < 0, -128, 0))
+                feed[s, 1::2] = np.where(im > 0, 127, np.where(im < 0, -128, 0))
             else:
                 feed[s, 0::2] = np.where(re > 0, 32767, np.where(re < 0, -32768, 0))
                 feed[s, 1::2] = np.where(im > 0, 32767, np.where(im < 0, -32768, 0))

@@ -26,6 +26,11 @@ float32 round-off -- DESIGN section 2 pins that tie as undecidable -- and the ve
   and stops ON that segment; after a reset (no previous map) it goes on to segment 0.
 * Schedule B: ten calls of 96 segments with the same tables.
 * Schedule C: equal lengths, the noise level moving quiet -> floor -> higher floor -> floor -> quiet, for AUTO and the pre-filters.
+* Schedule P: schedule A's tables on ten short calls (at most 47 segments) for the covering table of tests/combo_cases.py: an empty
+  call, one under K / 4 segments (9), one just over a chunk of 32 (33), four shorter than K = 42 (33, 35, 9, 41), so that a walk reads a tail wider
+  than the call, and each of the three rotating tails is written at least three times.  The first three calls are no shorter than K
+  (a misplaced column of a short call shows at once, not only on a tail written twice), and no T / h, h hot segments of a row, lies
+  within 4 % of the SNR thresholds the table uses (2.9 and 8 dB): a tone's cells over their row's mean are T / h.
 
 Also here: a NumPy model of the look-back tail with the two mutations the old three-call tests cannot see (``tail_model_records``),
 the float64 restatement the seed guard of schedule C uses (``records_f64``), and the helper that feeds a schedule's calls to a handle
@@ -62,6 +67,7 @@ SCHEDULES = {
     "B": Schedule("B", (96,) * 10, (0,) * 10, False, 0, None, None),
     # B for the chunk-bit pre-filter: every run at least 10 segments long (e stretched), see test_gpu_sequences
     "B10": Schedule("B10", (96,) * 10, (0,) * 10, False, 10, None, None),
+    "P": Schedule("P", (47, 47, 47, 33, 35, 9, 47, 0, 41, 47), (5, 0, -1, 7, 0, 3, 0, 100, 0, 9), True, 0, None, None),
 }
 
 # Schedule C: noise regimes.  The per-call sigma moves quiet -> floor -> higher floor -> floor -> quiet; stream 1 alone is noisy in
@@ -196,9 +202,9 @@ def call_sigma(sched, k, s, base):
     return sched.sigmas[k]
 
 
-def buffer(sched, nperseg, k, S=None, fs=FS, sigma=synth.NOISE_SIGMA, seed=None):
+def buffer(sched, nperseg, k, S=None, fs=FS, sigma=synth.NOISE_SIGMA, seed=None, peak_dbw=PEAK_DBW):
     """complex64 [S, T[k] nperseg + rag[k]]: call k of every stream.  Noise from (seed, k, s); the tones exp(2 pi j bin n / N), n
-    counted from the buffer's first sample, added in float64 and rounded once."""
+    counted from the buffer's first sample, added in float64 and rounded once.  ``peak_dbw``: the level of tone 0."""
     S = n_streams(nperseg) if S is None else S
     if seed is None:
         seed = 2024 if sched.sigmas is None else C_SEEDS.get(nperseg, 1)
@@ -207,7 +213,7 @@ def buffer(sched, nperseg, k, S=None, fs=FS, sigma=synth.NOISE_SIGMA, seed=None)
     amps = {}
     for s in range(S):
         for i, b in enumerate(tone_bins(nperseg, s) + extra_bins(nperseg, s)):
-            amps[(s, b)] = synth.amp_for_peak_dbw(PEAK_DBW - LEVEL_STEP_DB * i, w, fs)
+            amps[(s, b)] = synth.amp_for_peak_dbw(peak_dbw - LEVEL_STEP_DB * i, w, fs)
     out = np.empty((S, n), np.complex64)
     seg_idx = np.arange(nperseg)
     for s in range(S):
@@ -226,8 +232,8 @@ def buffer(sched, nperseg, k, S=None, fs=FS, sigma=synth.NOISE_SIGMA, seed=None)
 # ---- input formats ---------------------------------------------------------------------------------------------------------------
 def wire(x, fmt):
     """(what the handle is fed, what the reference arithmetic sees) for complex64 ``x``:
-    ``c64``; ``u8`` / ``i16`` (the kernels' conversion to complex64); ``c128`` (widened exactly); ``u8f64`` (bytes into a float64
-    handle: pyrtlsdr's conversion)."""
+    ``c64``; ``u8`` / ``i16`` / ``i8`` (the kernels' conversion to complex64); ``c128`` (widened exactly); ``u8f64`` (bytes into a
+    float64 handle: pyrtlsdr's conversion); ``i16f64`` / ``i8f64`` (integers into a float64 handle: the exact widening)."""
     if fmt == "c64":
         return x, x
     if fmt == "c128":
@@ -236,14 +242,21 @@ def wire(x, fmt):
     if fmt in ("u8", "u8f64"):
         raw = synth.quantize_u8(x, gain=WIRE_GAIN)
         return raw, (synth.u8_to_complex64_like_kernel(raw) if fmt == "u8" else synth.u8_to_complex128_like_pyrtlsdr(raw))
-    if fmt == "i16":
+    if fmt in ("i16", "i16f64"):
         raw = synth.quantize_i16(x, gain=WIRE_GAIN)
-        return raw, synth.i16_to_complex64(raw)
+        return raw, (synth.i16_to_complex64(raw) if fmt == "i16" else synth.i16_to_complex128(raw))
+    if fmt in ("i8", "i8f64"):
+        raw = synth.quantize_i8(x, gain=WIRE_GAIN)
+        return raw, (synth.i8_to_complex64(raw) if fmt == "i8" else synth.i8_to_complex128(raw))
     raise ValueError(fmt)
 
 
+WIRE_FORMATS = ("u8", "u8f64", "i16", "i16f64", "i8", "i8f64")
+F64_FORMATS = ("c128", "u8f64", "i16f64", "i8f64")
+
+
 def is_wire(fmt):
-    return fmt in ("u8", "u8f64", "i16")
+    return fmt in WIRE_FORMATS
 
 
 def case_settings(nperseg, fmt="c64", **over):
@@ -382,8 +395,10 @@ def tail_model_records(name, nperseg, s, L, rule="correct", n_calls=None, fs=FS)
 def enqueue(b, feed, fmt):
     if fmt in ("u8", "u8f64"):
         b.enqueue_bytes(np.ascontiguousarray(feed))
-    elif fmt == "i16":
+    elif fmt in ("i16", "i16f64"):
         b.enqueue_int16(np.ascontiguousarray(feed))
+    elif fmt in ("i8", "i8f64"):
+        b.enqueue_int8(np.ascontiguousarray(feed))
     else:
         b.enqueue(np.ascontiguousarray(feed))
 

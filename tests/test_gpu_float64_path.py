@@ -25,7 +25,7 @@ def _need_gpu():
 
 def _check(rec, want, cal=0.0):
     """rt_record_f64 rows of one stream against oracle records (all of them, shadow verdicts from the oracle's filter)."""
-    sig = oracle.records_to_signals(want, np.zeros(4096), fc.TS0, "0", 0.0)
+    sig = oracle.records_to_signals(want, np.zeros(16384), fc.TS0, "0", 0.0)
     kept = {(s.fi, s.start) for s in oracle.filter_shadows(sig)}
     assert [(int(r["fi"]), int(r["start"]), int(r["end"])) for r in rec] == fc.key(want)
     assert [int(r["shadowed"]) for r in rec] == [0 if (w.fi, w.start) in kept else 1 for w in want]

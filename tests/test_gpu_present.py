@@ -102,7 +102,7 @@ def test_float64(fmt):
 
 
 # the wire formats (absent rows: a full-scale tone)
-@pytest.mark.parametrize("fmt", ["u8", "i16"])
+@pytest.mark.parametrize("fmt", ["u8", "i16", "i8"])
 def test_wire_formats(fmt):
     _case("A", 256, "sparse", fmt)
 
@@ -405,6 +405,6 @@ def oracle_keys():
     """Every (schedule, nperseg, format, events, minimum) the cases above ask the gapped oracle for (tests/test_present_contract.py
     runs them all on the CPU)."""
     keys = [("A", n, "c64", (), sq.MIN_HOPS) for n in (128, 256, 1024, 4096, 8192)] + [("A", n, "c64", (), sq.MIN_HOPS) for n, _ in DENSE]
-    keys += [("A", 256, f, (), sq.MIN_HOPS) for f in ("c128", "u8f64", "u8", "i16")]
+    keys += [("A", 256, f, (), sq.MIN_HOPS) for f in ("c128", "u8f64", "u8", "i16", "i8")]
     keys += [("B10", 256, "c64", (), 8.0), ("C", 256, "c64", (), sq.C_MIN_HOPS), ("A", 256, "c64", EVENTS, sq.MIN_HOPS)]
     return sorted(set(keys), key=str)

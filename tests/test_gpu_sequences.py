@@ -109,7 +109,7 @@ def test_chunk_geometry(name, nperseg, L):
 
 
 # input formats: the conversion is fused into the scan's load; the handle must also equal a complex64 handle fed the conversion
-FORMATS = [(name, n, fmt) for name in ("A", "B") for n in (256, 4096) for fmt in ("u8", "i16")]
+FORMATS = [(name, n, fmt) for name in ("A", "B") for n in (256, 4096) for fmt in ("u8", "i16", "i8")]
 
 
 @pytest.mark.parametrize("name,nperseg,fmt", FORMATS)
