@@ -139,6 +139,8 @@ typedef struct rt_config {
 #define RT_FLAG_ROW_MEANS 16u      /* keep each call's row means for rt_fetch_row_means[_f64] (rt_create and rt_create_f64) */
 #define RT_FLAG_RECORD_CELLS 32u   /* keep the cells of every record of a call for rt_fetch_record_cells[_f64] (rt_create and rt_create_f64) */
 #define RT_FLAG_F64_SPARSE 64u     /* rt_create_f64 only (rt_create: RT_E_INVALID): the map-free float64 path, see "float64 handles" below */
+#define RT_FLAG_F64_RESCUE 128u    /* rt_create_f64 with RT_FLAG_F64_SPARSE only (else RT_E_INVALID): streams whose candidate lists overflow are
+                                    * analysed again on their own inside rt_fetch_f64, see "float64 handles" below */
 
 /*
  * One extracted plateau, before it becomes a Signal (analyze.py:442-449).
@@ -342,12 +344,27 @@ const char *rt_last_error(rt_handle *h);
  *     (RT_E_UNSUPPORTED).  On such a handle rt_config.hot_capacity counts candidate cells per stream and call: 0 = 4096,
  *     else 1024 ... 8192 (what one workgroup sorts in LDS; outside: RT_E_INVALID); a stream that emits more ends the call
  *     as RT_MODE_SPARSE does on a float32 handle -- rt_fetch_f64 returns RT_E_HOT_OVERFLOW, delivers nothing and consumes
- *     the call, whose look-back tail stays the next call's; there is no map to fall back to (create a dense handle).
+ *     the call, whose look-back tail stays the next call's; there is no map to fall back to (create a dense handle, or set
+ *     RT_FLAG_F64_RESCUE, below).
  *     rt_config.segs_per_chunk: segments of one stream a scan workgroup walks (0 = a default from the geometry); it sets
  *     the order of the row sums' partial sums, nothing else.  Everything listed below keeps its meaning, the four input
  *     formats, rt_set_present, rt_set_stream_params_f64 (the emission uses the stream's own threshold),
  *     rt_set_stream_settings_f64 and RT_FLAG_ROW_MEANS (every row's mean from the scan's sums) included; rt_extract_f64 and
  *     rt_spectrogram_f64 work on caller-supplied memory and are unchanged;
+ *     RT_FLAG_F64_RESCUE (only together with RT_FLAG_F64_SPARSE; without it, or on rt_create: RT_E_INVALID, refused before
+ *     any device is touched) takes the RT_E_HOT_OVERFLOW away.  A call in which no stream overflows runs exactly what it
+ *     runs without the flag.  Otherwise rt_fetch_f64 analyses the present streams that emitted more than hot_capacity cells
+ *     again, and only those: their segments are transformed once more with the scan's own arithmetic into a per-stream
+ *     float64 map in a scratch area (allocated at first need, kept until rt_destroy; 256 MiB, or one stream's
+ *     T * nperseg * 8 bytes where that is larger; more streams than it holds are taken in rounds), their rows are walked
+ *     densely with the row sums of the scan and the call's look-back tail, and the call's records are ranked and packed
+ *     again.  The records of such a stream are the ones a large enough hot_capacity would have given, byte for byte, the
+ *     row means (RT_FLAG_ROW_MEANS) as well.  rt_call_info of a delivered call of such a handle: mode_used =
+ *     RT_MODE_SPARSE, n_dense_streams = the streams analysed again, fell_back = 1 if there were any, n_hot = the cells the
+ *     present streams emitted (the counters, not the cells stored).  No memory for the scratch: rt_fetch_f64 returns
+ *     RT_E_NOMEM and consumes the call, whose look-back tail stays the next call's.  The cost is a second transform and
+ *     a serial walk over T cells per bin for each such stream: a handle many of whose streams overflow belongs on the
+ *     dense path (measured break-even at 4 096 streams x 300 kS, nperseg 256: about 4 % of the streams);
  *   - nperseg 8 ... 4096, or a power of two up to 8192 (a segment's transform in LDS: Bluestein's padded length M <= 8192
  *     complex doubles = 128 KiB); anything else is RT_E_UNSUPPORTED;
  *   - cfg->lanes must be 0 or 1 (RT_E_UNSUPPORTED otherwise): one launch sequence per call;

@@ -31,6 +31,7 @@ RT_FLAG_GROUP_DETECT = 4  # sparse detection by groups of candidate lists at any
 RT_FLAG_NO_GROUP_DETECT = 8  # ... never
 RT_FLAG_ROW_MEANS = 16  # keep each call's row means (every bin's noise level) for rt_fetch_row_means[_f64]
 RT_FLAG_RECORD_CELLS = 32  # keep the spectrogram cells of every record of a call (the reference's ``data``) for rt_fetch_record_cells[_f64]
+RT_FLAG_F64_RESCUE = 128  # rt_create_f64 with RT_FLAG_F64_SPARSE only: overflowing streams are analysed again on their own inside rt_fetch_f64
 RT_FLAG_F64_SPARSE = 64  # rt_create_f64 only: the map-free float64 path (fused scan + detection from candidate-cell lists)
 
 SUPPORTED_NPERSEG = tuple(range(8, 8193)) + (16384,)  # 8 .. 8192 and 16384 (32 .. 4096 powers of two: the fused scans; everything else: general transforms, dense path)
@@ -329,13 +330,17 @@ class NativeAnalyzer:
         row_means: bool = False,
         record_cells: bool = False,
         f64_sparse: bool = False,
+        f64_rescue: bool = False,
     ):
         """``precision="float64"``: a float64 handle (``rt_create_f64``) -- ``window_f32`` then holds the float64 window and
         ``scale`` / ``threshold`` / ``snr_threshold`` / ``calibration_db`` are passed on as float64, never rounded to float32;
         the analysis takes complex128 (or uint8) IQ and the records are ``RECORD_F64_DTYPE``.  ``row_means``:
         ``RT_FLAG_ROW_MEANS`` (``fetch_row_means``); ``record_cells``: ``RT_FLAG_RECORD_CELLS`` (``fetch_record_cells``).
         ``f64_sparse``: ``RT_FLAG_F64_SPARSE`` -- a float64 handle without the float64 map (``mode`` must be ``RT_MODE_AUTO``;
-        ``hot_capacity`` then counts candidate cells per stream and call, 0 or 1024 ... 8192)."""
+        ``hot_capacity`` then counts candidate cells per stream and call, 0 or 1024 ... 8192).
+        ``f64_rescue``: ``RT_FLAG_F64_RESCUE`` (needs ``f64_sparse``) -- a stream that emits more than ``hot_capacity`` cells no
+        longer ends the call with ``RT_E_HOT_OVERFLOW``: the fetch analyses it again on its own from a per-stream float64 map
+        (``call_info``: ``n_dense_streams``, ``fell_back``)."""
         if precision not in ("float32", "float64"):
             raise ValueError(f"precision must be 'float32' or 'float64', not {precision!r}")
         if f64_sparse:
@@ -345,6 +350,8 @@ class NativeAnalyzer:
                 raise ValueError("f64_sparse selects the path by itself: mode must be 'auto'")
             if record_cells:
                 raise ValueError("f64_sparse keeps no map: record_cells is not available with it")
+        if f64_rescue and not f64_sparse:
+            raise ValueError("f64_rescue re-runs the overflowing streams of the map-free path: it needs f64_sparse=True")
         self.f64 = precision == "float64"
         self._lib = load_library()
         self._handle = C.c_void_p()
@@ -372,7 +379,8 @@ class NativeAnalyzer:
                      | (0 if group_detect is None else RT_FLAG_GROUP_DETECT if group_detect else RT_FLAG_NO_GROUP_DETECT)
                      | (RT_FLAG_ROW_MEANS if row_means else 0)
                      | (RT_FLAG_RECORD_CELLS if record_cells else 0)
-                     | (RT_FLAG_F64_SPARSE if f64_sparse else 0))
+                     | (RT_FLAG_F64_SPARSE if f64_sparse else 0)
+                     | (RT_FLAG_F64_RESCUE if f64_rescue else 0))
         cfg.hip_stream = hip_stream
         cfg.lanes = int(lanes)
         cfg.record_pool = int(record_pool)

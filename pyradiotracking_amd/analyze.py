@@ -294,6 +294,7 @@ class BatchSignalAnalyzer:
         row_means: bool = False,
         record_cells: bool = False,
         f64_sparse: bool = False,
+        f64_rescue: bool = False,
         **kwargs,
     ):
         """``record_cells`` (``RT_FLAG_RECORD_CELLS``): keep the spectrogram cells every record of a call consists of -- the
@@ -315,6 +316,12 @@ class BatchSignalAnalyzer:
         detection works from those lists; nperseg a power of two 32 ... 4096.  ``hot_capacity`` then
         counts candidate cells per stream and call (0: 4096; 1024 ... 8192); a stream that emits more makes
         ``fetch_records`` raise ``RT_E_HOT_OVERFLOW`` for that call.  ``segs_per_chunk``: segments a scan workgroup walks.
+
+        ``f64_rescue`` (``RT_FLAG_F64_RESCUE``; needs ``f64_sparse=True``, else ``ValueError``): such a stream no longer costs
+        the call -- ``fetch_records`` analyses the overflowing streams again on their own from a per-stream float64 map in a
+        scratch area (DESIGN section 4.18) and delivers what a large enough ``hot_capacity`` would have, byte for byte;
+        ``call_info()`` reports them as ``n_dense_streams`` / ``fell_back``.  A call without such a stream runs what it runs
+        without the flag.
 
         ``mode`` (``rt_config.mode``): ``"auto"`` (default) analyses on the fused sparse path and, when an input's noise
         crosses the thresholds, climbs by itself -- chunk-bit pre-filter, exact SNR-aware pre-filter, dense spectrogram; the
@@ -368,7 +375,10 @@ class BatchSignalAnalyzer:
                 raise ValueError("f64_sparse selects the path by itself: mode must be 'auto'")
             if record_cells:
                 raise ValueError("f64_sparse keeps no map: record_cells is not available with it")
+        if f64_rescue and not f64_sparse:
+            raise ValueError("f64_rescue re-runs the overflowing streams of the map-free path: it needs f64_sparse=True")
         self.f64_sparse = bool(f64_sparse)
+        self.f64_rescue = bool(f64_rescue)
         per_stream_cal = None
         if np.ndim(calibration_db):
             per_stream_cal = [float(c) for c in calibration_db]
@@ -431,6 +441,7 @@ class BatchSignalAnalyzer:
             row_means=bool(row_means),
             record_cells=bool(record_cells),
             f64_sparse=self.f64_sparse,
+            f64_rescue=self.f64_rescue,
         )
         if per_stream_cal is not None or per_thr is not None:
             n = len(self.devices)
@@ -802,13 +813,15 @@ class SignalAnalyzer:
         row_means: bool = False,
         record_cells: bool = False,
         f64_sparse: bool = False,
+        f64_rescue: bool = False,
         **kwargs,
     ):
         """``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
 
         ``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer);
-        ``f64_sparse=True`` with it: on the map-free float64 path (same ``Signal``s).
+        ``f64_sparse=True`` with it: on the map-free float64 path (same ``Signal``s); ``f64_rescue=True`` with that: a buffer
+        that overflows the candidate lists is analysed again from a float64 map instead of raising ``RT_E_HOT_OVERFLOW``.
         ``row_means=True``: after every buffer ``noise_dbw`` holds the noise level of every bin (``[fft_nperseg]``, dBW, fftfreq
         order) -- what the reference prints as the ``noise`` of a Signal (analyze.py:446), for all bins."""
         self.device = device
@@ -868,6 +881,7 @@ class SignalAnalyzer:
             row_means=self.row_means,
             record_cells=self.record_cells,
             f64_sparse=bool(f64_sparse),
+            f64_rescue=bool(f64_rescue),
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
             **{k: kwargs[k] for k in ("record_capacity", "record_pool", "hot_capacity", "group_detect") if k in kwargs},
         )

@@ -32,6 +32,7 @@
 #include "rt_general.h"
 #include "rt_f64.h"
 #include "rt_f64_sparse.h"
+#include "rt_f64_rescue.h"
 #include "rt_cells.h"
 #include "rt_present.h"
 #include "rt_tables.h"
@@ -192,6 +193,7 @@ struct F64Slot {
     double *d_vals = nullptr;      // [S][hot_cap]
     int32_t *d_cell_count = nullptr;  // [S], zero between calls
     int32_t *h_hot = nullptr;      // pinned, device-visible: [S] cells each stream emitted
+    int n_rescued = -1;            // RT_FLAG_F64_RESCUE: streams of the enqueued call rt_fetch_f64 has analysed again (-1: not looked at yet)
     hipEvent_t ev_done = nullptr;
 };
 struct F64State {
@@ -221,6 +223,13 @@ struct F64State {
     int group = 1, chunk = 1, chunk_cap = 0, hot_cap = 0, sort_cap = 0;
     double *d_partial = nullptr;   // [S][chunk_cap][N]
     double *d_row_sums = nullptr;  // [S][N]
+    // RT_FLAG_F64_RESCUE: the scratch of rt_fetch_f64's re-analysis (rt_f64_rescue.h), allocated at first need and kept
+    bool rescue = false;
+    bool rs_attr = false;          // the map scans' dynamic LDS limit is set
+    double *d_rs_map = nullptr;    // [per_round][T][N]
+    double *d_rs_partial = nullptr;  // [per_round][n_chunks][N]
+    size_t rs_map_bytes = 0, rs_partial_bytes = 0;
+    int32_t *d_rs_list = nullptr;  // [S] the call's overflowing streams
 };
 
 }  // namespace
@@ -1501,6 +1510,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     const bool general = fam.general, bluestein = fam.bluestein;
     if (cfg->mode < RT_MODE_AUTO || cfg->mode > RT_MODE_RUNFILTER) return fail_create(RT_E_INVALID, "bad mode");
     if (cfg->flags & RT_FLAG_F64_SPARSE) return fail_create(RT_E_INVALID, "RT_FLAG_F64_SPARSE is a flag of float64 handles (rt_create_f64)");
+    if (cfg->flags & RT_FLAG_F64_RESCUE) return fail_create(RT_E_INVALID, "RT_FLAG_F64_RESCUE is a flag of float64 handles (rt_create_f64)");
     if (general && cfg->mode != RT_MODE_AUTO && cfg->mode != RT_MODE_DENSE)
         return fail_create(RT_E_UNSUPPORTED, "fft_nperseg " + std::to_string(cfg->nperseg) + " runs on the dense path only: mode must be RT_MODE_AUTO or RT_MODE_DENSE");
     if (big && (cfg->mode == RT_MODE_PREFILTER || cfg->mode == RT_MODE_RUNFILTER))
@@ -3070,6 +3080,7 @@ int f64_enqueue_sparse(rt_handle *h, F64Slot &sl) {
     const int S = h->cfg.n_streams;
     hipStream_t st = h->s_scan;
     const int n_chunks = f64_sparse_chunks(sl.n_seg, f->chunk);
+    sl.n_rescued = -1;
     if (sl.n_seg > 0) {
         F64ScanParams p{};
         p.iq = sl.iq;
@@ -3126,6 +3137,113 @@ int f64_enqueue_sparse(rt_handle *h, F64Slot &sl) {
     clear_counts_sparse_f64<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(sl.d_raw_count, sl.d_cell_count, S);
     RT_HIP(h, hipGetLastError());
     RT_HIP(h, hipEventRecord(sl.ev_done, st));
+    return RT_OK;
+}
+
+template <int FMT>
+void launch_scan_map_f64(const F64MapScanParams &p, int nb, unsigned grid, size_t lds, hipStream_t st) {
+    if (nb == 4) scan_map_f64<FMT, 4><<<grid, kF64ScanBlock, lds, st>>>(p);
+    else if (nb == 8) scan_map_f64<FMT, 8><<<grid, kF64ScanBlock, lds, st>>>(p);
+    else scan_map_f64<FMT, 16><<<grid, kF64ScanBlock, lds, st>>>(p);
+}
+
+// a rescue scratch area of at least `bytes` (kept; a smaller one is replaced once nothing on the stream uses it any more)
+int f64_rescue_area(rt_handle *h, double *&area, size_t &have, size_t bytes) {
+    if (have >= bytes) return RT_OK;
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    (void)hipFree(area);
+    area = nullptr;
+    have = 0;
+    if (hipMalloc(&area, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        area = nullptr;
+        return f64_err(h, RT_E_NOMEM, "RT_FLAG_F64_RESCUE: no device memory for the rescue scratch (" + std::to_string(bytes) + " bytes)");
+    }
+    have = bytes;
+    return RT_OK;
+}
+
+// RT_FLAG_F64_RESCUE: the present streams of the slot's call (its first pass is over) whose lists overflowed, analysed again from
+// the rescue map in rounds; then the whole call ranked and packed again.  Once per enqueue of the call: sl.n_rescued.
+int f64_rescue(rt_handle *h, F64Slot &sl) {
+    F64State *f = h->f64;
+    if (sl.n_rescued >= 0) return RT_OK;
+    const int S = h->cfg.n_streams, N = f->N, T = sl.n_seg;
+    std::vector<int32_t> bad;
+    for (int s = 0; s < S; ++s)
+        if (sl.h_hot[s] > f->hot_cap) bad.push_back(s);  // (an absent stream reports 0 cells)
+    if (bad.empty() || T <= 0) {
+        sl.n_rescued = 0;
+        return RT_OK;
+    }
+    hipStream_t st = h->s_scan;
+    const int n_chunks = f64_sparse_chunks(T, f->chunk);
+    const F64RescueRounds rr = f64_rescue_rounds((int)bad.size(), T, N, kF64RescueBudget);
+    int rc = f64_rescue_area(h, f->d_rs_map, f->rs_map_bytes, (size_t)rr.per_round * (size_t)T * (size_t)N * sizeof(double));
+    if (rc == RT_OK) rc = f64_rescue_area(h, f->d_rs_partial, f->rs_partial_bytes, (size_t)rr.per_round * (size_t)n_chunks * (size_t)N * sizeof(double));
+    if (rc != RT_OK) return rc;
+    if (!f->d_rs_list && hipMalloc(&f->d_rs_list, (size_t)S * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        f->d_rs_list = nullptr;
+        return f64_err(h, RT_E_NOMEM, "RT_FLAG_F64_RESCUE: no device memory for the stream list");
+    }
+    const size_t lds = f64_scan_lds(f);
+    if (!f->rs_attr && lds > 64 * 1024) {
+        const void *scans[] = {(const void *)scan_map_f64<kFmtC64, 4>, (const void *)scan_map_f64<kFmtC64, 8>, (const void *)scan_map_f64<kFmtC64, 16>,
+                               (const void *)scan_map_f64<kFmtU8, 4>,  (const void *)scan_map_f64<kFmtU8, 8>,  (const void *)scan_map_f64<kFmtU8, 16>,
+                               (const void *)scan_map_f64<kFmtI16, 4>, (const void *)scan_map_f64<kFmtI16, 8>, (const void *)scan_map_f64<kFmtI16, 16>,
+                               (const void *)scan_map_f64<kFmtI8, 4>,  (const void *)scan_map_f64<kFmtI8, 8>,  (const void *)scan_map_f64<kFmtI8, 16>};
+        for (const void *fn : scans) RT_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    f->rs_attr = true;
+    // (blocking: the list lives on this function's stack; the kernels of a round before have read it by the time it is rewritten,
+    // because every rescue ends with a wait for the call's event)
+    RT_HIP(h, hipMemcpy(f->d_rs_list, bad.data(), bad.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    // clear_counts_sparse_f64 has zeroed the raw counters behind the first pass, the other streams' raw records are still in
+    // place: their counts back from the slot's meta block (an overflowing stream's is 0 there)
+    RT_HIP(h, hipMemcpyAsync(sl.d_raw_count, sl.h_meta + S + 1, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    F64ListArgs la{};
+    la.a = f64_detect_args(h, sl);
+    la.a.spec = f->d_rs_map;
+    la.partial = f->d_rs_partial;
+    la.n_chunks = n_chunks;
+    const int nb = N * f->group / kF64ScanBlock;
+    for (int r = 0; r < rr.rounds; ++r) {
+        const int first = r * rr.per_round;
+        const int n_list = std::min(rr.per_round, (int)bad.size() - first);
+        F64MapScanParams p{};
+        p.iq = sl.iq;
+        p.stream_stride = sl.stream_stride;
+        p.n_seg = T;
+        p.nperseg = N;
+        p.group = f->group;
+        p.chunk = f->chunk;
+        p.n_chunks = n_chunks;
+        p.n_list = n_list;
+        p.list = f->d_rs_list + first;
+        p.scale = f->c.scale;
+        p.window = f->d_window;
+        p.tw = f->d_tw;
+        p.map = f->d_rs_map;
+        p.partial = f->d_rs_partial;
+        const unsigned grid = (unsigned)((int64_t)n_list * n_chunks);
+        if (sl.fmt == kFmtU8) launch_scan_map_f64<kFmtU8>(p, nb, grid, lds, st);
+        else if (sl.fmt == kFmtI16) launch_scan_map_f64<kFmtI16>(p, nb, grid, lds, st);
+        else if (sl.fmt == kFmtI8) launch_scan_map_f64<kFmtI8>(p, nb, grid, lds, st);
+        else launch_scan_map_f64<kFmtC64>(p, nb, grid, lds, st);
+        la.list = p.list;
+        la.n_list = n_list;
+        const int64_t rows = (int64_t)n_list * N;
+        detect_list_f64<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(la);
+        stats_list_f64<<<(unsigned)n_list, 256, 0, st>>>(la);
+        RT_HIP(h, hipGetLastError());
+    }
+    finalize_sparse_f64<<<(unsigned)S, 256, 0, st>>>(la.a);
+    clear_counts_sparse_f64<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(sl.d_raw_count, sl.d_cell_count, S);
+    RT_HIP(h, hipGetLastError());
+    RT_HIP(h, hipEventRecord(sl.ev_done, st));
+    RT_HIP(h, hipEventSynchronize(sl.ev_done));
+    sl.n_rescued = (int)bad.size();
     return RT_OK;
 }
 
@@ -3250,6 +3368,9 @@ static void destroy_f64(rt_handle *h) {
     }
     (void)hipFree(f->d_partial);
     (void)hipFree(f->d_row_sums);
+    (void)hipFree(f->d_rs_map);
+    (void)hipFree(f->d_rs_partial);
+    (void)hipFree(f->d_rs_list);
     (void)hipFree(f->d_window);
     (void)hipFree(f->d_cwin);
     (void)hipFree(f->d_bfilt);
@@ -3372,6 +3493,8 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
         return fail_create(RT_E_INVALID, "RT_FLAG_F64_SPARSE on a float64 handle selects the path by itself: mode must be RT_MODE_AUTO");
     if (cfg->mode != RT_MODE_AUTO && cfg->mode != RT_MODE_DENSE)
         return fail_create(RT_E_UNSUPPORTED, "a float64 handle runs the dense path only: mode must be RT_MODE_AUTO or RT_MODE_DENSE");
+    if ((cfg->flags & RT_FLAG_F64_RESCUE) && !sparse)
+        return fail_create(RT_E_INVALID, "RT_FLAG_F64_RESCUE re-runs the overflowing streams of the map-free path: it needs RT_FLAG_F64_SPARSE");
     if (cfg->lanes > 1) return fail_create(RT_E_UNSUPPORTED, "a float64 handle has one launch sequence per call: lanes must be 0 or 1");
     if (sparse) {  // the map-free path (rt_f64_sparse.h): its own limits, the arithmetic in rt_core.h
         if (!f64_sparse_nperseg_ok(n))
@@ -3426,6 +3549,7 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
         f->chunk_cap = std::max(1, f64_sparse_chunks(f->max_seg, f->chunk));
         f->hot_cap = f64_sparse_hot_capacity(cfg->hot_capacity);
         f->sort_cap = next_pow2(f->hot_cap);
+        f->rescue = (cfg->flags & RT_FLAG_F64_RESCUE) != 0;
     }
 #define RT_F64_CREATE(expr)                                                               \
     do {                                                                                  \
@@ -3627,7 +3751,21 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     RT_HIP(h, hipSetDevice(h->cfg.device));
     RT_HIP(h, hipEventSynchronize(sl.ev_done));
     const bool sparse_call = f->sparse && !sl.is_extract;
-    if (sparse_call) {
+    const bool rescue_call = sparse_call && f->rescue;
+    // RT_FLAG_F64_RESCUE: the overflowing streams analysed again on their own.  A failure (RT_E_NOMEM: no scratch) consumes the
+    // call like an overflow without the flag; the look-back tail the call wrote stays the next call's.
+    const auto rescue = [&]() -> int {
+        const int rc = f64_rescue(h, sl);
+        if (rc != RT_OK) {
+            sl.pending = false;
+            f->rm_slot = kRowMeansNone;
+        }
+        return rc;
+    };
+    if (rescue_call) {
+        const int rc = rescue();
+        if (rc != RT_OK) return rc;
+    } else if (sparse_call) {
         // RT_FLAG_F64_SPARSE: a stream emitted more cells than its list holds -- no result, the call is consumed (as
         // RT_MODE_SPARSE on a float32 handle); the look-back tail the call wrote stays the next call's
         for (int s = 0; s < S; ++s)
@@ -3676,6 +3814,10 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
             return rc;
         }
         RT_HIP(h, hipEventSynchronize(sl.ev_done));
+        if (rescue_call) {  // (the whole call ran again: so do its overflowing streams)
+            rc = rescue();
+            if (rc != RT_OK) return rc;
+        }
     }
     const size_t total = (size_t)sl.h_meta[S];
     *n_out = total;
@@ -3683,6 +3825,11 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     h->info.n_seg = sl.n_seg;
     h->info.mode_used = sparse_call ? RT_MODE_SPARSE : RT_MODE_DENSE;
     h->info.n_records = (int64_t)total;
+    if (rescue_call) {
+        h->info.n_dense_streams = sl.n_rescued;
+        h->info.fell_back = sl.n_rescued > 0 ? 1 : 0;
+        for (int s = 0; s < S; ++s) h->info.n_hot += sl.h_hot[s];  // (the counters: cells emitted, not cells stored)
+    }
     if (total && (!out || !cap)) return truncated ? RT_E_CAPACITY : RT_OK;  // size query: the call stays pending
     const size_t n = std::min(total, cap);
     if (n) std::memcpy(out, sl.h_out, n * sizeof(rt_record_f64));

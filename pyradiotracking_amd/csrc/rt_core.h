@@ -354,6 +354,19 @@ inline int f64_sparse_chunk(int nperseg, int segs_per_chunk, int n_streams, int 
 }
 inline int f64_sparse_chunks(int n_seg, int L) { return n_seg <= 0 ? 0 : (n_seg + L - 1) / L; }
 inline int f64_sparse_last_chunk(int n_seg, int L) { return n_seg <= 0 ? 0 : n_seg - (f64_sparse_chunks(n_seg, L) - 1) * L; }
+// RT_FLAG_F64_RESCUE: the streams of a call whose lists overflowed are analysed again from a float64 map [slot][T][N] in a
+// scratch area of kF64RescueBudget bytes -- or one stream's map where that is larger --, as many streams a round as fit.
+constexpr int64_t kF64RescueBudget = 256ll << 20;
+struct F64RescueRounds {
+    int32_t per_round;  // streams a round takes at most (the last round: what is left)
+    int32_t rounds;
+};
+inline F64RescueRounds f64_rescue_rounds(int n_bad, int n_seg, int nperseg, int64_t budget) {
+    if (n_bad <= 0) return F64RescueRounds{0, 0};
+    const int64_t one = std::max<int64_t>(8, (int64_t)n_seg * nperseg * 8);
+    const int64_t fit = std::min<int64_t>(n_bad, std::max<int64_t>(1, budget / one));
+    return F64RescueRounds{(int32_t)fit, (int32_t)((n_bad + fit - 1) / fit)};
+}
 
 // ---- Streams that sit out a call (rt_set_present; host side of rt_analyze.hip, here so that the CPU suite can drive it) ----
 // In the reference every SDR is a SignalAnalyzer of its own: `_spectrogram_last` is the buffer ITS radio delivered before, whatever

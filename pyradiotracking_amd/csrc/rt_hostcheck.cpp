@@ -431,4 +431,73 @@ int hc_f64_sparse_chunk(int nperseg, int segs_per_chunk, int n_streams, int max_
 int hc_f64_sparse_chunks(int n_seg, int L) { return f64_sparse_chunks(n_seg, L); }
 int hc_f64_sparse_last_chunk(int n_seg, int L) { return f64_sparse_last_chunk(n_seg, L); }
 
+// ---- RT_FLAG_F64_RESCUE (rt_core.h: f64_rescue_rounds; kernels in rt_f64_rescue.h) ----
+long long hc_f64_rescue_budget(void) { return (long long)kF64RescueBudget; }
+// out[2]: streams per round, rounds
+void hc_f64_rescue_rounds(int n_bad, int n_seg, int nperseg, long long budget, int *out) {
+    const F64RescueRounds r = f64_rescue_rounds(n_bad, n_seg, nperseg, (int64_t)budget);
+    out[0] = r.per_round;
+    out[1] = r.rounds;
+}
+
+// The sequential twin of detect_list_f64 + stats_list_f64 + finalize_sparse_f64 for ONE stream: the dense row walk over the
+// stream's map spec[t * n_bins + f] with every row's sum GIVEN (row_sums[n_bins]: the scan's chunk-ordered fold, not a fresh
+// sum of the row) and the look-back as in hc_extract_f64.  Returns the number of records (written up to cap, ordered by
+// (fi, start)): byte for byte hc_extract_sparse_f64's on the list the emission rule makes of the same map.
+int hc_extract_rescue_f64(const double *spec, const double *row_sums, int n_seg, int n_bins, const double *last, int n_seg_last,
+                          int tail_cols, int nperseg, double fs, double thr, double snr, double cal_db, double min_d, double max_d,
+                          rt_record_f64 *out, int cap) {
+    DetectParams64 p;
+    p.n_seg = n_seg;
+    p.n_seg_last = last ? n_seg_last : -1;
+    p.tail_cols = last ? tail_cols : 0;
+    p.stride = probe_stride(nperseg, fs, min_d);
+    p.nperseg = nperseg;
+    p.thr = thr;
+    p.snr = snr;
+    p.cal_db = cal_db;
+    p.fs = fs;
+    p.min_d = min_d;
+    p.max_d = max_d;
+    std::vector<rt_record_f64> rec;
+    std::vector<long long> ts, du;
+    for (int fi = 0; fi < n_bins; ++fi) {
+        auto cur = [&](int t) -> double { return spec[(size_t)t * n_bins + fi]; };
+        auto prev = [&](int d) -> double { return last[(size_t)(n_seg_last - d) * n_bins + fi]; };
+        double avg = 0.0;
+        auto on_run = [&](int b, int e, double av) {
+            int start;
+            if (!gate_run(p, b, e, av, prev, &start)) return;
+            auto cell = [&](int32_t k) -> double {
+                const int32_t t = start + k;
+                return t < 0 ? prev(-t) : cur(t);
+            };
+            const RunStatsT<double> st = run_stats(e - start, cell);
+            rt_record_f64 r;
+            std::memset(&r, 0, sizeof r);
+            r.fi = fi;
+            r.start = start;
+            r.end = e;
+            r.max_p = st.max_p;
+            r.mean_p = st.mean_p;
+            r.std_db = st.std_db;
+            r.row_mean = av;
+            rec.push_back(r);
+            ts.push_back(timedelta_us(start_time(p, start)));
+            du.push_back(timedelta_us(run_duration(p, start, e)));
+        };
+        scan_dense_row(p, cur, row_sums[fi], &avg, on_run);
+    }
+    const int m = (int)rec.size();
+    std::vector<rt_record_f64> ordered((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        int rank, shadow;
+        rank_and_shadow(i, m, rec.data(), ts.data(), du.data(), cal_db, &rank, &shadow);
+        ordered[(size_t)rank] = rec[(size_t)i];
+        ordered[(size_t)rank].shadowed = shadow;
+    }
+    for (int i = 0; i < m && i < cap; ++i) out[i] = ordered[(size_t)i];
+    return m;
+}
+
 }  // extern "C"
