@@ -523,6 +523,49 @@ int rt_set_stream_settings_f64(rt_handle *h, const double *snr_threshold, const 
  */
 int rt_set_present(rt_handle *h, const uint8_t *present);
 
+/*
+ * ---- consecutive buffers of one recording in one call (additive within ABI version 6) ----
+ * A recording is one stream; analysed callback by callback it costs one rt_process* + rt_fetch per buffer.  What buffer k + 1
+ * needs from buffer k is only `_spectrogram_last` (analyze.py:268): the last K columns of buffer k, which every scan writes
+ * anyway.  rt_set_chain lets the streams of ONE call be consecutive buffers: a contiguous recording is [links][B] with
+ * stream_stride = B.
+ *   - grouping: links >= 2 groups the handle's streams into RUNS of `links` consecutive indices (run r = streams r * links ...
+ *     r * links + links - 1); n_streams % links != 0 is RT_E_INVALID.  Within one rt_process* call the present streams of a run
+ *     are consecutive buffers of one analyzer of the reference, in index order.
+ *   - look-back: the buffer at stream s looks back into the buffer of the nearest present stream before it in its run, in the
+ *     same call; its `start_min` (analyze.py:383) comes from that buffer's segment count, the call's.  A run's first present
+ *     stream looks back into the run's LAST present stream of the latest earlier call in which the run had a present stream,
+ *     with that call's segment count; it has no look-back if there was no such call.
+ *   - links 0 or 1 turns chaining off.  A call that changes the value forgets all look-back, as rt_reset.
+ *   - refused: RT_E_INVALID (the message says "pending") while unfetched calls are pending; RT_E_UNSUPPORTED on a float64 handle
+ *     and -- a limit of this version: lanes cut the streams into groups that a run may straddle -- on a handle created with
+ *     lanes > 1.  Both before any device work.  RT_E_NOMEM if the first call with links >= 2 cannot allocate its two
+ *     [n_streams][K][nperseg] float buffers (one per call slot).
+ *   - rt_reset_stream(h, s), a changed threshold, a changed setting keep their per-index meaning: the buffer at stream s of the
+ *     next call in which s is present starts without look-back -- a cut in the recording in front of it; the streams behind it
+ *     in the run chain on as usual.  rt_reset cuts in front of every run's first stream.
+ *   - uniform values per run: rt_set_stream_params / rt_set_stream_settings on a chained handle must give all streams of a run
+ *     the same threshold, calibration and settings (RT_E_INVALID otherwise, the message names the run), and rt_set_chain on a
+ *     handle whose current per-stream values differ inside a run is refused the same way: the sparse scans keep a look-back
+ *     cell iff the later cells pass the WRITING stream's threshold.
+ *   - rt_set_present works as documented for an absent stream's own row, records, row means and rt_call_info; the one
+ *     difference is who follows whom, as above.  Any mask is legal ("the last call of a recording has fewer buffers",
+ *     "recordings of different lengths in one batch").  n_samples and stream_stride stay per call: all links of a call have the
+ *     same length, a recording's short last buffer is one more call with one link present.
+ *   - unchanged: records (`stream` is the stream index, a negative `start` counts back from the end of the predecessor buffer),
+ *     RT_FLAG_ROW_MEANS, RT_FLAG_RECORD_CELLS (gathered through the look-back the detection read), every rt_mode, every nperseg
+ *     and input format of a float32 handle, two calls in flight, every re-analysis inside rt_fetch.  rt_extract, rt_spectrogram
+ *     and rt_calibrate_read ignore chaining.
+ *   - differences from `links` sequential calls of a plain handle: RT_MODE_RUNFILTER's quiet levels and the detrend guard's
+ *     marks stay per stream INDEX.  The quiet levels only steer selectivity and are verified per call, so the records are exact
+ *     either way.  A guard mark changes the form of the transform for that index from then on, so a chained run can differ in
+ *     float32 round-off from a sequential run after a mark.
+ *   - a handle on which the entry was never called with links >= 2 launches exactly what it launched before: no kernel, copy
+ *     or allocation is added and no kernel argument changes meaning.
+ * RT_E_INVALID as well: null handle, links < 0.
+ */
+int rt_set_chain(rt_handle *h, int32_t links);
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

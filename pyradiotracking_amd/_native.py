@@ -164,6 +164,7 @@ ABI_SYMBOLS = (
     "rt_set_stream_settings",
     "rt_set_stream_settings_f64",
     "rt_set_present",
+    "rt_set_chain",
 )
 
 _lib = None
@@ -235,6 +236,7 @@ def load_library(path: Optional[str] = None):
     lib.rt_set_stream_settings.argtypes = [vp, vp, vp, vp]
     lib.rt_set_stream_settings_f64.argtypes = [vp, vp, vp, vp]
     lib.rt_set_present.argtypes = [vp, vp]
+    lib.rt_set_chain.argtypes = [vp, C.c_int32]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -475,6 +477,12 @@ class NativeAnalyzer:
         if m.shape != (self.n_streams,):
             raise ValueError(f"expected {self.n_streams} flags")
         self._check(self._lib.rt_set_present(self._handle, m.ctypes.data))
+
+    def set_chain(self, links: int):
+        """``rt_set_chain``: ``links >= 2`` groups the streams into runs of ``links`` consecutive indices whose present streams
+        are, within one call, consecutive buffers of one recording (stream ``s`` looks back into its predecessor of the same
+        call); 0 or 1 turns it off.  Refused with calls pending, on a float64 handle and on a handle with ``lanes > 1``."""
+        self._check(self._lib.rt_set_chain(self._handle, int(links)))
 
     # -- analysis ---------------------------------------------------------
     def process_device(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):

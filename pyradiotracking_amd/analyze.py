@@ -266,6 +266,8 @@ class BatchSignalAnalyzer:
     HBM inside the native handle.
     """
 
+    chain = 0  # links per run (``chain=L``), 0: every stream is a device of its own
+
     def __init__(
         self,
         devices: Sequence[str],
@@ -295,9 +297,20 @@ class BatchSignalAnalyzer:
         record_cells: bool = False,
         f64_sparse: bool = False,
         f64_rescue: bool = False,
+        chain: int = 0,
         **kwargs,
     ):
-        """``record_cells`` (``RT_FLAG_RECORD_CELLS``): keep the spectrogram cells every record of a call consists of -- the
+        """``chain=L`` (``rt_set_chain``, ``L >= 2``): every device is a RECORDING, analysed ``L`` consecutive buffers per call.
+        The handle has ``len(devices) * L`` streams -- run ``r`` (streams ``r * L ... r * L + L - 1``, :meth:`run_of` /
+        :meth:`link_of`) holds device ``r``'s buffers of a call in time order, each looking back into the one before it, the
+        first into the run's last buffer of the call before.  ``devices`` then lists every STREAM's device name (each name ``L``
+        times), ``run_devices`` the names as given; per-device values are repeated over the run.  ``enqueue*`` take
+        ``[R, l * B]`` with ``l <= L`` (``links=l``, or ``B = sdr_callback_length``; ``l < L``: the run's last ``L - l``
+        streams sit the call out), :meth:`process_batch` returns per device the signals of all its links in time order.
+        ``lanes`` is 1 (an explicit ``lanes > 1``: ``ValueError``, a run could straddle two lanes), and so is
+        ``precision="float64"``.
+
+        ``record_cells`` (``RT_FLAG_RECORD_CELLS``): keep the spectrogram cells every record of a call consists of -- the
         reference's ``data`` (analyze.py:437-440), which it reduces to max / mean / std and drops -- for
         :meth:`fetch_record_cells`.
 
@@ -357,6 +370,23 @@ class BatchSignalAnalyzer:
         envelope of the durations -- the smallest minimum, the largest maximum: look-back depth and pre-filters derive from it
         -- and every stream is gated by its own values (``rt_set_stream_settings``); :meth:`set_stream_settings` changes them
         later, inside that envelope."""
+        self.run_devices = [str(d) for d in devices]
+        self.chain = int(chain) if chain and int(chain) >= 2 else 0
+        self._chain_call = (self.chain, 0)  # links and samples per link of the buffer enqueued last
+        if self.chain:
+            if precision == "float64":
+                raise ValueError("chain is not available with precision='float64'")
+            if lanes != "auto" and int(lanes) > 1:
+                raise ValueError("chain needs lanes=1: lanes cut the streams into groups that a run may straddle")
+            lanes = 1
+
+            def over_run(v):  # a per-device sequence -> one value per stream
+                return [x for x in v for _ in range(self.chain)] if np.ndim(v) else v
+
+            devices = over_run(self.run_devices)
+            calibration_db, center_freq = over_run(calibration_db), over_run(center_freq)
+            signal_threshold_dbw, snr_threshold_db = over_run(signal_threshold_dbw), over_run(snr_threshold_db)
+            signal_min_duration_ms, signal_max_duration_ms = over_run(signal_min_duration_ms), over_run(signal_max_duration_ms)
         self.devices = [str(d) for d in devices]
         # (a sequence of the wrong length is refused before anything native is touched)
         per_thr = _per_stream("signal_threshold_dbw", signal_threshold_dbw, self.devices)
@@ -457,6 +487,8 @@ class BatchSignalAnalyzer:
                 self._native.set_stream_params(np.array(self.signal_threshold, dtype=np.float64).astype(np.float32), cal_arr)
         if per_snr is not None or per_min is not None or per_max is not None:
             self._push_stream_settings()
+        if self.chain:
+            self._native.set_chain(self.chain)
         self._decoder = _RecordDecoder(fft_nperseg, sample_rate, self.center_freq, self.calibration_db, f64=f64)
         self.decoder = self._decoder  # record -> field conversion, shared with pyradiotracking_amd.match
         self.gpu = gpu
@@ -530,6 +562,8 @@ class BatchSignalAnalyzer:
         n = len(self.devices)
 
         def values(name, v, conv):
+            if self.chain and np.ndim(v) and len(v) == len(self.run_devices):
+                v = [x for x in v for _ in range(self.chain)]  # one value per recording: the same for every link of its run
             per = _per_stream(name, v, self.devices)
             return [conv(x) for x in (per if per is not None else [v] * n)]
 
@@ -545,6 +579,59 @@ class BatchSignalAnalyzer:
         except Exception:
             self.snr_threshold, self.signal_min_duration, self.signal_max_duration = old
             raise
+
+    # -- chain=L: consecutive buffers of a recording as the streams of a call ------------------------------------------
+    def run_of(self, stream):
+        """The recording (index into ``run_devices``) stream ``stream`` belongs to; arrays as well (``rec["stream"]``)."""
+        return stream // self.chain if self.chain else stream
+
+    def link_of(self, stream):
+        """The buffer number of ``stream`` inside its call (0 = the earliest); arrays as well."""
+        return stream % self.chain if self.chain else stream * 0
+
+    def _chain_rows(self, x, per_sample: int, links: Optional[int], n_samples: Optional[int] = None):
+        """``[R, l * B]`` (``per_sample`` array elements a sample) -> the handle's ``[R * L, B]`` rows, link ``j`` of device ``r`` at
+        row ``r * L + j``; ``l < L`` sets the suffix mask.  A raw device pointer is the caller's ``[R * L, stride]`` already."""
+        L, R = self.chain, len(self.run_devices)
+        if isinstance(x, int):
+            l = L if links is None else int(links)
+            if not 0 <= l <= L:
+                raise ValueError(f"links must be 0 ... {L}")
+            self._set_links(l, n_samples)
+            return x
+        is_np = isinstance(x, np.ndarray)
+        if (x.ndim if is_np else x.dim()) == 1:
+            x = x[None, :]
+        if x.shape[0] != R or x.shape[1] % per_sample:
+            raise ValueError(f"expected [{R}, links * B] samples: one row per recording")
+        n, b0 = x.shape[1] // per_sample, self.sdr_callback_length
+        if links is None:
+            if n > b0 and n % b0:
+                raise ValueError(f"{n} samples are no whole number of buffers of sdr_callback_length {b0}: pass links=")
+            l = 1 if n <= b0 else n // b0
+        else:
+            l = int(links)
+            if l < 1 or n % l:
+                raise ValueError(f"{n} samples do not divide into links={links} buffers")
+        if l > L:
+            raise ValueError(f"{l} buffers per recording, the analyzer chains {L}")
+        width = n // l * per_sample
+        self._set_links(l, n // l)
+        x = np.ascontiguousarray(x) if is_np else x.contiguous()
+        if l == L:
+            return x.reshape(R * L, width)
+        if is_np:
+            rows = np.zeros((R, L, width), dtype=x.dtype)
+        else:
+            import torch
+
+            rows = torch.zeros((R, L, width), dtype=x.dtype, device=x.device)
+        rows[:, :l] = x.reshape(R, l, width)
+        return rows.reshape(R * L, width)
+
+    def _set_links(self, l: int, n_samples: Optional[int]):
+        self._chain_call = (l, n_samples)
+        self.set_present([j < l for _ in self.run_devices for j in range(self.chain)])
 
     def close(self):
         """Destroy the native handle (waits for everything in flight), then let go of the device tensors the
@@ -572,12 +659,19 @@ class BatchSignalAnalyzer:
         else:
             self._native.process_device(ptr, n_samples, stride)
 
-    def enqueue(self, iq, n_samples: Optional[int] = None, stream_stride: Optional[int] = None):
+    def enqueue(self, iq, n_samples: Optional[int] = None, stream_stride: Optional[int] = None, links: Optional[int] = None):
         """Start analysing one buffer per stream (asynchronous).
 
         ``iq``: a CUDA/HIP torch tensor ``[S, B]`` complex64, a raw device
         pointer (int, with ``n_samples``), or a host ndarray ``[S, B]``.
+        With ``chain=L``: ``[R, links * B]``, one row per recording (a device pointer: ``[R * L, stream_stride]`` with
+        ``n_samples = B`` and ``links``); so for the other formats below.
         """
+        if self.chain:
+            if isinstance(iq, np.ndarray) and iq.dtype == np.uint8:
+                self.enqueue_bytes(iq, links=links)
+                return
+            iq = self._chain_rows(iq, 1, links, n_samples)
         if isinstance(iq, int):
             if n_samples is None:
                 raise ValueError("n_samples is required with a raw device pointer")
@@ -609,12 +703,14 @@ class BatchSignalAnalyzer:
             torch.cuda.current_stream(iq.device).synchronize()
         self._process_device(iq.data_ptr(), iq.shape[1], iq.stride(0) if iq.shape[0] > 1 else iq.shape[1], iq.element_size(), False)
 
-    def enqueue_bytes(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None):
+    def enqueue_bytes(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None, links: Optional[int] = None):
         """Same as :meth:`enqueue` for the RTL-SDR wire format: interleaved uint8 I, Q (what
         librtlsdr delivers; pyrtlsdr's ``packed_bytes_to_iq`` turns it into the complex buffer
         the reference's callback sees).  ``raw``: host ndarray / CUDA torch tensor of uint8 shaped
         ``[S, 2*B]`` (or ``[2*B]`` for one stream), or a raw device pointer with ``n_samples``.
         The byte -> float conversion is fused into the scan kernel's load."""
+        if self.chain:
+            raw = self._chain_rows(raw, 2, links, n_samples)
         if isinstance(raw, int):
             if n_samples is None:
                 raise ValueError("n_samples is required with a raw device pointer")
@@ -643,12 +739,14 @@ class BatchSignalAnalyzer:
         stride = (raw.stride(0) if raw.shape[0] > 1 else raw.shape[1]) // 2
         self._process_device(raw.data_ptr(), raw.shape[1] // 2, stride, 2, True)
 
-    def enqueue_int16(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None):
+    def enqueue_int16(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None, links: Optional[int] = None):
         """Same as :meth:`enqueue` for 16-bit signed IQ (SoapySDR ``CS16``, UHD ``sc16``, SigMF ``ci16_le``): interleaved
         little-endian int16 I, Q, a component's value ``i * 2**-15``.  ``raw``: host ndarray / CUDA torch tensor of int16 shaped
         ``[S, 2*B]`` (or ``[2*B]`` for one stream), or a raw device pointer (4-byte aligned) with ``n_samples``.  The conversion
         is exact and fused into the scan kernel's load: the results are those of :meth:`enqueue` on
         ``synth.i16_to_complex64(raw)`` (``i16_to_complex128`` on a float64 analyzer), byte for byte."""
+        if self.chain:
+            raw = self._chain_rows(raw, 2, links, n_samples)
         if isinstance(raw, int):
             if n_samples is None:
                 raise ValueError("n_samples is required with a raw device pointer")
@@ -683,12 +781,14 @@ class BatchSignalAnalyzer:
         stride = (raw.stride(0) if raw.shape[0] > 1 else raw.shape[1]) // 2
         self._process_device(raw.data_ptr(), raw.shape[1] // 2, stride, 4, False, True)
 
-    def enqueue_int8(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None):
+    def enqueue_int8(self, raw, n_samples: Optional[int] = None, stream_stride: Optional[int] = None, links: Optional[int] = None):
         """Same as :meth:`enqueue` for 8-bit signed IQ (HackRF's native format, SoapySDR ``CS8``, UHD ``sc8``, SigMF ``ci8``):
         interleaved two's-complement int8 I, Q, a component's value ``i * 2**-7``.  ``raw``: host ndarray / CUDA torch tensor of int8
         shaped ``[S, 2*B]`` (or ``[2*B]`` for one stream), or a raw device pointer (2-byte aligned) with ``n_samples``.  The conversion
         is exact and fused into the scan kernel's load: the results are those of :meth:`enqueue` on
         ``synth.i8_to_complex64(raw)`` (``i8_to_complex128`` on a float64 analyzer), byte for byte."""
+        if self.chain:
+            raw = self._chain_rows(raw, 2, links, n_samples)
         if isinstance(raw, int):
             if n_samples is None:
                 raise ValueError("n_samples is required with a raw device pointer")
@@ -751,7 +851,8 @@ class BatchSignalAnalyzer:
         out = self._native.fetch_row_means()
         return self._decoder.noise_dbw(out) if dbw else out
 
-    def process_batch(self, iq, ts_starts: Union[datetime.datetime, Sequence[datetime.datetime]], filtered: bool = True, lazy: bool = True):
+    def process_batch(self, iq, ts_starts: Union[datetime.datetime, Sequence[datetime.datetime]], filtered: bool = True, lazy: bool = True,
+                      links: Optional[int] = None):
         """One buffer per stream -> per stream a sequence of ``Signal``.
 
         ``filtered=True`` returns what the reference puts on its queue
@@ -761,9 +862,17 @@ class BatchSignalAnalyzer:
         ``lazy`` (default): every stream's sequence is a :class:`SignalBatch` -- the nine field columns of the whole call are built
         at once, a ``Signal`` object only when an element is asked for (it compares equal to the list of those objects; 2.6 x the
         rate of building every object up front, and a consumer that hands columns on -- CSV rows, the matcher -- never needs
-        them).  ``lazy=False``: plain lists of ``Signal`` objects."""
-        self.enqueue(iq)
+        them).  ``lazy=False``: plain lists of ``Signal`` objects.
+
+        With ``chain=L``: ``iq`` is ``[R, l * B]`` and ``ts_starts`` holds one time per recording, the start of its first
+        buffer of this call; the result is per RECORDING, the signals of its ``l`` buffers in time order -- what ``l``
+        consecutive ``SignalAnalyzer.process_samples`` callbacks put on the queue.  Buffer ``j`` starts at ``ts_start + j *
+        timedelta(seconds=B / sample_rate)``: the reference's running clock adds that ``timedelta`` once per callback
+        (analyze.py:205, 221, 231), and ``timedelta`` arithmetic is exact."""
+        self.enqueue(iq, links=links)
         rec = self.fetch_records()
+        if self.chain:
+            return self._chained_signals(rec, ts_starts, filtered, lazy)
         if isinstance(ts_starts, datetime.datetime):
             ts_starts = [ts_starts] * len(self.devices)
         if filtered:
@@ -775,6 +884,24 @@ class BatchSignalAnalyzer:
             return [batch[int(bounds[s]):int(bounds[s + 1])] for s in range(len(self.devices))]
         sigs = self._decoder.signals(rec, self.devices, ts_starts)
         return [sigs[int(bounds[s]):int(bounds[s + 1])] for s in range(len(self.devices))]
+
+
+    def _chained_signals(self, rec, ts_starts, filtered: bool, lazy: bool):
+        """``process_batch`` of a chained analyzer: the fetched records -> per recording its signals, links in time order."""
+        L, R = self.chain, len(self.run_devices)
+        if isinstance(ts_starts, datetime.datetime):
+            ts_starts = [ts_starts] * R
+        if len(ts_starts) != R:
+            raise ValueError(f"expected {R} start times: one per recording")
+        l, n = self._chain_call
+        step = datetime.timedelta(seconds=(n or 0) / self.sample_rate)  # analyze.py:205
+        ts_streams = [ts_starts[r] + j * step for r in range(R) for j in range(L)]  # :221, :231
+        if filtered:
+            rec = rec[rec["shadowed"] == 0]
+        # (records come ordered by stream, i.e. by recording and inside it by link: a recording's signals are one slice)
+        bounds = np.searchsorted(rec["stream"], np.arange(R + 1) * L)
+        sigs = self._decoder.signal_batch(rec, self.devices, ts_streams) if lazy else self._decoder.signals(rec, self.devices, ts_streams)
+        return [sigs[int(bounds[r]):int(bounds[r + 1])] for r in range(R)]
 
 
 class SignalAnalyzer:
@@ -863,6 +990,13 @@ class SignalAnalyzer:
 
         self._spectrogram_last = None  # only used by extract_signals() called directly
         self._ts = None
+        self._replay_batch = None  # (replay: a chained analyzer of its own, made at first use)
+        self._replay_kw = dict(
+            calibration_db=calibration_db, sample_rate=sample_rate, center_freq=center_freq, fft_nperseg=fft_nperseg, fft_window=fft_window,
+            signal_min_duration_ms=signal_min_duration_ms, signal_max_duration_ms=signal_max_duration_ms, signal_threshold_dbw=signal_threshold_dbw,
+            snr_threshold_db=snr_threshold_db, sdr_callback_length=sdr_callback_length, gpu=gpu, mode=mode,
+            **{k: kwargs[k] for k in ("record_capacity", "record_pool", "hot_capacity", "group_detect") if k in kwargs},
+        )
         self._batch = BatchSignalAnalyzer(
             [device],
             calibration_db=calibration_db,
@@ -1022,6 +1156,53 @@ class SignalAnalyzer:
             f"SDR {self.device} recv {len(buffer)}, {len(out)} signals, "
             f"compute: {(time.time() - bench_start) * 1000:.1f} ms"
         )
+        return out
+
+    def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64") -> List[Signal]:
+        """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
+        instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
+        (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
+        ``"i16"`` / ``"i8"``) on a fresh analyzer once per buffer, in that order, with a clock that starts at ``ts_start``.
+        ``samples``: one array, complex for ``"c64"``, else interleaved I, Q.  The last call has fewer links; a remainder
+        shorter than a buffer is one more call if it holds at least two segments, else it is dropped with a log line (nothing
+        could be detected in it).  Every replay starts without look-back; the analyzer's own callback state is left alone."""
+        per_sample = {"c64": 1, "u8": 2, "i16": 2, "i8": 2}[fmt]
+        want = {"c64": np.complex64, "u8": np.uint8, "i16": np.int16, "i8": np.int8}[fmt]
+        x = np.asarray(samples).reshape(-1)
+        if fmt == "c64":
+            x = np.ascontiguousarray(x, dtype=np.complex64)
+        elif x.dtype != want or x.size % 2:
+            raise TypeError(f"fmt {fmt!r} takes an interleaved {np.dtype(want).name} array [2 * n]")
+        if self.precision == "float64":
+            raise ValueError("replay is not available with precision='float64'")
+        if int(chain) < 2:
+            raise ValueError("chain must be >= 2")
+        if self._replay_batch is None or self._replay_batch.chain != int(chain):
+            if self._replay_batch is not None:
+                self._replay_batch.close()
+            self._replay_batch = BatchSignalAnalyzer([self.device], chain=int(chain), **self._replay_kw)
+        batch = self._replay_batch
+        batch.reset()
+        enqueue = {"c64": batch.enqueue, "u8": batch.enqueue_bytes, "i16": batch.enqueue_int16, "i8": batch.enqueue_int8}[fmt]
+        B, L = batch.sdr_callback_length, int(chain)
+        n = x.size // per_sample
+        n_full, rest = divmod(n, B)
+        step = datetime.timedelta(seconds=B / self.sample_rate)  # analyze.py:205
+        out: List[Signal] = []
+
+        def call(first: int, links: int, length: int):
+            part = x[first * B * per_sample:(first * B + links * length) * per_sample]
+            enqueue(part.reshape(1, -1), links=links)
+            rec = batch.fetch_records()
+            out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
+
+        for first in range(0, n_full, L):
+            call(first, min(L, n_full - first), B)
+        if rest >= 2 * self.fft_nperseg:
+            call(n_full, 1, rest)
+        elif rest:
+            logger.info(f"SDR {self.device} replay: the last {rest} samples hold fewer than two segments and are dropped")
+        [self.consume_signal(s) for s in out]
         return out
 
     def _keep_noise(self):

@@ -35,6 +35,7 @@
 #include "rt_f64_rescue.h"
 #include "rt_cells.h"
 #include "rt_present.h"
+#include "rt_chain.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -90,6 +91,7 @@ struct CallCtx {
     uint64_t sub_epoch = 0;   // rt_handle::sub_epoch when its kernels were enqueued
     int cells_grown = 0;      // times the slot's cell pool was enlarged for this call and the call analysed again (RT_FLAG_RECORD_CELLS)
     bool masked = false;      // enqueued on a handle with a presence mask (rt_set_present): the slot's `pc` and mask arrays are this call's
+    bool chained = false;     // enqueued on a chained handle (rt_set_chain): the slot's `cc`, chain rows and d_chain are this call's
     // handle state before this call (restored when the call is rolled back: a later lane failed to enqueue)
     int prev_tail_cur = 0, prev_n_seg_last = -1, prev_dense_sticky = 0, prev_minsum_slot = -1;
 };
@@ -141,6 +143,12 @@ struct Slot {
     PresenceCall pc;
     int32_t *h_mask = nullptr, *d_mask = nullptr;
     int n_lin_present = 0, n_sub_present = 0, n_absent = 0;  // entries of the rows kMaskLinList / kMaskSubList / kMaskAbsentList
+    // rt_set_chain only (allocated by the handle's first call of the entry with links >= 2).  The sources a call was enqueued with
+    // (rt_core.h: ChainCall), their device form -- two rows of [S]: ChainCall::src_buf, src_idx (pinned copy beside it) -- and the
+    // look-back columns its detection reads, [S][K][N] as a rotation buffer (rt_chain.h: chain_tails writes them):
+    ChainCall cc;
+    int32_t *h_chain_rows = nullptr, *d_chain_rows = nullptr;
+    float *d_chain = nullptr;
     hipEvent_t ev_begin = nullptr, ev_first = nullptr, ev_scan = nullptr, ev_done = nullptr;  // first launch; end of the first scan; end of the scans; end of the call
     CallCtx call;
 };
@@ -337,6 +345,9 @@ struct rt_handle {
     PresenceBook pres;
     size_t chunk_min_bytes = 0;         // bytes of a slot's d_chunk_min (0: none)
     const Slot *launch_mask = nullptr;  // while a masked call's kernels are being enqueued: the slot whose mask rows its scans take (launch_stft)
+    // rt_set_chain (rt_core.h: ChainBook): off -- and nothing of it used -- until the entry is called with links >= 2
+    ChainBook chain;
+    std::vector<float> h_cal_s;  // host copy of the per-stream calibration (empty: rt_config's for every stream): rt_set_chain's uniformity check
 
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
 };
@@ -718,6 +729,24 @@ int enqueue_row_means(rt_handle *h, Slot &sl, int chunks, int n_seg, hipStream_t
     return RT_OK;
 }
 
+// ---- rt_set_chain: the look-back a call's detection (and its cell gather) reads, and the copy that fills it ----
+// The slot's chained columns if the call is chained, else the rotation buffer the call reads.
+const float *call_prev(rt_handle *h, const Slot &sl) { return sl.call.chained ? sl.d_chain : h->d_tail[sl.call.tail_read]; }
+
+// chain_tails for the call of `sl` on `st`: behind the scans of this analysis (they write the rotation buffer the copy reads for
+// every stream that follows one of the same call), in front of its detection.  Every analysis of the call runs it again: a
+// level-up or a subtract-first re-run rewrites the columns, some with other bits.  Nothing for a call that is not chained.
+int enqueue_chain(rt_handle *h, Slot &sl, hipStream_t st) {
+    const CallCtx &c = sl.call;
+    const int64_t per = (int64_t)h->K * h->N;
+    if (!c.chained || per <= 0) return RT_OK;
+    const int S = h->cfg.n_streams, bps = chain_blocks<float>(per);
+    hipLaunchKernelGGL((chain_tails<float>), dim3((unsigned)((int64_t)S * bps)), dim3(kChainBlock), 0, st, sl.d_chain_rows, sl.d_chain_rows + S, S, bps,
+                       h->d_tail[c.tail_write], h->d_tail[c.tail_read], sl.d_chain, per);
+    RT_HIP(h, hipGetLastError());
+    return RT_OK;
+}
+
 // RT_FLAG_RECORD_CELLS: the cells of the call's final records (rt_cells.h) into the slot's pool -- where enqueue_row_means is
 // called, on the same stream behind the call's detection: the dense map is one per handle and belongs to the next call as soon
 // as this one's kernels are through, so the gather is never left to fetch time.  `spec`: the dense map the detection read
@@ -745,7 +774,7 @@ int enqueue_record_cells(rt_handle *h, Slot &sl, const float *spec, const int32_
     a.spec = spec;
     a.stream_list = stream_list;
     a.n_list = n_list;
-    a.prev = h->d_tail[c.tail_read];
+    a.prev = call_prev(h, sl);
     a.prev_cols = h->K;
     a.hot = sl.d_hot;
     a.hot_count = sl.d_hot_kept;
@@ -852,6 +881,15 @@ int upload_mask(rt_handle *h, Slot &sl) {
     return RT_OK;
 }
 
+// rt_set_chain: the call's source rows to the device (once per call: a re-analysis reads them again).  As upload_mask.
+int upload_chain_rows(rt_handle *h, Slot &sl) {
+    const size_t S = (size_t)h->cfg.n_streams;
+    std::memcpy(sl.h_chain_rows, sl.cc.src_buf.data(), S * sizeof(int32_t));
+    std::memcpy(sl.h_chain_rows + S, sl.cc.src_idx.data(), S * sizeof(int32_t));
+    RT_HIP(h, hipMemcpyAsync(sl.d_chain_rows, sl.h_chain_rows, 2 * S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
+    return RT_OK;
+}
+
 // The absent streams' K look-back columns from the rotation buffer the call reads to the one it writes, on the scan's stream, where
 // the scan's own tail stores are (rt_present.h).  Once per call: a re-analysis finds them in place.
 template <class P>
@@ -892,9 +930,10 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
             hipLaunchKernelGGL(row_sums_dense, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->s_scan, h->d_spec, sl.d_psum, h->cfg.n_streams, c.n_seg, h->N);
         }
         RT_HIP(h, hipGetLastError());
+        { const int rc2 = enqueue_chain(h, sl, h->s_scan); if (rc2 != RT_OK) return rc2; }
         RT_HIP(h, hipEventRecord(sl.ev_scan, h->s_scan));
         DetectArgs a = make_detect_args(h, sl, c.n_seg, h->N, c.n_seg_last);
-        a.prev = h->d_tail[c.tail_read];
+        a.prev = call_prev(h, sl);
         a.prev_cols = h->K;
         a.spec = h->d_spec;
         a.psum = sl.d_psum;  // one partial row per stream (row_sums_dense)
@@ -1091,10 +1130,12 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
     RT_HIP(h, hipGetLastError());
     // (ev_scan: the end of the call's scans -- on `sd` where a second scan ran there)
     const bool two_scans = !dense && (mode == RT_MODE_RUNFILTER || mode == RT_MODE_PREFILTER);
+    // (rt_set_chain: behind the call's last scan, where ev_scan is recorded -- s2 is behind the first scan, which wrote the columns)
+    { const int rc = enqueue_chain(h, sl, two_scans ? s2 : h->s_scan); if (rc != RT_OK) return rc; }
     RT_HIP(h, hipEventRecord(sl.ev_scan, two_scans ? s2 : h->s_scan));
     if (sd != (two_scans ? s2 : h->s_scan)) RT_HIP(h, hipStreamWaitEvent(sd, sl.ev_scan, 0));
     DetectArgs a = make_detect_args(h, sl, c.n_seg, h->N, c.n_seg_last);
-    a.prev = h->d_tail[c.tail_read];
+    a.prev = call_prev(h, sl);
     a.prev_cols = h->K;
     a.chunks = sp.blocks_per_stream;
     a.spec = h->d_spec;
@@ -1154,8 +1195,9 @@ int enqueue_partial_dense(rt_handle *h, Slot &sl, int n_list, unsigned long long
     RT_HIP(h, hipMemcpyAsync(sl.d_counters, sl.h_total, sizeof(unsigned long long), hipMemcpyHostToDevice, h->s_scan));
     launch_scan<1>(h, sp, n_list * sp.blocks_per_stream, c.fmt);
     RT_HIP(h, hipGetLastError());
+    { const int rc = enqueue_chain(h, sl, h->s_scan); if (rc != RT_OK) return rc; }  // (the dense scan rewrote the listed streams' columns)
     DetectArgs a = make_detect_args(h, sl, c.n_seg, h->N, c.n_seg_last);
-    a.prev = h->d_tail[c.tail_read];
+    a.prev = call_prev(h, sl);
     a.prev_cols = h->K;
     a.chunks = sp.blocks_per_stream;
     a.spec = h->d_spec_part;
@@ -1271,6 +1313,7 @@ void rollback_newest(rt_handle *h) {
             h->pres.rollback(best->pc, h->reset_pending);
             h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
         }
+        if (c.chained) h->chain.rollback(best->cc);
     }
     best->call = CallCtx{};
     h->n_calls--;
@@ -1366,6 +1409,31 @@ static int check_stream_settings(rt_handle *h, const char *what, const P *snr, c
         }
     }
     return RT_OK;
+}
+
+// rt_set_chain: the streams of a run are buffers of ONE analyzer, so per-stream values must not differ inside a run (the sparse
+// scans write a look-back cell iff the later cells pass the WRITING stream's threshold: a reader with a lower one could walk onto
+// a cell that was never stored).  Each array [S] or null (= the handle's one value for every stream).
+static int chain_runs_uniform(rt_handle *h, const ChainBook &book, const char *what, const float *thr, const float *cal, const float *snr,
+                              const double *min_d, const double *max_d) {
+    if (!book.on()) return RT_OK;
+    const char *name = nullptr;
+    int r = -1;
+    auto look = [&](int run, const char *n) {
+        if (r < 0 && run >= 0) {
+            r = run;
+            name = n;
+        }
+    };
+    if (thr) look(book.first_mixed_run(thr), "threshold");
+    if (cal) look(book.first_mixed_run(cal), "calibration_db");
+    if (snr) look(book.first_mixed_run(snr), "snr_threshold");
+    if (min_d) look(book.first_mixed_run(min_d), "min_duration_s");
+    if (max_d) look(book.first_mixed_run(max_d), "max_duration_s");
+    if (r < 0) return RT_OK;
+    h->err = std::string(what) + ": run " + std::to_string(r) + " (streams " + std::to_string(r * book.links) + " ... " +
+             std::to_string((r + 1) * book.links - 1) + "): " + name + " differs inside the run; the streams of a chained run are buffers of one recording";
+    return RT_E_INVALID;
 }
 
 // ... and the table itself: `cur` becomes the new settings (empty: all three arrays null), `changed[s]` says whether stream s's differ from before
@@ -1471,6 +1539,9 @@ void rt_destroy(rt_handle *h) {
         (void)hipHostFree(sl.h_no_last);
         (void)hipHostFree(sl.h_mask);
         (void)hipFree(sl.d_mask);
+        (void)hipHostFree(sl.h_chain_rows);
+        (void)hipFree(sl.d_chain_rows);
+        (void)hipFree(sl.d_chain);
         (void)hipHostFree(sl.h_overflow);
         (void)hipHostFree(sl.h_incons);
         (void)hipHostFree(sl.h_dc_flag);
@@ -1872,6 +1943,7 @@ int rt_reset(rt_handle *h) {
     for (rt_handle *k : h->kids) rt_reset(k);
     h->n_seg_last = -1;
     if (h->pres.active) h->pres.forget_all();
+    h->chain.forget_all();
     std::fill(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)0);
     h->any_reset_pending = false;
     return RT_OK;
@@ -1915,6 +1987,7 @@ int rt_set_stream_params(rt_handle *h, const float *threshold, const float *cali
         h->err = "rt_set_stream_params with unfetched calls pending: fetch them first";
         return RT_E_INVALID;
     }
+    { const int rcu = chain_runs_uniform(h, h->chain, "rt_set_stream_params", threshold, calibration_db, nullptr, nullptr, nullptr); if (rcu != RT_OK) return rcu; }
     RT_HIP(h, hipSetDevice(h->cfg.device));
     // kernels in flight read the arrays: let them finish first (a configuration call, not on the hot path)
     RT_HIP(h, hipStreamSynchronize(h->s_scan));
@@ -1942,6 +2015,7 @@ int rt_set_stream_params(rt_handle *h, const float *threshold, const float *cali
         }
     }
     if (threshold) h->h_thr_s.assign(threshold, threshold + h->cfg.n_streams); else h->h_thr_s.clear();
+    if (calibration_db) h->h_cal_s.assign(calibration_db, calibration_db + h->cfg.n_streams); else h->h_cal_s.clear();
     int rc = put(h->d_thr_s, threshold);
     if (rc != RT_OK) return rc;
     return put(h->d_cal_s, calibration_db);
@@ -1979,6 +2053,7 @@ int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const doubl
     // stream as the caller counts it -- the lanes share rt_config's envelope), then the pending calls
     const int rc = check_stream_settings<float>(h, "rt_set_stream_settings", snr_threshold, min_duration_s, max_duration_s);
     if (rc != RT_OK) return rc;
+    { const int rcu = chain_runs_uniform(h, h->chain, "rt_set_stream_settings", nullptr, nullptr, snr_threshold, min_duration_s, max_duration_s); if (rcu != RT_OK) return rcu; }
     bool pending = h->kids.empty() && oldest_pending(h);
     for (rt_handle *k : h->kids) pending = pending || oldest_pending(k);
     if (pending) {
@@ -2038,6 +2113,81 @@ int rt_set_present(rt_handle *h, const uint8_t *present) {
     }
     book.set_mask(present);
     return RT_OK;
+}
+
+// rt_set_chain (include/rt_analyze.h).  Every refusal comes before any device work.  The first call with links >= 2 moves the
+// handle to the per-stream rows of rt_set_present (a chained call always fills them) and allocates, per call slot, the source
+// rows and the [S][K][N] buffer its detection reads as look-back (rt_chain.h); later calls only regroup the book.
+int rt_set_chain(rt_handle *h, int32_t links) {
+    if (!h) return RT_E_INVALID;
+    if (links < 0) {
+        h->err = "rt_set_chain: links must be >= 0";
+        return RT_E_INVALID;
+    }
+    if (h->f64) {
+        h->err = "rt_set_chain on a float64 handle (rt_create_f64): not available in this version";
+        return RT_E_UNSUPPORTED;
+    }
+    if (!h->kids.empty() || h->cfg.lanes > 1) {
+        h->err = "rt_set_chain on a handle created with lanes > 1: lanes cut the streams into groups that a run may straddle (not available in this version)";
+        return RT_E_UNSUPPORTED;
+    }
+    const int S = h->cfg.n_streams;
+    const int want = links >= 2 ? links : 0;
+    if (want && S % want != 0) {
+        h->err = "rt_set_chain: links " + std::to_string(links) + " does not divide n_streams " + std::to_string(S);
+        return RT_E_INVALID;
+    }
+    if (oldest_pending(h)) {
+        h->err = "rt_set_chain with unfetched calls pending: fetch them first";
+        return RT_E_INVALID;
+    }
+    if (want == h->chain.links) return RT_OK;
+    if (want) {
+        ChainBook next;
+        next.configure(S, want);
+        std::vector<float> snr;
+        std::vector<double> min_d, max_d;
+        for (const StreamSettings &q : h->h_set_s) {
+            snr.push_back(q.snr);
+            min_d.push_back(q.min_d);
+            max_d.push_back(q.max_d);
+        }
+        const int rcu = chain_runs_uniform(h, next, "rt_set_chain", h->h_thr_s.empty() ? nullptr : h->h_thr_s.data(), h->h_cal_s.empty() ? nullptr : h->h_cal_s.data(),
+                                           snr.empty() ? nullptr : snr.data(), min_d.empty() ? nullptr : min_d.data(), max_d.empty() ? nullptr : max_d.data());
+        if (rcu != RT_OK) return rcu;
+        if (!h->slot[0].d_chain) {
+            RT_HIP(h, hipSetDevice(h->cfg.device));
+            const size_t row_bytes = 2 * (size_t)S * sizeof(int32_t), col_bytes = (size_t)S * (size_t)h->K * (size_t)h->N * sizeof(float);
+            int32_t *hr[kSlots] = {nullptr, nullptr}, *dr[kSlots] = {nullptr, nullptr};
+            float *dc[kSlots] = {nullptr, nullptr};
+            bool ok = true;
+            for (int i = 0; i < kSlots && ok; ++i)
+                ok = hipHostMalloc(&hr[i], row_bytes) == hipSuccess && hipMalloc(&dr[i], row_bytes) == hipSuccess && hipMalloc(&dc[i], col_bytes ? col_bytes : 4) == hipSuccess;
+            if (!ok) {
+                (void)hipGetLastError();
+                for (int i = 0; i < kSlots; ++i) {
+                    (void)hipHostFree(hr[i]);
+                    (void)hipFree(dr[i]);
+                    (void)hipFree(dc[i]);
+                }
+                h->err = "rt_set_chain: no memory for the chained look-back columns (" + std::to_string(col_bytes) + " bytes per call slot)";
+                return RT_E_NOMEM;
+            }
+            for (int i = 0; i < kSlots; ++i) {
+                std::memset(hr[i], 0, row_bytes);
+                h->slot[i].h_chain_rows = hr[i];
+                h->slot[i].d_chain_rows = dr[i];
+                h->slot[i].d_chain = dc[i];
+            }
+        }
+        if (!h->pres.active) {
+            const int rcp = rt_set_present(h, nullptr);  // (every stream present: the mask rows exist from here on)
+            if (rcp != RT_OK) return rcp;
+        }
+    }
+    h->chain.configure(S, want);
+    return rt_reset(h);  // a change of the grouping forgets all look-back
 }
 
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, int fmt);
@@ -2125,7 +2275,14 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             h->pres.begin_call(T, h->tail_cur, h->reset_pending, sl.pc);
             c.masked = true;
             h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
-            int rcm = upload_mask(h, sl);
+            int rcm = RT_OK;
+            if (h->chain.on()) {
+                // rt_set_chain: who follows whom (the snapshot's n_seg_last row becomes the count of the buffer each stream follows)
+                h->chain.begin_call(T, sl.pc, sl.cc);
+                c.chained = true;
+                rcm = upload_chain_rows(h, sl);
+            }
+            if (rcm == RT_OK) rcm = upload_mask(h, sl);
             if (rcm == RT_OK)
                 rcm = enqueue_carry<float>(h, sl.d_mask + (size_t)kMaskAbsentList * h->cfg.n_streams, sl.n_absent, h->d_tail[c.tail_read], h->d_tail[c.tail_write],
                                            h->K, h->N);
@@ -2185,6 +2342,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             h->pres.rollback(sl.pc, h->reset_pending);
             h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
         }
+        if (c.chained) h->chain.rollback(sl.cc);
         if (launched) {
             (void)hipStreamSynchronize(h->s_scan);
             (void)hipStreamSynchronize(h->s_detect);

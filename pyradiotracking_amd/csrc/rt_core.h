@@ -441,6 +441,83 @@ struct PresenceBook {
     }
 };
 
+// ---- Consecutive buffers of one recording as the streams of one call (rt_set_chain; host side, driven by the CPU suite) ----
+// The handle's streams are grouped into runs of `links` consecutive indices; the present streams of a run are, in index order,
+// consecutive buffers of ONE analyzer of the reference.  So the buffer at stream s looks back into the nearest present stream
+// before it in its run, of the SAME call (whose columns the call's own scan writes into the rotation buffer the call writes);
+// a run's first present stream looks back into the run's last present stream of the latest earlier call the run took part in
+// -- carried along the rotation since (PresenceBook), so it is in the buffer the call reads -- with THAT call's segment count.
+// The book sits on top of a PresenceBook (the mask, the pending resets, the rotation): begin_call rewrites the n_seg_last row of
+// the PresenceCall the presence book has just filled and yields each stream's source for the copy (rt_chain.h: chain_tails).
+enum : int32_t { kChainNone = 0, kChainWritten = 1, kChainRead = 2 };  // ChainCall::src_buf: no copy / the buffer the call writes / reads
+struct ChainCall {
+    std::vector<int32_t> src_buf;   // [S] kChain*: absent streams and streams without look-back take none
+    std::vector<int32_t> src_idx;   // [S] the stream whose columns are copied (-1: none)
+    std::vector<int32_t> before_idx, before_T;  // [runs] the book before the call (put back when the call is rolled back)
+};
+struct ChainBook {
+    int S = 0, links = 0;             // links >= 2: chaining is on
+    std::vector<int32_t> last_idx;    // [runs] the run's last present stream of the latest call it took part in, -1: none
+    std::vector<int32_t> last_T;      // [runs] ... and that call's segment count
+    bool on() const { return links >= 2; }
+    int runs() const { return on() ? S / links : 0; }
+    void configure(int n_streams, int n_links) {
+        S = n_streams;
+        links = n_links >= 2 ? n_links : 0;
+        last_idx.assign((size_t)runs(), (int32_t)-1);
+        last_T.assign((size_t)runs(), (int32_t)-1);
+    }
+    void forget_all() {  // rt_reset: a cut in front of every run's first stream
+        std::fill(last_idx.begin(), last_idx.end(), (int32_t)-1);
+        std::fill(last_T.begin(), last_T.end(), (int32_t)-1);
+    }
+    // `pc`: the call's snapshot as PresenceBook::begin_call left it (absent, took_reset; n_seg_last per stream INDEX, which is
+    // replaced here for the present streams by the count of the buffer each one follows, -1: none).
+    void begin_call(int T, PresenceCall &pc, ChainCall &cc) {
+        cc.src_buf.assign((size_t)S, (int32_t)kChainNone);
+        cc.src_idx.assign((size_t)S, (int32_t)-1);
+        cc.before_idx = last_idx;
+        cc.before_T = last_T;
+        for (int r = 0; r < runs(); ++r) {
+            int pred = -1;  // the nearest present stream before s in the run, in this call
+            for (int s = r * links; s < (r + 1) * links; ++s) {
+                const size_t i = (size_t)s;
+                if (pc.absent[i]) continue;
+                if (pc.took_reset[i]) {
+                    pc.n_seg_last[i] = -1;
+                } else if (pred >= 0) {
+                    cc.src_buf[i] = kChainWritten;
+                    cc.src_idx[i] = pred;
+                    pc.n_seg_last[i] = T;
+                } else if (last_idx[(size_t)r] >= 0) {
+                    cc.src_buf[i] = kChainRead;
+                    cc.src_idx[i] = last_idx[(size_t)r];
+                    pc.n_seg_last[i] = last_T[(size_t)r];
+                } else {
+                    pc.n_seg_last[i] = -1;
+                }
+                pred = s;
+            }
+            if (pred >= 0) {
+                last_idx[(size_t)r] = pred;
+                last_T[(size_t)r] = T;
+            }
+        }
+    }
+    void rollback(const ChainCall &cc) {
+        last_idx = cc.before_idx;
+        last_T = cc.before_T;
+    }
+    // the first run whose streams do not all hold the same value of `v` ([S]), or -1
+    template <class V>
+    int first_mixed_run(const V *v) const {
+        for (int r = 0; r < runs(); ++r)
+            for (int j = 1; j < links; ++j)
+                if (!(v[r * links + j] == v[r * links])) return r;
+        return -1;
+    }
+};
+
 // Column rotation of exchange 1 in the fused scans with R3 > 1 (rt_kernels.h: "Exchange layouts"): s1(b) = (16 / R3 - 2) * b mod 16.
 // The kernel rotates by it; the host folds the phase that undoes it into the pass-2 twiddles (rt_tables.h: scan_twiddles).
 RT_HD int x1_rotation(int R3, int b) { return ((16 / R3 - 2) * b) & 15; }

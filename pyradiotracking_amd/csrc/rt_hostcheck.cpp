@@ -294,6 +294,8 @@ struct HcPresence {
     int tail_cur = 0;
     unsigned long long n_calls = 0;
     PresenceCall slot[2];
+    ChainBook chain;  // (hc_chain_*, below: off until hc_chain_set)
+    ChainCall chain_slot[2];
 };
 static void hc_presence_copy(const PresenceCall &c, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
     if (absent) std::memcpy(absent, c.absent.data(), c.absent.size());
@@ -349,6 +351,52 @@ void hc_presence_state(void *h, int32_t *n_seg_last, uint8_t *reset_pending, uin
     std::memcpy(reset_pending, p->reset_pending.data(), p->reset_pending.size());
     std::memcpy(present, p->book.present.data(), p->book.present.size());
 }
+
+// ---- consecutive buffers as the streams of one call (rt_core.h: ChainBook) ----
+// On top of the presence bookkeeping above, as a chained handle drives both: `h` is an hc_presence_new handle.
+void hc_chain_set(void *h, int links) {  // (a change forgets all look-back, as rt_set_chain does)
+    HcPresence *p = static_cast<HcPresence *>(h);
+    p->chain.configure(p->book.S, links);
+    hc_presence_reset_all(h);
+}
+void hc_chain_reset_all(void *h) {  // rt_reset
+    hc_presence_reset_all(h);
+    static_cast<HcPresence *>(h)->chain.forget_all();
+}
+static void hc_chain_copy(const ChainCall &c, int32_t *src_buf, int32_t *src_idx) {
+    if (src_buf) std::memcpy(src_buf, c.src_buf.data(), c.src_buf.size() * sizeof(int32_t));
+    if (src_idx) std::memcpy(src_idx, c.src_idx.data(), c.src_idx.size() * sizeof(int32_t));
+}
+// one chained call of T segments: hc_presence_call's outputs (n_seg_last as the chain rewrites it) and each stream's source
+// (src_buf[S]: 0 none, 1 the buffer the call writes, 2 the buffer it reads; src_idx[S])
+int hc_chain_call(void *h, int T, uint8_t *absent, int32_t *n_seg_last, int32_t *tails, int32_t *src_buf, int32_t *src_idx, uint8_t *took_reset) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    const int slot = (int)(p->n_calls % 2);
+    PresenceCall &c = p->slot[slot];
+    p->book.begin_call(T, p->tail_cur, p->reset_pending, c);
+    p->chain.begin_call(T, c, p->chain_slot[slot]);
+    p->tail_cur = c.tail_write;
+    ++p->n_calls;
+    hc_presence_copy(c, absent, n_seg_last, tails);
+    hc_chain_copy(p->chain_slot[slot], src_buf, src_idx);
+    if (took_reset) std::memcpy(took_reset, c.took_reset.data(), c.took_reset.size());
+    return c.n_present;
+}
+int hc_chain_snapshot(void *h, unsigned long long k, int32_t *n_seg_last, int32_t *src_buf, int32_t *src_idx) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    if (k >= p->n_calls || k + 2 < p->n_calls) return -1;
+    hc_presence_copy(p->slot[k % 2], nullptr, n_seg_last, nullptr);
+    hc_chain_copy(p->chain_slot[k % 2], src_buf, src_idx);
+    return 0;
+}
+void hc_chain_rollback(void *h) {
+    HcPresence *p = static_cast<HcPresence *>(h);
+    if (p->n_calls == 0) return;
+    p->chain.rollback(p->chain_slot[(p->n_calls - 1) % 2]);
+    hc_presence_rollback(h);
+}
+// the first run in which `v` ([S] floats) is not uniform, or -1 (rt_set_stream_params / rt_set_stream_settings on a chained handle)
+int hc_chain_first_mixed_run(void *h, const float *v) { return static_cast<HcPresence *>(h)->chain.first_mixed_run(v); }
 
 }  // extern "C"
 
