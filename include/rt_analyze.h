@@ -128,8 +128,11 @@ typedef struct rt_config {
 #define RT_FLAG_NO_LIN_DETREND 2u /* always subtract the segment mean before windowing (scipy's order of operations);
                                      default: for hamming / hann / boxcar windows and complex64 input the constant
                                      detrend is applied to the transform instead (three bins), which is cheaper and
-                                     equal within float32 round-off -- other windows and uint8 input (where a saturated
-                                     segment cancels exactly in the reference) use the subtract-first form anyway */
+                                     equal within float32 round-off, except that a segment whose samples are all one finite
+                                     value (a front end that clips for a segment) is recognised and gives the column of exact
+                                     zeros that x - mean gives in the reference, in every input format -- other windows and
+                                     uint8 input (where a saturated segment cancels exactly in the reference) use the
+                                     subtract-first form anyway */
 #define RT_FLAG_GROUP_DETECT 4u    /* sparse detection (analyze.py:330-452 on the candidate lists) with one wave per stream, or per quarter
                                      of a stream's sixteen lists, instead of one per list -- the same records; the default from 1 024
                                      streams per handle on, while the streams of the call fetched last held few candidate cells (<= 448 on

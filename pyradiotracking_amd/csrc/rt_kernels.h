@@ -306,6 +306,38 @@ __device__ __forceinline__ cf group_sum(cf v, cf *red /* [kBlock/64] LDS */) {
     return v;
 }
 
+// LIN instantiations: is the segment constant?  Where every sample of a segment is one finite value c, x - mean is exactly zero
+// in the reference and so is every cell of the column (std = NaN over a plateau that holds one: a front end that clips for a
+// segment), while FFT(w x) - m W leaves round-off there.  The sums of a segment are trees of pairwise additions (halves in the
+// lane, DPP folds across lanes: wave_sum), and over n = 2^k equal values every addition is x + x, which is exact: `sum` is n c
+// bit for bit unless it overflows, and sum / n is c again.  So the n samples behind `sum` are all one finite value iff every one
+// of them equals sum * inv_n (-0 counts as +0: numerically the same segment; NaN equals nothing; an infinite or overflowing sum
+// is refused, the reference's mean is not finite there either).  The hot path pays for ONE sample's compare and a vote: on
+// ordinary input no lane's first sample is its segment's mean, and the other fifteen are only looked at behind a wave-uniform branch
+// (idle lane groups -- a chunk past the stream's end, a step past its segments -- hold zeros and take it in every step; their result
+// is unused).  The test waits for the sum's DPP folds, which the linearity form otherwise needs only behind pass 3: 1 - 2 % of the
+// nperseg-256 scan, 2 - 3.5 % on int8 input (profiles/constant_segments_bench_ab.txt).  Measured and dropped, headline scan against
+// the parent commit on one box: the same test with the samples (not the exchange rows) set to zero in its branch, -1.9 %; a test
+// of the lane's first two samples and a vote folded in scalar registers, needing no sum, behind the sums -6.7 % and at the head of
+// the step -6.5 %; the sum-based test behind pass 3 on a kept sample and a second read of the segment, -5.7 %.
+// v: the lane's 16 raw samples; sum: over the LG lanes of its group that sit in this wave (wave_sum<LG>); inv_n: 1 / their count.
+// Returns the verdict for the lane's group (LG > 64: for this wave's share of it), the same in every lane of the group.
+template <int LG, class C>
+__device__ __forceinline__ bool const_segment(const C (&v)[16], cf sum, float inv_n) {
+    const float mx = sum.x * inv_n, my = sum.y * inv_n;
+    const bool finite = ((__float_as_uint(mx) & 0x7F800000u) != 0x7F800000u) && ((__float_as_uint(my) & 0x7F800000u) != 0x7F800000u);
+    bool same = finite && v[0].x == mx && v[0].y == my;
+    if (__builtin_amdgcn_ballot_w64(same) == 0ull) return false;
+#pragma unroll
+    for (int m = 1; m < 16; ++m) same = same && v[m].x == mx && v[m].y == my;
+    const unsigned long long odd = __builtin_amdgcn_ballot_w64(!same);
+    if constexpr (LG >= 64) {
+        return odd == 0ull;
+    } else {
+        return ((odd >> ((threadIdx.x & 63u) & ~(unsigned)(LG - 1))) & ((1ull << LG) - 1ull)) == 0ull;
+    }
+}
+
 // Exchange layouts for R3 > 1 (tools/lds_banks.py models them with the gfx950 bank rules: every ds_write_b64 and
 // ds_read_b128 of both exchanges is conflict-free; the plain [row][column] layout was 2-way conflicted on every store).
 //   exchange 1: element (a = b + R3*c, k1) goes to row k1*R3 + b, physical column (c + s1(b)) & 15 with
@@ -646,7 +678,7 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
     constexpr bool DMA = scan_dma(R3, FMT, QS);
     constexpr int kStage = (R3 <= RT_WG4_MAX_R3 || (U8 && R3 == 1 && !RT_EXP_U8_PK)) ? 32 : (R3 == 8) ? 96 : DMA ? 64 : kStageCap;  // candidate cells staged per wave before a flush
     constexpr size_t kXchB = sizeof(cf) * (BLK * ROW + GPW * GPAD);
-    constexpr size_t kRedB = (LG > 64) ? sizeof(cf) * (BLK / 64) + 16 : 0;  // + the three tail_any words
+    constexpr size_t kRedB = (LG > 64) ? sizeof(cf) * (BLK / 64) + 16 + sizeof(uint32_t) * (BLK / 64) : 0;  // + the three tail_any words + red_const
     constexpr size_t kWB = W_IN_LDS ? sizeof(float4) * 4 * LG : 0;
     constexpr size_t kT1fB = T1_FACTORED ? sizeof(float4) * 2 * LG : 0;
     constexpr size_t kT1B = T1_IN_LDS ? sizeof(float4) * 8 * LG : 0;
@@ -673,6 +705,7 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
     cf *const xch = reinterpret_cast<cf *>(lds_block);
     cf *const red = reinterpret_cast<cf *>(lds_block + kXchB);
     uint32_t *const tail_any = reinterpret_cast<uint32_t *>(lds_block + kXchB + sizeof(cf) * (BLK / 64));  // LG > 64, see the tail columns below
+    uint32_t *const red_const = tail_any + 4;  // LIN, LG > 64: [BLK / 64] a wave's share of its segment is constant (written and read with `red`)
 
     const int tid = threadIdx.x;
     const int g = tid / LG;
@@ -1101,6 +1134,7 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
             sum = cf{s1.x, s1.y};
         }
         RT_STAMP(2);  // wait for this segment's samples (requested a step ago) + the in-lane sums
+        bool cseg = false;  // LIN: this lane group's segment is constant (const_segment below); the same in every lane of the group
         if constexpr (LIN && LG > 64) {
             // The sum is only needed after pass 3.  This wave's share goes to `red` behind the barrier that frees the
             // exchange rows (every wave has read the previous step's shares by then: it read them right behind that
@@ -1111,10 +1145,15 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
             // step ~1 000 cycles apart; without this one they wait as long at the exchange barrier instead:
             // profiles/r03_d_stage_stamps.txt, profiles/r03_g_wave_skew.txt.)
             sum = wave_sum<LG>(sum);
+            cseg = const_segment<64>(v, sum, 1.0f / 1024.0f);  // this wave's share: 64 lanes x 16 samples (the group's verdict: below)
             __syncthreads();  // the previous step's last use of the exchange rows is over in every wave
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+            if ((threadIdx.x & 63) == 0) {
+                red[threadIdx.x >> 6] = sum;
+                red_const[threadIdx.x >> 6] = cseg ? 1u : 0u;
+            }
         } else {
             sum = group_sum<LG>(sum, red);  // (for LG > 64 its barrier also frees the exchange rows)
+            if constexpr (LIN) cseg = const_segment<LG>(v, sum, 1.0f / (float)N);
         }
         RT_STAMP(3);  // group sum (lane shuffles, nperseg >= 2048: workgroup barrier)
         const cf mean_s = LIN ? cf{0.f, 0.f} : cscale(sum, 1.0f / (float)N);
@@ -1185,6 +1224,24 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
             for (int k1 = 0; k1 < 16; ++k1) gx[(k1 * R3 + b) * kRowF2 + c] = v[k1];
         }
         RT_STAMP(6);  // exchange 1: stores
+        if constexpr (LIN && LG <= 64) {
+            // A constant segment (const_segment): x - mean is exactly zero in every sample, so the column is zeros.  Its lane group writes
+            // zeros over what it has just put into its exchange rows, and everything behind them transforms zeros -- a rare, wave-uniform
+            // branch that holds stores only: choosing between the registers and zero costs the step sixteen instructions or, in a
+            // branch, a second set of registers.  (DS operations of a wave execute in program order.)
+            if (__builtin_amdgcn_ballot_w64(cseg) != 0ull) {
+                if (cseg) {
+                    if constexpr (QS) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) gx[(r % QS) * ROW + (r / QS) * QS + lt] = make_c<C>(0.f, 0.f);
+                    } else {
+                        const int b = lt % R3, c = (lt / R3 + x1_rotation<R3>(lt % R3)) & 15;
+#pragma unroll
+                        for (int k1 = 0; k1 < 16; ++k1) gx[(k1 * R3 + b) * kRowF2 + c] = make_c<C>(0.f, 0.f);
+                    }
+                }
+            }
+        }
         group_sync<LG>();
         RT_STAMP(7);  // exchange 1: barrier (nperseg >= 2048)
         if constexpr (LIN && LG > 64) {
@@ -1193,6 +1250,10 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
             cf t{0.f, 0.f};
 #pragma unroll
             for (int w = 0; w < WPG; ++w) t = cadd(t, red[w0 + w]);
+            // the group's segment is constant where every wave's share is, and at one value: equal shares' sums are equal
+            const cf t0 = red[w0];
+#pragma unroll
+            for (int w = 0; w < WPG; ++w) cseg = cseg && red_const[w0 + w] != 0u && red[w0 + w].x == t0.x && red[w0 + w].y == t0.y;
             sum = t;  // (used after pass 3)
         }
         if constexpr (QS) {
@@ -1264,10 +1325,20 @@ __global__ __launch_bounds__(scan_block(R3), scan_wgs_per_cu(R3, scan_fmt(MODEF,
                 if (active && !halo) dc_acc = __builtin_fmaf(sum.x, sum.x, __builtin_fmaf(sum.y, sum.y, dc_acc));  // (guard of this form: StftParams::dc_flag)
             }
             // X[k] -= (sum x) * W[k]/N for k in {0, 1, N-1}: the constant detrend, applied to the transform
+            // (a constant segment has transformed zeros, see exchange 1: nothing to subtract from them)
+            const cf sum_d = (LG <= 64 && cseg) ? cf{0.f, 0.f} : sum;
 #pragma unroll
             for (int j = 0; j < kLinRegs; ++j) {
-                v[kLinReg[j]].x = __builtin_fmaf(-lin_k[j], sum.x, v[kLinReg[j]].x);
-                v[kLinReg[j]].y = __builtin_fmaf(-lin_k[j], sum.y, v[kLinReg[j]].y);
+                v[kLinReg[j]].x = __builtin_fmaf(-lin_k[j], sum_d.x, v[kLinReg[j]].x);
+                v[kLinReg[j]].y = __builtin_fmaf(-lin_k[j], sum_d.y, v[kLinReg[j]].y);
+            }
+            if constexpr (LG > 64) {
+                // (a group of several waves learns that its segment is constant behind the exchange barrier, too late for the rows: the
+                // column is set to zero here, in a rare, wave-uniform branch)
+                if (__builtin_amdgcn_ballot_w64(cseg) != 0ull) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) v[r] = cseg ? make_c<C>(0.f, 0.f) : v[r];
+                }
             }
         }
         // |X|^2 * scale  (scipy _spectral_py.py:2126-2128); sqrt(scale) is folded into the window table

@@ -280,6 +280,47 @@ __global__ __launch_bounds__(kW64Block, 1) void stft_scan64(const StftParams p) 
                     __builtin_amdgcn_s_waitcnt(0x8F70);  // vmcnt(32)
                     __builtin_amdgcn_sched_barrier(0);
                     RT_STAMP(2);  // wait for the prefetched half
+                    if constexpr (LIN) {
+                        // A constant segment (rt_kernels.h: const_segment): x - mean is exactly zero in every sample, so the reference's
+                        // column is zeros, while FFT(w x) - m W leaves round-off.  The step pays for two samples out of the prefetched
+                        // half and a vote; where every lane's two agree -- never on ordinary input -- the segment is read once more and
+                        // compared sample by sample, and a segment of one finite value (4096 of which do not overflow) is transformed as
+                        // the zeros that x - mean is: its samples are replaced here, ahead of the step, where the registers are free --
+                        // no branch inside the transform.  The guard's D keeps what the samples summed to.
+                        int lane_c = lane;
+                        asm volatile("" : "+v"(lane_c));
+                        const raw_t *two = reinterpret_cast<const raw_t *>(area);
+                        const cf x0 = to_cf(two[lane_c]), x1 = to_cf(two[64 + lane_c]);
+                        if (__builtin_amdgcn_ballot_w64(!(x0.x == x1.x && x0.y == x1.y)) == 0ull) {
+                            const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x0.x)));
+                            const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x0.y)));
+                            bool same = true;
+#pragma unroll 8
+                            for (int m = 0; m < 64; ++m) {
+                                const cf x = to_cf(buf_load_iq(r, lane * (int)sizeof(raw_t), 64 * m * (int)sizeof(raw_t), raw_t{}));
+                                same = same && x.x == cx && x.y == cy;
+                            }
+                            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): quarters 2 and 3 have landed as well
+                            const bool small = __builtin_fabsf(cx) < 8.0e34f && __builtin_fabsf(cy) < 8.0e34f;
+                            if (small && __builtin_amdgcn_ballot_w64(!same) == 0ull) {
+#pragma unroll
+                                for (int j = 0; j < 16; ++j) {
+                                    q2r[j] = raw_t{};
+                                    q3r[j] = raw_t{};
+                                }
+                                wave_sync();  // (the two samples above have been read)
+                                // (the whole 16 KiB of the wave's area, whatever the format: int16 / int8 samples fill 8 / 4 KiB of it, the
+                                // rest is exchange space nobody reads before this step's exchange writes it)
+                                float4 *const z = reinterpret_cast<float4 *>(area) + lane_c;
+#pragma unroll
+                                for (int j = 0; j < 16; ++j) z[64 * j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                                wave_sync();
+                                if constexpr (SUMS) {
+                                    if (!halo) dc_acc = __builtin_fmaf(4096.0f * cx, 4096.0f * cx, __builtin_fmaf(4096.0f * cy, 4096.0f * cy, dc_acc));
+                                }
+                            }
+                        }
+                    }
                     // (lane indices made opaque inside the step: otherwise hipcc hoists the lanes' LDS addresses -- one per exchange
                     // chunk, table row and prefetched piece, 54 of them -- out of the step loop, where they cost the registers the
                     // row sums need: spills in every step)

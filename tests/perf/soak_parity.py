@@ -196,6 +196,7 @@ while time.time() < t_end:
     # the case as a list of events, then one pass over the GPU (fetches lag one call behind the enqueues when
     # `pipelined`: two calls in flight)
     events = []
+    prev_rows, last_rows, prev_specs = {}, {}, {}  # SOAK_DUMP_CELLS: per stream, the previous analysed buffer's samples and map (records that start in it)
     for k in range(n_buf):
         n_k = blen if not vary_len else int(rng.integers(2 * nperseg, blen + 1))
         chunk = np.ascontiguousarray(iq[:, k * blen:k * blen + n_k])
@@ -284,6 +285,9 @@ while time.time() < t_end:
                     print(f"  MISMATCH (UNEXPLAINED) case {case} buf {k} stream {s}: {int((rec['stream'] == s).sum())} records of a stream that sat the buffer out")
                 continue
             try:
+                if os.environ.get("SOAK_DUMP_CELLS"):
+                    prev_specs[s], prev_rows[s] = oas[s].spec_last, last_rows.get(s)
+                    last_rows[s] = chunk[s]
                 want, kept = oas[s].process(chunk[s], TS0)
             except IndexError:
                 # the reference indexes the CURRENT time axis with a look-back offset (analyze.py:422-423): a run reaching
@@ -350,6 +354,13 @@ while time.time() < t_end:
                         # the samples of the record's segments (complex64 as the oracle saw them), for a fixture
                         np.save(os.path.join(os.environ["SOAK_DUMP_CELLS"], f"case{case}_buf{k}_stream{s}_fi{x.fi}_seg{max(x.start, 0)}_{x.end}.npy"),
                                 chunk[s][max(x.start, 0) * nperseg:x.end * nperseg])
+                        if x.start < 0 and prev_rows.get(s) is not None and prev_specs.get(s) is not None:
+                            # ... and the part in the previous buffer: its last -start segments
+                            t_prev = prev_specs[s].shape[1]
+                            back = prev_specs[s][x.fi, t_prev + x.start:]
+                            print(f"    oracle cells of the record (the previous buffer's part, segments {t_prev + x.start} .. {t_prev - 1}) {back.tolist()}")
+                            np.save(os.path.join(os.environ["SOAK_DUMP_CELLS"], f"case{case}_buf{k}_stream{s}_fi{x.fi}_prev_seg{t_prev + x.start}_{t_prev}.npy"),
+                                    prev_rows[s][(t_prev + x.start) * nperseg:t_prev * nperseg])
                     break
     b.close()
     n_cases += 1
