@@ -569,6 +569,64 @@ int rt_set_present(rt_handle *h, const uint8_t *present);
  */
 int rt_set_chain(rt_handle *h, int32_t links);
 
+/*
+ * ---- record IQ: the samples behind every record (additive within ABI version 6) ----
+ * The reference hands on a Signal's figures and drops the samples.  Whoever works with a detection afterwards -- a frequency
+ * estimate finer than fs / nperseg, a pulse edge finer than one segment, a coded-ID decode, cutting bursts out of an archive --
+ * needs the IQ of the pulse, and would have to keep every buffer of every stream (and the one before it, for records whose
+ * `start` is negative) to slice it on the host.  rt_set_record_iq makes the handle keep what that takes -- the tail of every
+ * stream's previous buffer, as samples -- and rt_fetch_record_iq hands out each record's samples, cut from the caller's own bytes.
+ *   - rt_set_record_iq(h, m): 0 <= m <= 1024 turns the feature on with a margin of m whole segments on either side of a record;
+ *     m < 0 turns it off.  On every handle kind: float32 handles in every mode, nperseg and lane count, chained handles, float64
+ *     handles (dense, RT_FLAG_F64_SPARSE, with RT_FLAG_F64_RESCUE) -- the samples are gathered from the delivered records and the
+ *     IQ alone.  Refused (RT_E_INVALID, the message says "pending") while unfetched calls are pending; RT_E_INVALID as well: null
+ *     handle, m > 1024.  A call that changes m, or turns the feature off, forgets the held sample tails.  RT_E_NOMEM: no memory
+ *     for the bookkeeping rows.
+ *   - a handle on which the entry was never called with m >= 0 allocates, copies and launches exactly what it did before; no
+ *     kernel argument changes meaning.  With the feature on every rt_process* adds one streaming copy in front of its scan (the
+ *     last min(T, K + m) whole segments of every present stream, K = the handle's look-back columns) and every delivering rt_fetch
+ *     one gather; the analysis -- records, row means, record cells -- is untouched, byte for byte.
+ *   - memory: three tail rows per stream of (K + m) * nperseg samples, sized by the widest input format the handle has seen
+ *     (allocated by the first rt_process* after the entry; RT_E_NOMEM from that call if the device cannot hold them, and the call
+ *     is not enqueued), plus a byte pool per call slot that grows on demand inside rt_fetch.
+ * What rt_fetch_record_iq delivers.  The call concerned is the one the last rt_fetch / rt_fetch_f64 delivered IN FULL (RT_OK,
+ * cap >= *n_out), as for rt_fetch_record_cells; record i is the i-th record that fetch wrote, shadowed ones included, in (stream,
+ * fi, start) order over all lanes.  With N = nperseg, T = the call's segment count and, for record i of stream s,
+ *     D(s) = min(T_pred, K + m)  if the detection of this call had look-back for s and the predecessor buffer -- the one the
+ *            detection looked back into: the stream's own last present buffer (after any number of absent calls); on a chained
+ *            handle the nearest present stream before it in its run, in the same call, or for a run's first present stream the
+ *            run's remembered stream of the earlier call -- came in the same input format and its tail is held;
+ *     D(s) = 0  otherwise: the first call, after rt_reset / rt_reset_stream / a changed threshold or setting, T_pred == 0, another
+ *            format, the first call after rt_set_record_iq turned the feature on or changed m;
+ * record i delivers the WHOLE segments
+ *     first_seg[i] = max(start_i - m, -D(s))   ...   min(end_i + m, T) - 1.
+ * Segment t >= 0 is samples [t * N, (t + 1) * N) of the call's buffer of stream s.  Segment -d is samples [(T_pred - d) * N,
+ * (T_pred - d + 1) * N) of the predecessor buffer: counted from that buffer's last WHOLE segment, exactly as rt_record.start counts
+ * cells.  The predecessor's ragged remainder (its n_samples % N last samples, which no segment covers) is never delivered: in time
+ * it lies between segment -1 and segment 0, so a snippet that crosses the boundary is contiguous in time only where that
+ * remainder is empty.
+ *   - the payload is the caller's own bytes in the call's input format, nothing is converted: *bytes_per_sample = 8 (complex64),
+ *     16 (complex128 on a float64 handle), 2 (uint8, int8), 4 (int16).  Bit for bit the bytes at those places of the buffers the
+ *     caller passed, device pointers and the _host entries (the staged copy) alike.
+ *   - `offsets`: HOST memory, n_offsets == n_records + 1 entries (or NULL: not wanted), in SAMPLES; offsets[0] == 0,
+ *     *n_bytes == offsets[n_records] * *bytes_per_sample.  `first_seg`: HOST memory, n_first == n_records entries (or NULL);
+ *     first_seg[i] <= start_i, except where D(s) clips the lead: it is 0 for a negative start_i when D(s) == 0.
+ *   - `iq`: HOST memory, cap_bytes bytes.  iq == NULL or cap_bytes == 0: a size query (*n_bytes, *bytes_per_sample and, if given,
+ *     offsets and first_seg); nothing is consumed.  cap_bytes < *n_bytes with a buffer: RT_E_CAPACITY, nothing written to `iq`.
+ *   - the data stay valid until the next rt_process*, rt_extract*, rt_reset or rt_set_record_iq on the handle; with two calls in
+ *     flight: process k, process k + 1, fetch k, then the IQ of k.  (The samples are gathered inside the delivering rt_fetch, so
+ *     the call's IQ need not outlive that fetch.)
+ *   - a call without records: offsets[0] = 0, *n_bytes = 0, RT_OK.  An absent stream (rt_set_present) has no records; its held
+ *     tail stays its own for its next present call.  A failed rt_process* leaves the held tails as they were before it.
+ *   - RT_E_INVALID, refused before anything is copied or launched: null handle, `n_bytes` or `bytes_per_sample`; the feature is
+ *     off; a wrong n_offsets / n_first; no delivered call, or one no longer valid (see above), or one enqueued before the feature
+ *     was turned on; a call delivered truncated (RT_E_CAPACITY from the fetch, or cap < *n_out); a delivered rt_extract* call.
+ *   - RT_E_NOMEM: the device could not hold the call's samples (the pool grows on demand, inside rt_fetch, like the cell pool).
+ */
+int rt_set_record_iq(rt_handle *h, int32_t margin_segments);   /* >= 0: on, with that margin; < 0: off */
+int rt_fetch_record_iq(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                       void *iq, size_t cap_bytes, size_t *n_bytes, int32_t *bytes_per_sample);
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

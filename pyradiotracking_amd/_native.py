@@ -5,6 +5,7 @@ entry point here raises -- there is no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Optional
@@ -165,6 +166,8 @@ ABI_SYMBOLS = (
     "rt_set_stream_settings_f64",
     "rt_set_present",
     "rt_set_chain",
+    "rt_set_record_iq",
+    "rt_fetch_record_iq",
 )
 
 _lib = None
@@ -237,6 +240,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_set_stream_settings_f64.argtypes = [vp, vp, vp, vp]
     lib.rt_set_present.argtypes = [vp, vp]
     lib.rt_set_chain.argtypes = [vp, C.c_int32]
+    lib.rt_set_record_iq.argtypes = [vp, C.c_int32]
+    lib.rt_fetch_record_iq.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -403,6 +408,8 @@ class NativeAnalyzer:
         self.nperseg = nperseg
         self.device = device
         self.max_samples = max_samples
+        self._fed = collections.deque(maxlen=2)  # the formats of the calls in flight (a third enqueue drops the oldest, as the handle does)
+        self.fetched_format = None               # ... and of the call ``fetch`` consumed last: "c", "u8", "i16", "i8" or "extract"
 
     # -- lifecycle --------------------------------------------------------
     def close(self):
@@ -487,15 +494,19 @@ class NativeAnalyzer:
     # -- analysis ---------------------------------------------------------
     def process_device(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):
         self._check(self._lib.rt_process(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
+        self._fed.append("c")
 
     def process_device_u8(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):
         self._check(self._lib.rt_process_u8(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
+        self._fed.append("u8")
 
     def process_device_i16(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):
         self._check(self._lib.rt_process_i16(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
+        self._fed.append("i16")
 
     def process_device_i8(self, iq_ptr: int, n_samples: int, stream_stride: Optional[int] = None):
         self._check(self._lib.rt_process_i8(self._handle, iq_ptr, n_samples, stream_stride or n_samples))
+        self._fed.append("i8")
 
     def process_host(self, iq: np.ndarray):
         """``[S, B]`` complex IQ in host memory: complex64 (complex128 on a float64 handle, where complex64 is widened exactly)."""
@@ -506,6 +517,7 @@ class NativeAnalyzer:
             raise ValueError(f"expected {self.n_streams} streams, got {a.shape[0]}")
         self._keep = a  # async H2D copy reads it until the fetch
         self._check(self._lib.rt_process_host(self._handle, a.ctypes.data, a.shape[1], a.shape[1]))
+        self._fed.append("c")
 
     def process_host_u8(self, raw: np.ndarray):
         """``[S, 2*B]`` uint8 (interleaved I, Q) in host memory; staged by the library (one buffer per call in flight)."""
@@ -515,6 +527,7 @@ class NativeAnalyzer:
         if a.shape[0] != self.n_streams or a.shape[1] % 2:
             raise ValueError(f"expected uint8 [{self.n_streams}, 2*B]")
         self._check(self._lib.rt_process_u8_host(self._handle, a.ctypes.data, a.shape[1] // 2, a.shape[1] // 2))
+        self._fed.append("u8")
 
     def process_host_i16(self, raw: np.ndarray):
         """``[S, 2*B]`` int16 (interleaved I, Q) in host memory; staged by the library (one buffer per call in flight)."""
@@ -527,6 +540,7 @@ class NativeAnalyzer:
         if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % 2:
             raise ValueError(f"expected int16 [{self.n_streams}, 2*B]")
         self._check(self._lib.rt_process_i16_host(self._handle, a.ctypes.data, a.shape[1] // 2, a.shape[1] // 2))
+        self._fed.append("i16")
 
     def process_host_i8(self, raw: np.ndarray):
         """``[S, 2*B]`` int8 (interleaved I, Q) in host memory; staged by the library (one buffer per call in flight)."""
@@ -539,6 +553,7 @@ class NativeAnalyzer:
         if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % 2:
             raise ValueError(f"expected int8 [{self.n_streams}, 2*B]")
         self._check(self._lib.rt_process_i8_host(self._handle, a.ctypes.data, a.shape[1] // 2, a.shape[1] // 2))
+        self._fed.append("i8")
 
     def fetch(self, allow_truncated: bool = False) -> np.ndarray:
         """Records of the oldest enqueued call.  A call whose records were truncated (``RT_E_CAPACITY``: an ``rt_extract``
@@ -549,6 +564,7 @@ class NativeAnalyzer:
         n = C.c_size_t(0)
         self.last_truncated = False
         fetch = self._lib.rt_fetch_f64 if self.f64 else self._lib.rt_fetch
+        self.fetched_format = self._fed.popleft() if self._fed else None  # (whatever follows consumes the call)
         rc = fetch(self._handle, None, 0, C.byref(n))  # size query: the call stays pending
         if rc != RT_OK and rc != RT_E_CAPACITY:
             self._check(rc)  # incl. RT_E_HOT_OVERFLOW: the library has dropped the call
@@ -575,6 +591,28 @@ class NativeAnalyzer:
             self._check(fn(self._handle, offsets.ctypes.data, offsets.size, cells.ctypes.data, cells.size, C.byref(n)))
         return offsets, cells
 
+    def set_record_iq(self, margin_segments: int):
+        """``rt_set_record_iq``: ``margin_segments >= 0`` makes the handle keep the sample tail of every stream's previous
+        buffer, so that ``fetch_record_iq`` can hand out each record's samples with that many whole segments on either side;
+        a negative value turns it off.  Refused with calls pending."""
+        self._check(self._lib.rt_set_record_iq(self._handle, int(margin_segments)))
+
+    def fetch_record_iq(self):
+        """``rt_fetch_record_iq``: ``(offsets, first_segment, payload, bytes_per_sample)`` of the call ``fetch`` delivered last
+        (in full) -- ``offsets`` int64 ``[n_records + 1]`` in samples, ``first_segment`` int32 ``[n_records]``, ``payload`` the
+        caller's own bytes (uint8) of the whole segments ``first_segment[i] ... `` of record ``i``, back to back."""
+        n_rec = getattr(self, "_n_fetched", 0)
+        offsets = np.zeros(n_rec + 1, dtype=np.int64)
+        first = np.zeros(n_rec, dtype=np.int32)
+        n, bps = C.c_size_t(0), C.c_int32(0)
+        fn = self._lib.rt_fetch_record_iq
+        self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, None, 0, C.byref(n), C.byref(bps)))
+        payload = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, payload.ctypes.data,
+                           payload.size, C.byref(n), C.byref(bps)))
+        return offsets, first, payload, int(bps.value)
+
     def fetch_row_means(self) -> np.ndarray:
         """``rt_fetch_row_means`` (``rt_fetch_row_means_f64`` on a float64 handle): ``[S, nperseg]`` float32 (float64), the
         mean of every bin's row over the segments of the call ``fetch`` delivered last, bins in fftfreq order."""
@@ -587,6 +625,7 @@ class NativeAnalyzer:
         """``rt_extract`` (float32 maps), or ``rt_extract_f64`` (float64 maps) on a float64 handle."""
         fn = self._lib.rt_extract_f64 if self.f64 else self._lib.rt_extract
         self._check(fn(self._handle, spec_ptr, n_seg, n_bins, last_ptr, n_seg_last))
+        self._fed.append("extract")
 
     def spectrogram_device(self, iq_ptr: int, n_samples: int, stream_stride: int, out_ptr: int):
         """``rt_spectrogram`` (complex64 -> float32), or ``rt_spectrogram_f64`` (complex128 -> float64) on a float64 handle."""

@@ -298,9 +298,15 @@ class BatchSignalAnalyzer:
         f64_sparse: bool = False,
         f64_rescue: bool = False,
         chain: int = 0,
+        record_iq: bool = False,
+        record_iq_margin: int = 0,
         **kwargs,
     ):
-        """``chain=L`` (``rt_set_chain``, ``L >= 2``): every device is a RECORDING, analysed ``L`` consecutive buffers per call.
+        """``record_iq`` (``rt_set_record_iq``): keep the sample tail of every stream's previous buffer, so that
+        :meth:`fetch_record_iq` can hand out the IQ samples behind every record of a call, ``record_iq_margin`` whole segments
+        on either side included.  On every kind of analyzer (any ``mode``, ``lanes``, ``chain``, ``precision``).
+
+        ``chain=L`` (``rt_set_chain``, ``L >= 2``): every device is a RECORDING, analysed ``L`` consecutive buffers per call.
         The handle has ``len(devices) * L`` streams -- run ``r`` (streams ``r * L ... r * L + L - 1``, :meth:`run_of` /
         :meth:`link_of`) holds device ``r``'s buffers of a call in time order, each looking back into the one before it, the
         first into the run's last buffer of the call before.  ``devices`` then lists every STREAM's device name (each name ``L``
@@ -489,6 +495,12 @@ class BatchSignalAnalyzer:
             self._push_stream_settings()
         if self.chain:
             self._native.set_chain(self.chain)
+        self.record_iq = bool(record_iq)
+        self.record_iq_margin = int(record_iq_margin)
+        if self.record_iq:
+            if not 0 <= self.record_iq_margin <= 1024:
+                raise ValueError("record_iq_margin must be 0 ... 1024 segments")
+            self._native.set_record_iq(self.record_iq_margin)
         self._decoder = _RecordDecoder(fft_nperseg, sample_rate, self.center_freq, self.calibration_db, f64=f64)
         self.decoder = self._decoder  # record -> field conversion, shared with pyradiotracking_amd.match
         self.gpu = gpu
@@ -840,6 +852,35 @@ class BatchSignalAnalyzer:
         reset, after an ``extract_signals`` call and after a truncated fetch."""
         return self._native.fetch_record_cells()
 
+    def fetch_record_iq(self, convert: bool = False):
+        """``(offsets, first_segment, samples)``: the IQ samples behind every record of the call :meth:`fetch_records` (or
+        :meth:`process_batch`) returned last -- all records, shadowed ones included, in the order they were returned.
+        ``samples[offsets[i]:offsets[i + 1]]`` are the whole segments ``first_segment[i] ... min(end + margin, T) - 1`` of record
+        ``i``'s stream, ``first_segment[i] = max(start - margin, -D)``: a negative segment counts back from the last whole
+        segment of the buffer the detection looked back into, of which the analyzer holds ``D = min(T_before, K + margin)``
+        segments (``D = 0`` on a first buffer, after a reset or changed settings, and when that buffer came in another format).
+        ``samples`` is in the format the buffer was fed in, bit for bit the caller's bytes: complex64 (complex128 with
+        ``precision="float64"``), or ``[n, 2]`` uint8 / int8 / int16 (I, Q).  ``convert=True``: complex64 (complex128) through the
+        conversions of :mod:`pyradiotracking_amd.synth`, the ones the kernels apply.
+        Needs ``record_iq=True``; raises ``NativeError`` (``RT_E_INVALID``) once another buffer was enqueued or the analyzer
+        reset, after an ``extract_signals`` call and after a truncated fetch."""
+        from . import synth
+
+        offsets, first, payload, bps = self._native.fetch_record_iq()
+        fed = self._native.fetched_format
+        f64 = self.precision == "float64"
+        if fed == "c":
+            samples = payload.view(np.complex128 if f64 else np.complex64)
+        else:
+            samples = payload.view({"u8": np.uint8, "i8": np.int8, "i16": np.int16}[fed]).reshape(-1, 2)
+            if convert:
+                flat = samples.reshape(-1)
+                samples = {"u8": synth.u8_to_complex128_like_pyrtlsdr if f64 else synth.u8_to_complex64_like_kernel,
+                           "i8": synth.i8_to_complex128 if f64 else synth.i8_to_complex64,
+                           "i16": synth.i16_to_complex128 if f64 else synth.i16_to_complex64}[fed](flat)
+        assert len(samples) == offsets[-1]
+        return offsets, first, samples
+
     def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
         """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
         reference's noise figure (analyze.py:373-375) -- over the buffer of the call :meth:`fetch_records` (or
@@ -941,9 +982,15 @@ class SignalAnalyzer:
         record_cells: bool = False,
         f64_sparse: bool = False,
         f64_rescue: bool = False,
+        record_iq: bool = False,
+        record_iq_margin: int = 0,
         **kwargs,
     ):
-        """``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
+        """``record_iq=True``: after every buffer ``signal_iq`` is the list of the sample arrays of the signals put on the queue
+        (unshadowed, queue order, like ``signal_data``) -- the IQ of each pulse in the format the buffer came in, with
+        ``record_iq_margin`` whole segments on either side (:meth:`BatchSignalAnalyzer.fetch_record_iq`).
+
+        ``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
 
         ``precision="float64"``: complex128 buffers are analysed in float64 as the reference does (BatchSignalAnalyzer);
@@ -957,6 +1004,9 @@ class SignalAnalyzer:
         self.noise_dbw: Optional[np.ndarray] = None
         self.record_cells = bool(record_cells)
         self.signal_data: Optional[List[np.ndarray]] = None
+        self.record_iq = bool(record_iq)
+        self.record_iq_margin = int(record_iq_margin)
+        self.signal_iq: Optional[List[np.ndarray]] = None
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -1014,6 +1064,8 @@ class SignalAnalyzer:
             precision=precision,
             row_means=self.row_means,
             record_cells=self.record_cells,
+            record_iq=self.record_iq,
+            record_iq_margin=self.record_iq_margin,
             f64_sparse=bool(f64_sparse),
             f64_rescue=bool(f64_rescue),
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
@@ -1079,7 +1131,7 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = None
+        self.noise_dbw = self.signal_data = self.signal_iq = None
         self._batch.enqueue_bytes(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1103,7 +1155,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = None
+        self.noise_dbw = self.signal_data = self.signal_iq = None
         self._batch.enqueue_int16(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1127,7 +1179,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = None
+        self.noise_dbw = self.signal_data = self.signal_iq = None
         self._batch.enqueue_int8(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1142,8 +1194,8 @@ class SignalAnalyzer:
         buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = None
-        if self.record_cells:  # (process_batch, with the records kept for the cells' shadow flags)
+        self.noise_dbw = self.signal_data = self.signal_iq = None
+        if self.record_cells or self.record_iq:  # (process_batch, with the records kept for the cells' shadow flags)
             self._batch.enqueue(buf)
             rec = self._batch.fetch_records()
             keep = rec["shadowed"] == 0 if filtered else np.ones(len(rec), dtype=bool)
@@ -1158,14 +1210,16 @@ class SignalAnalyzer:
         )
         return out
 
-    def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64") -> List[Signal]:
+    def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False):
         """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
         instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
         (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
         ``"i16"`` / ``"i8"``) on a fresh analyzer once per buffer, in that order, with a clock that starts at ``ts_start``.
         ``samples``: one array, complex for ``"c64"``, else interleaved I, Q.  The last call has fewer links; a remainder
         shorter than a buffer is one more call if it holds at least two segments, else it is dropped with a log line (nothing
-        could be detected in it).  Every replay starts without look-back; the analyzer's own callback state is left alone."""
+        could be detected in it).  Every replay starts without look-back; the analyzer's own callback state is left alone.
+        ``record_iq=True``: returns ``(signals, signal_iq)`` -- beside every signal its samples, as the per-buffer callbacks of an
+        analyzer made with ``record_iq=True`` (and this analyzer's ``record_iq_margin``) leave them in ``signal_iq``."""
         per_sample = {"c64": 1, "u8": 2, "i16": 2, "i8": 2}[fmt]
         want = {"c64": np.complex64, "u8": np.uint8, "i16": np.int16, "i8": np.int8}[fmt]
         x = np.asarray(samples).reshape(-1)
@@ -1177,10 +1231,11 @@ class SignalAnalyzer:
             raise ValueError("replay is not available with precision='float64'")
         if int(chain) < 2:
             raise ValueError("chain must be >= 2")
-        if self._replay_batch is None or self._replay_batch.chain != int(chain):
+        if self._replay_batch is None or self._replay_batch.chain != int(chain) or self._replay_batch.record_iq != bool(record_iq):
             if self._replay_batch is not None:
                 self._replay_batch.close()
-            self._replay_batch = BatchSignalAnalyzer([self.device], chain=int(chain), **self._replay_kw)
+            self._replay_batch = BatchSignalAnalyzer([self.device], chain=int(chain), record_iq=bool(record_iq), record_iq_margin=self.record_iq_margin,
+                                                     **self._replay_kw)
         batch = self._replay_batch
         batch.reset()
         enqueue = {"c64": batch.enqueue, "u8": batch.enqueue_bytes, "i16": batch.enqueue_int16, "i8": batch.enqueue_int8}[fmt]
@@ -1189,11 +1244,15 @@ class SignalAnalyzer:
         n_full, rest = divmod(n, B)
         step = datetime.timedelta(seconds=B / self.sample_rate)  # analyze.py:205
         out: List[Signal] = []
+        out_iq: List[np.ndarray] = []
 
         def call(first: int, links: int, length: int):
             part = x[first * B * per_sample:(first * B + links * length) * per_sample]
             enqueue(part.reshape(1, -1), links=links)
             rec = batch.fetch_records()
+            if record_iq:  # (records come by link, i.e. in time order: the kept ones line up with the signals below)
+                offsets, _, got = batch.fetch_record_iq()
+                out_iq.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
             out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
 
         for first in range(0, n_full, L):
@@ -1203,7 +1262,7 @@ class SignalAnalyzer:
         elif rest:
             logger.info(f"SDR {self.device} replay: the last {rest} samples hold fewer than two segments and are dropped")
         [self.consume_signal(s) for s in out]
-        return out
+        return (out, out_iq) if record_iq else out
 
     def _keep_noise(self):
         if self.row_means:
@@ -1214,6 +1273,9 @@ class SignalAnalyzer:
         if self.record_cells:
             offsets, cells = self._batch.fetch_record_cells()
             self.signal_data = [cells[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
+        if self.record_iq:
+            offsets, _, samples = self._batch.fetch_record_iq()
+            self.signal_iq = [samples[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
 
     def reset(self):
         self._batch.reset()
@@ -1235,7 +1297,7 @@ class SignalAnalyzer:
         dense detect kernel (``rt_extract``).  The time axis must be the one
         SciPy produces for ``fft_nperseg`` / ``sample_rate`` (hop = nperseg/fs);
         ``freqs`` is used as given."""
-        self.noise_dbw = self.signal_data = None  # (the caller holds this map: no row means, no cells of it)
+        self.noise_dbw = self.signal_data = self.signal_iq = None  # (the caller holds this map: no row means, no cells of it)
         spec = np.asarray(spectrogram)
         n_bins, n_seg = spec.shape
         if n_seg == 0:

@@ -36,6 +36,7 @@
 #include "rt_cells.h"
 #include "rt_present.h"
 #include "rt_chain.h"
+#include "rt_record_iq.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -92,6 +93,7 @@ struct CallCtx {
     int cells_grown = 0;      // times the slot's cell pool was enlarged for this call and the call analysed again (RT_FLAG_RECORD_CELLS)
     bool masked = false;      // enqueued on a handle with a presence mask (rt_set_present): the slot's `pc` and mask arrays are this call's
     bool chained = false;     // enqueued on a chained handle (rt_set_chain): the slot's `cc`, chain rows and d_chain are this call's
+    bool iq_on = false;       // enqueued with rt_set_record_iq on: the slot's IqSlot::call is this call's (RecordIq)
     // handle state before this call (restored when the call is rolled back: a later lane failed to enqueue)
     int prev_tail_cur = 0, prev_n_seg_last = -1, prev_dense_sticky = 0, prev_minsum_slot = -1;
 };
@@ -202,6 +204,7 @@ struct F64Slot {
     int32_t *d_cell_count = nullptr;  // [S], zero between calls
     int32_t *h_hot = nullptr;      // pinned, device-visible: [S] cells each stream emitted
     int n_rescued = -1;            // RT_FLAG_F64_RESCUE: streams of the enqueued call rt_fetch_f64 has analysed again (-1: not looked at yet)
+    bool iq_on = false;            // enqueued with rt_set_record_iq on (as CallCtx::iq_on)
     hipEvent_t ev_done = nullptr;
 };
 struct F64State {
@@ -238,6 +241,33 @@ struct F64State {
     double *d_rs_partial = nullptr;  // [per_round][n_chunks][N]
     size_t rs_map_bytes = 0, rs_partial_bytes = 0;
     int32_t *d_rs_list = nullptr;  // [S] the call's overflowing streams
+};
+
+// rt_set_record_iq (rt_record_iq_book.h, rt_record_iq.h): nothing of it exists until the entry is called with a margin >= 0.
+// One per lane-less handle, float32 or float64; a laned handle's lanes each own theirs.
+constexpr int kIqNone = -1, kIqExtract = -2, kIqTruncated = -3, kIqOff = -4;  // RecordIq::delivered without a slot
+constexpr size_t kInitialIqPoolBytes = 1u << 20;  // a slot's byte pool at first need; a call that wants more grows it inside rt_fetch
+struct IqSlot {
+    IqCall call;                                     // what the slot's call was enqueued with
+    int32_t *h_rows = nullptr, *d_rows = nullptr;    // [S] IqCall::write_buf, pinned / device (iq_tails reads it)
+    char *d_pool = nullptr;                          // the snippets of the slot's delivered call, in record order
+    size_t pool_bytes = 0;
+    char *h_descs = nullptr, *d_descs = nullptr;     // the copy list and its tile prefix, pinned / device
+    size_t desc_bytes = 0;
+    std::vector<int64_t> offsets;                    // [records + 1] of the delivered call, in samples
+    std::vector<int32_t> first_seg;                  // [records]
+    int bps = 0;                                     // bytes per sample of the delivered call
+    int state = RT_OK;                               // what the gather left: RT_OK, RT_E_NOMEM, RT_E_HIP
+    std::string why;
+};
+struct RecordIq {
+    IqTailBook book;
+    char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
+    int64_t row_bytes = 0;     // (K + m) * N * area_bps, rounded up to 16
+    int area_bps = 0;          // bytes per sample of the widest format seen so far
+    hipStream_t s_gather = nullptr;  // the gather's own stream: a fetch must not queue behind the next call's scan
+    IqSlot slot[kSlots];
+    int delivered = kIqNone;   // the slot whose snippets rt_fetch_record_iq hands out, or kIq*
 };
 
 }  // namespace
@@ -350,6 +380,8 @@ struct rt_handle {
     std::vector<float> h_cal_s;  // host copy of the per-stream calibration (empty: rt_config's for every stream): rt_set_chain's uniformity check
 
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
+    RecordIq *riq = nullptr;  // rt_set_record_iq (float32 and float64 handles; a laned handle: its lanes hold theirs)
+    int iq_margin = -1;       // ... the margin in force, -1: off (the one thing a laned handle keeps itself)
 };
 
 namespace {
@@ -1270,6 +1302,172 @@ int grow_record_capacity(rt_handle *h, unsigned long long wanted) {
 
 // claim the slot of the next call; the GPU work of the call that used it last must be over
 // before its scratch is rewritten (its results, if never fetched, are dropped)
+// ---- rt_set_record_iq: the sample tails and the gather (rt_record_iq.h; the decisions: rt_record_iq_book.h) ----
+int iq_nperseg(const rt_handle *h) { return h->f64 ? h->f64->N : h->N; }
+int iq_sample_bytes(const rt_handle *h, int fmt) { return (h->f64 && fmt == kFmtC64) ? 16 : (int)fmt_sample_bytes(fmt); }
+
+// The tail area for samples of `bps` bytes: made at first need, and made again for a wider format.  Every row keeps its place
+// and its bytes (a pending call's fetch may still read the narrow tails), so a wider format loses nothing.
+int iq_tail_area(rt_handle *h, int bps) {
+    RecordIq &q = *h->riq;
+    if (q.d_tails && bps <= q.area_bps) return RT_OK;
+    const int64_t row = ((int64_t)q.book.cols() * iq_nperseg(h) * bps + 15) / 16 * 16;
+    const size_t rows = (size_t)kIqRows * (size_t)h->cfg.n_streams;
+    char *area = nullptr;
+    if (hipMalloc(&area, std::max<size_t>(rows * (size_t)row, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = "rt_set_record_iq: no device memory for the sample tails (" + std::to_string(rows * (size_t)row) + " bytes)";
+        return RT_E_NOMEM;
+    }
+    if (q.d_tails) {
+        hipError_t e = hipStreamSynchronize(h->s_scan);  // (kernels in flight write and read the old rows)
+        if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+        if (e == hipSuccess) e = hipMemcpy2D(area, (size_t)row, q.d_tails, (size_t)q.row_bytes, (size_t)q.row_bytes, rows, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(area);
+            h->err = std::string("rt_set_record_iq: moving the sample tails: ") + hipGetErrorString(e);
+            return RT_E_HIP;
+        }
+        (void)hipFree(q.d_tails);
+    }
+    q.d_tails = area;
+    q.row_bytes = row;
+    q.area_bps = bps;
+    return RT_OK;
+}
+
+// At enqueue, in front of the scan: the book's decisions for the call that takes slot `idx` (its snapshot stays in the slot for its
+// fetch), the rows it writes to the device, iq_tails on the scan's stream.  `slot_done`: the event behind the slot's previous call
+// (null: it never held one) -- the pinned rows are rewritten.  A failure leaves the book as it was.
+int iq_begin(rt_handle *h, int idx, hipEvent_t slot_done, int T, int fmt, const void *iq, int64_t stream_stride, const int32_t *n_seg_last,
+             const uint8_t *absent, const int32_t *src_buf, const int32_t *src_idx, const IqCall *other) {
+    RecordIq &q = *h->riq;
+    IqSlot &qs = q.slot[idx];
+    const int S = h->cfg.n_streams, N = iq_nperseg(h), bps = iq_sample_bytes(h, fmt);
+    const int rc = iq_tail_area(h, bps);
+    if (rc != RT_OK) return rc;
+    if (slot_done) RT_HIP(h, hipEventSynchronize(slot_done));
+    q.book.begin_call(T, fmt, n_seg_last, absent, src_buf, src_idx, other, qs.call);
+    const int D = std::min(T, q.book.cols());
+    bool any = false;
+    for (int s = 0; s < S; ++s) {
+        qs.h_rows[s] = qs.call.write_buf[(size_t)s];
+        any = any || qs.h_rows[s] >= 0;
+    }
+    if (D <= 0 || !any) return RT_OK;
+    IqTailsArgs a{};
+    a.iq = static_cast<const char *>(iq);
+    a.stream_stride = stream_stride;
+    a.bps = bps;
+    a.n_streams = S;
+    a.src_sample = (int64_t)(T - D) * N;
+    a.bytes = (int64_t)D * N * bps;  // (<= row_bytes: D <= K + m, bps <= area_bps)
+    a.tiles_per_stream = (int32_t)((a.bytes + kIqTileBytes - 1) / kIqTileBytes);
+    a.write_buf = qs.d_rows;
+    a.tails = q.d_tails;
+    a.row_bytes = q.row_bytes;
+    hipError_t e = hipMemcpyAsync(qs.d_rows, qs.h_rows, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(iq_tails, dim3((unsigned)S * (unsigned)a.tiles_per_stream), dim3(kIqBlock), 0, h->s_scan, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        q.book.rollback(qs.call);
+        qs.call.on = false;
+        h->err = std::string("iq_tails: ") + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    return RT_OK;
+}
+
+// Inside rt_fetch*, behind the delivery of the call in slot `idx` in full: its records -> offsets, first segments and the copy
+// list; the pool grown to what they need; the gather, waited for (the call's IQ need not outlive the fetch).  What goes wrong is
+// kept for rt_fetch_record_iq to report: the fetch itself has delivered.
+void iq_gather(rt_handle *h, int idx, const void *rec, size_t rec_stride, size_t n, const void *iq, int64_t stream_stride) {
+    RecordIq &q = *h->riq;
+    IqSlot &qs = q.slot[idx];
+    const int S = h->cfg.n_streams, N = iq_nperseg(h), bps = iq_sample_bytes(h, qs.call.fmt);
+    q.delivered = idx;
+    qs.state = RT_OK;
+    qs.bps = bps;
+    qs.offsets.assign(n + 1, 0);
+    qs.first_seg.assign(n, 0);
+    std::vector<IqDesc> descs;
+    const int64_t total = iq_build_descs(qs.call, N, rec, rec_stride, n, qs.offsets.data(), qs.first_seg.data(), &descs);
+    if (descs.empty()) return;
+    const auto fail = [&](int code, const std::string &why) {
+        (void)hipGetLastError();
+        qs.state = code;
+        qs.why = why;
+    };
+    if (!iq_descs_in_bounds(descs, S, (int64_t)qs.call.T * N, (int64_t)q.book.cols() * N, total) || !q.d_tails)
+        return fail(RT_E_HIP, "internal: a record's samples lie outside the buffers the handle holds");
+    const size_t bytes = (size_t)total * (size_t)bps;
+    if (qs.pool_bytes < bytes) {
+        (void)hipFree(qs.d_pool);
+        qs.d_pool = nullptr;
+        const size_t want = std::max(bytes, std::max(qs.pool_bytes * 2, kInitialIqPoolBytes));
+        qs.pool_bytes = 0;
+        if (hipMalloc(&qs.d_pool, want) != hipSuccess) {
+            (void)hipGetLastError();
+            if (want == bytes || hipMalloc(&qs.d_pool, bytes) != hipSuccess) return fail(RT_E_NOMEM, "no device memory for the call's samples (" + std::to_string(bytes) + " bytes)");
+            qs.pool_bytes = bytes;
+        } else {
+            qs.pool_bytes = want;
+        }
+    }
+    std::vector<int64_t> tile_first;
+    const int64_t tiles = iq_tile_prefix(descs, bps, &tile_first);
+    const size_t list_bytes = descs.size() * sizeof(IqDesc), need = list_bytes + tile_first.size() * sizeof(int64_t);
+    if (qs.desc_bytes < need) {
+        (void)hipHostFree(qs.h_descs);
+        (void)hipFree(qs.d_descs);
+        qs.h_descs = qs.d_descs = nullptr;
+        qs.desc_bytes = 0;
+        const size_t want = std::max(need, (size_t)1 << 16);
+        if (hipHostMalloc(&qs.h_descs, want) != hipSuccess || hipMalloc(&qs.d_descs, want) != hipSuccess) return fail(RT_E_NOMEM, "no memory for the copy list");
+        qs.desc_bytes = want;
+    }
+    std::memcpy(qs.h_descs, descs.data(), list_bytes);  // (sizeof(IqDesc) is a multiple of 8: the prefix behind it is aligned)
+    std::memcpy(qs.h_descs + list_bytes, tile_first.data(), tile_first.size() * sizeof(int64_t));
+    IqGatherArgs a{};
+    a.descs = reinterpret_cast<const IqDesc *>(qs.d_descs);
+    a.tile_first = reinterpret_cast<const int64_t *>(qs.d_descs + list_bytes);
+    a.n_descs = (int32_t)descs.size();
+    a.bps = bps;
+    a.n_streams = S;
+    a.iq = static_cast<const char *>(iq);
+    a.stream_stride = stream_stride;
+    a.tails = q.d_tails;
+    a.row_bytes = q.row_bytes;
+    a.pool = qs.d_pool;
+    // (one copy for the list and its prefix; the call's own iq_tails and everything before it ended in front of the call's ev_done)
+    hipError_t e = hipMemcpyAsync(qs.d_descs, qs.h_descs, need, hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(record_iq_gather, dim3((unsigned)tiles), dim3(kIqBlock), 0, q.s_gather, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) fail(RT_E_HIP, std::string("record_iq_gather: ") + hipGetErrorString(e));
+}
+
+// rt_destroy (the device is idle by then), and a failed first rt_set_record_iq
+void iq_free(rt_handle *h) {
+    RecordIq *q = h->riq;
+    if (!q) return;
+    for (IqSlot &qs : q->slot) {
+        (void)hipHostFree(qs.h_rows);
+        (void)hipFree(qs.d_rows);
+        (void)hipFree(qs.d_pool);
+        (void)hipHostFree(qs.h_descs);
+        (void)hipFree(qs.d_descs);
+    }
+    (void)hipFree(q->d_tails);
+    if (q->s_gather) (void)hipStreamDestroy(q->s_gather);
+    delete q;
+    h->riq = nullptr;
+}
+
 int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
     Slot &sl = h->slot[h->n_calls % kSlots];
     // the slot's previous call may still be in its detection (a stream of its own): what is enqueued from here on waits for it
@@ -1314,6 +1512,7 @@ void rollback_newest(rt_handle *h) {
             h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
         }
         if (c.chained) h->chain.rollback(best->cc);
+        if (c.iq_on) h->riq->book.rollback(h->riq->slot[best - h->slot].call);
     }
     best->call = CallCtx{};
     h->n_calls--;
@@ -1333,6 +1532,7 @@ void keep_row_means(rt_handle *h, const Slot &sl) { h->rm_slot = sl.call.is_extr
 void forget_row_means(rt_handle *h) {
     h->rm_slot = kRowMeansNone;
     if (h->f64) h->f64->rm_slot = kRowMeansNone;
+    if (h->riq) h->riq->delivered = kIqNone;  // (rt_fetch_record_iq: the same validity)
     for (rt_handle *k : h->kids) forget_row_means(k);
 }
 
@@ -1495,6 +1695,7 @@ void rt_destroy(rt_handle *h) {
     }
     (void)hipSetDevice(h->cfg.device);
     (void)hipDeviceSynchronize();
+    iq_free(h);
     (void)hipFree(h->d_work);
     (void)hipFree(h->d_twg);
     (void)hipFree(h->d_cwin);
@@ -1933,6 +2134,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
 int rt_reset(rt_handle *h) {
     if (!h) return RT_E_INVALID;
     forget_row_means(h);
+    if (h->riq) h->riq->book.forget_all();  // (no look-back, no lead: the held sample tails go with it)
     if (h->f64) {
         h->f64->n_seg_last = -1;
         if (h->f64->pres.active) h->f64->pres.forget_all();
@@ -2295,6 +2497,25 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             h->any_reset_pending = false;
             c.no_last = true;
         }
+        if (h->riq && h->riq->book.on()) {
+            // rt_set_record_iq: the tails of this call's samples, in front of its scan; who each stream's detection looks back into
+            // is what the rows above say (per stream), or the handle's one count less the resets this call takes
+            const int S = h->cfg.n_streams, idx = (int)(&sl - h->slot);
+            const Slot &o = h->slot[1 - idx];
+            std::vector<int32_t> last;
+            if (!c.masked) {
+                last.assign((size_t)S, (int32_t)c.n_seg_last);
+                if (c.no_last)
+                    for (int s = 0; s < S; ++s)
+                        if (sl.h_no_last[s]) last[(size_t)s] = -1;
+            }
+            launched = true;  // (the slot's snapshot is rewritten from here on)
+            const int rcq = iq_begin(h, idx, saved.seq ? sl.ev_done : nullptr, T, fmt, iq_dev, stream_stride, c.masked ? sl.pc.n_seg_last.data() : last.data(),
+                                     c.masked ? sl.pc.absent.data() : nullptr, c.chained ? sl.cc.src_buf.data() : nullptr,
+                                     c.chained ? sl.cc.src_idx.data() : nullptr, o.call.pending && o.call.iq_on ? &h->riq->slot[1 - idx].call : nullptr);
+            if (rcq != RT_OK) return rcq;
+            c.iq_on = true;
+        }
         c.mode_used = h->cfg.mode;
         if (h->cfg.mode == RT_MODE_AUTO) {
             // the level the input last needed, for `dense_sticky` more calls; then a probe of the level below
@@ -2343,6 +2564,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
         }
         if (c.chained) h->chain.rollback(sl.cc);
+        if (c.iq_on) h->riq->book.rollback(h->riq->slot[&sl - h->slot].call);  // (the held sample tails are the ones before the call)
         if (launched) {
             (void)hipStreamSynchronize(h->s_scan);
             (void)hipStreamSynchronize(h->s_detect);
@@ -2796,6 +3018,25 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
     if (!peek && !c.pending) {
         keep_row_means(h, sl);
         h->cells_full = cap >= total && !(flags & kFlagRecOverflow);  // (rt_fetch_record_cells: only of a call delivered in full)
+        if (h->riq) {
+            // rt_fetch_record_iq: the record list stands (every re-run is behind us) and the call's IQ is still the caller's to keep
+            RecordIq &q = *h->riq;
+            if (c.is_extract) {
+                q.delivered = kIqExtract;
+            } else if (!c.iq_on) {
+                q.delivered = kIqOff;
+            } else if (!h->cells_full) {
+                q.delivered = kIqTruncated;
+            } else {
+                std::vector<int32_t> keys;  // stream, fi, start, end of every record, in delivery order
+                keys.reserve(total * 4);
+                for (int s = 0; s < S; ++s) {
+                    const rt_record *r = sl.h_records + sl.h_rec_offset[s];
+                    for (int i = 0; i < sl.h_rec_count[s]; ++i) keys.insert(keys.end(), {(int32_t)s, r[i].fi, r[i].start, r[i].end});
+                }
+                iq_gather(h, (int)(&sl - h->slot), keys.data(), 4 * sizeof(int32_t), total, c.iq, c.stream_stride);
+            }
+        }
     }
     // (out == NULL / cap == 0 with records available is a size query: the call stays pending)
     if (flags & kFlagRecOverflow) {
@@ -2845,6 +3086,7 @@ int rt_fetch(rt_handle *h, rt_record *out, size_t cap, size_t *n_out) {
             // behind a buffer of exactly the call's size loses nothing: it is delivered in full below, and its cells stand.)
             if (const Slot *o = oldest_pending(k)) keep_row_means(k, *o);  // (delivered, if not in full: its row means stand)
             k->cells_full = false;
+            if (k->riq) k->riq->delivered = kIqTruncated;
             discard_oldest(k);
         } else if (deliver) {
             size_t n = 0;
@@ -3095,6 +3337,131 @@ int rt_fetch_record_cells(rt_handle *h, int64_t *offsets, size_t n_offsets, floa
         }
         r0 += n_rec[k];
         c0 += n_cell[k];
+    }
+    return RT_OK;
+}
+
+// rt_set_record_iq of one lane-less handle (float32 or float64): the first call with a margin makes the gather's stream and the
+// slots' pinned rows; the tail area follows with the first rt_process* (its size depends on the format).
+static int set_record_iq_one(rt_handle *h, int32_t m) {
+    const int S = h->cfg.n_streams, K = h->f64 ? h->f64->K : h->K;
+    h->iq_margin = m < 0 ? -1 : m;
+    if (m < 0) {
+        if (h->riq) {
+            h->riq->book.configure(S, K, -1);
+            h->riq->delivered = kIqNone;
+        }
+        return RT_OK;
+    }
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    if (!h->riq) {
+        h->riq = new (std::nothrow) RecordIq();
+        bool ok = h->riq && hipStreamCreateWithFlags(&h->riq->s_gather, hipStreamNonBlocking) == hipSuccess;
+        for (int i = 0; i < kSlots && ok; ++i)
+            ok = hipHostMalloc(&h->riq->slot[i].h_rows, (size_t)S * sizeof(int32_t)) == hipSuccess &&
+                 hipMalloc(&h->riq->slot[i].d_rows, (size_t)S * sizeof(int32_t)) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            iq_free(h);
+            h->iq_margin = -1;
+            h->err = "rt_set_record_iq: no memory for the rows of the sample tails";
+            return RT_E_NOMEM;
+        }
+        h->riq->book.configure(S, K, m);
+    } else if (h->riq->book.margin != m) {
+        // another margin is another row length: the area is made again by the next rt_process*, the held tails are forgotten
+        RT_HIP(h, hipStreamSynchronize(h->s_scan));
+        (void)hipFree(h->riq->d_tails);
+        h->riq->d_tails = nullptr;
+        h->riq->row_bytes = 0;
+        h->riq->area_bps = 0;
+        h->riq->book.configure(S, K, m);
+    }
+    h->riq->delivered = kIqNone;
+    return RT_OK;
+}
+
+int rt_set_record_iq(rt_handle *h, int32_t margin_segments) {
+    if (!h) return RT_E_INVALID;
+    if (margin_segments > kIqMaxMargin) {
+        h->err = "rt_set_record_iq: margin_segments must be <= " + std::to_string(kIqMaxMargin);
+        return RT_E_INVALID;
+    }
+    bool pending = false;
+    if (h->f64) {
+        for (const F64Slot &sl : h->f64->slot) pending = pending || sl.pending;
+    } else {
+        pending = h->kids.empty() && oldest_pending(h);
+        for (rt_handle *k : h->kids) pending = pending || oldest_pending(k);
+    }
+    if (pending) {
+        h->err = "rt_set_record_iq with unfetched calls pending: fetch them first";
+        return RT_E_INVALID;
+    }
+    if (!h->kids.empty()) {
+        const int rc = for_each_lane(h, [&](rt_handle *k, int64_t) { return set_record_iq_one(k, margin_segments); });
+        h->iq_margin = (rc == RT_OK && margin_segments >= 0) ? margin_segments : -1;
+        if (rc != RT_OK)
+            for (rt_handle *k : h->kids) (void)set_record_iq_one(k, -1);  // (no lane keeps what another could not get)
+        return rc;
+    }
+    return set_record_iq_one(h, margin_segments);
+}
+
+int rt_fetch_record_iq(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, void *iq, size_t cap_bytes,
+                       size_t *n_bytes, int32_t *bytes_per_sample) {
+    if (!h || !n_bytes || !bytes_per_sample) return RT_E_INVALID;
+    *n_bytes = 0;
+    *bytes_per_sample = 0;
+    const auto refuse = [&](const char *why) {
+        h->err = std::string("rt_fetch_record_iq: ") + why;
+        return RT_E_INVALID;
+    };
+    if (h->iq_margin < 0) return refuse("rt_set_record_iq has not turned the feature on");
+    std::vector<rt_handle *> one{h};
+    const std::vector<rt_handle *> &lanes = h->kids.empty() ? one : h->kids;
+    // every lane holds the samples of its streams' records: all of them are checked and counted before anything is written
+    size_t records = 0, samples = 0;
+    int bps = 0;
+    for (rt_handle *l : lanes) {
+        const int d = l->riq ? l->riq->delivered : kIqNone;
+        if (d == kIqExtract) return refuse("the call fetched last was an rt_extract: it has no samples");
+        if (d == kIqTruncated) return refuse("the call fetched last was delivered truncated");
+        if (d == kIqOff) return refuse("the call fetched last was enqueued before the feature was turned on");
+        if (d < 0) return refuse("no samples: no call delivered by rt_fetch since the last rt_process*, rt_extract, rt_reset or rt_set_record_iq");
+        const IqSlot &qs = l->riq->slot[d];
+        if (qs.state != RT_OK) {
+            h->err = "rt_fetch_record_iq: " + qs.why;
+            return qs.state;
+        }
+        records += qs.first_seg.size();
+        samples += (size_t)qs.offsets.back();
+        bps = qs.bps;
+    }
+    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records))
+        return refuse("n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number");
+    *n_bytes = samples * (size_t)bps;
+    *bytes_per_sample = bps;
+    const bool query = !iq || cap_bytes == 0;
+    if (!query && cap_bytes < *n_bytes) {
+        h->err = "rt_fetch_record_iq: output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    size_t r0 = 0, s0 = 0;
+    if (offsets) offsets[0] = 0;
+    for (rt_handle *l : lanes) {
+        const IqSlot &qs = l->riq->slot[l->riq->delivered];
+        const size_t n = qs.first_seg.size(), mine = (size_t)qs.offsets.back();
+        if (offsets)
+            for (size_t i = 0; i < n; ++i) offsets[r0 + i + 1] = (int64_t)s0 + qs.offsets[i + 1];
+        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
+        if (!query && mine) {
+            // (the gather was waited for inside the delivering rt_fetch; a copy on the null stream, as rt_fetch_record_cells copies)
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(static_cast<char *>(iq) + s0 * (size_t)bps, qs.d_pool, mine * (size_t)bps, hipMemcpyDeviceToHost));
+        }
+        r0 += n;
+        s0 += mine;
     }
     return RT_OK;
 }
@@ -3504,6 +3871,7 @@ static void destroy_f64(rt_handle *h) {
     F64State *f = h->f64;
     (void)hipSetDevice(h->cfg.device);
     (void)hipDeviceSynchronize();
+    iq_free(h);
     for (F64Slot &sl : f->slot) {
         (void)hipFree(sl.d_raw);
         (void)hipFree(sl.d_raw_count);
@@ -3587,6 +3955,28 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
         sl.iq = sl.d_stage;
     }
     sl.masked = f->pres.active;
+    sl.iq_on = false;
+    // rt_set_record_iq: as on a float32 handle (process_impl) -- the tails of this call's samples in front of its scan
+    const auto iq_tails_of_call = [&]() -> int {
+        if (!h->riq || !h->riq->book.on()) return RT_OK;
+        const int idx = (int)(&sl - f->slot);
+        const F64Slot &o = f->slot[1 - idx];
+        std::vector<int32_t> last;
+        if (!sl.masked) {
+            last.assign((size_t)S, (int32_t)sl.n_seg_last);
+            if (f->any_reset)
+                for (int s = 0; s < S; ++s)
+                    if (f->reset_pending[(size_t)s]) last[(size_t)s] = -1;
+        }
+        const int rcq = iq_begin(h, idx, sl.seq ? sl.ev_done : nullptr, T, fmt, sl.iq, stream_stride, sl.masked ? sl.pc.n_seg_last.data() : last.data(),
+                                 sl.masked ? sl.pc.absent.data() : nullptr, nullptr, nullptr, o.pending && o.iq_on ? &h->riq->slot[1 - idx].call : nullptr);
+        sl.iq_on = rcq == RT_OK;
+        return rcq;
+    };
+    const auto iq_undo = [&]() {
+        if (sl.iq_on) h->riq->book.rollback(h->riq->slot[&sl - f->slot].call);
+        sl.iq_on = false;
+    };
     const auto any_pending = [&]() { return std::find(f->reset_pending.begin(), f->reset_pending.end(), (uint8_t)1) != f->reset_pending.end(); };
     if (sl.masked) {
         // rt_set_present: as on a float32 handle (process_impl) -- the snapshot into the slot, the rows to the device, the absent
@@ -3605,8 +3995,10 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
             return enqueue_carry<double>(h, sl.d_mask + (size_t)kMaskAbsentList * S, sl.n_absent, f->d_tail[sl.tail_read], f->d_tail[sl.tail_write], f->K, f->N);
         };
         rcm = upload();
+        if (rcm == RT_OK) rcm = iq_tails_of_call();
         if (rcm == RT_OK) rcm = f64_start(h, sl);
         if (rcm != RT_OK) {
+            iq_undo();
             f->pres.rollback(sl.pc, f->reset_pending);
             f->any_reset = any_pending();
             sl.masked = false;
@@ -3622,8 +4014,12 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
         RT_HIP(h, hipMemcpyAsync(sl.d_no_last, sl.no_last_h.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
         RT_HIP(h, hipStreamSynchronize(h->s_scan));
     }
-    const int rc = f64_start(h, sl);
-    if (rc != RT_OK) return rc;
+    int rc = iq_tails_of_call();
+    if (rc == RT_OK) rc = f64_start(h, sl);
+    if (rc != RT_OK) {
+        iq_undo();
+        return rc;
+    }
     if (f->any_reset) {
         std::fill(f->reset_pending.begin(), f->reset_pending.end(), (uint8_t)0);
         f->any_reset = false;
@@ -3884,6 +4280,7 @@ int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t 
     F64Slot &sl = f64_claim(f);
     sl.pending = false;
     sl.is_extract = true;
+    sl.iq_on = false;
     sl.n_seg = n_seg;
     sl.ex_spec = spec_dev;
     sl.ex_bins = n_bins;
@@ -3994,6 +4391,13 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     sl.pending = false;
     f->rm_slot = sl.is_extract ? kRowMeansExtract : (int)(&sl - f->slot);
     f->cells_full = !truncated && n == total;
+    if (h->riq) {  // rt_fetch_record_iq, as in fetch_one
+        RecordIq &q = *h->riq;
+        if (sl.is_extract) q.delivered = kIqExtract;
+        else if (!sl.iq_on) q.delivered = kIqOff;
+        else if (!f->cells_full) q.delivered = kIqTruncated;
+        else iq_gather(h, (int)(&sl - f->slot), sl.h_out, sizeof(rt_record_f64), total, sl.iq, sl.stream_stride);
+    }
     if (truncated) return f64_err(h, RT_E_CAPACITY, "rt_extract_f64: a stream found more records than record_capacity");
     if (n < total) return f64_err(h, RT_E_CAPACITY, "output buffer too small: records lost");
     return RT_OK;

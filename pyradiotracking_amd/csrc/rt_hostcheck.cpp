@@ -15,6 +15,7 @@
 
 #include "../../include/rt_analyze.h"
 #include "rt_core.h"
+#include "rt_record_iq_book.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -397,6 +398,186 @@ void hc_chain_rollback(void *h) {
 }
 // the first run in which `v` ([S] floats) is not uniform, or -1 (rt_set_stream_params / rt_set_stream_settings on a chained handle)
 int hc_chain_first_mixed_run(void *h, const float *v) { return static_cast<HcPresence *>(h)->chain.first_mixed_run(v); }
+
+// ---- the samples behind every record (rt_record_iq_book.h: IqTailBook, iq_build_descs) ----
+// The bookkeeping as a handle drives it (rt_analyze.hip: iq_begin at enqueue, iq_gather inside rt_fetch), with the two kernels of
+// rt_record_iq.h restated as memcpy on host memory: one handle-wide segment count until hc_iq_present / hc_iq_chain move the handle
+// to per-stream rows, the pending resets, two call slots (call k in slot k % 2), three tail rows per stream.  The caller's arrays
+// must stay alive until their call is fetched, as a handle's callers' must.
+struct HcIq {
+    int S = 0, K = 0, N = 0;
+    IqTailBook book;
+    PresenceBook pres;
+    ChainBook chain;
+    std::vector<uint8_t> reset_pending;
+    int tail_cur = 0, n_seg_last = -1;
+    unsigned long long n_calls = 0;
+    struct Call {
+        bool pending = false, iq_on = false, masked = false, chained = false;
+        PresenceCall pc;
+        ChainCall cc;
+        IqCall iq;
+        std::vector<uint8_t> took;  // unmasked: the resets the call took
+        int prev_n_seg_last = -1;
+        const char *data = nullptr;
+        int64_t stride = 0;
+        int bps = 0;
+    } slot[2];
+    std::vector<char> tails;
+    int64_t row_bytes = 0;
+    int area_bps = 0;
+};
+void *hc_iq_new(int n_streams, int tail_cols, int nperseg) {
+    HcIq *p = new HcIq();
+    p->S = n_streams;
+    p->K = tail_cols;
+    p->N = nperseg;
+    p->reset_pending.assign((size_t)n_streams, (uint8_t)0);
+    p->book.configure(n_streams, tail_cols, -1);
+    return p;
+}
+void hc_iq_free(void *h) { delete static_cast<HcIq *>(h); }
+// rt_set_record_iq: -1 = refused (calls pending, or m out of range)
+int hc_iq_set_margin(void *h, int m) {
+    HcIq *p = static_cast<HcIq *>(h);
+    if (m > kIqMaxMargin || p->slot[0].pending || p->slot[1].pending) return -1;
+    if ((m < 0 ? -1 : m) != p->book.margin) {
+        p->book.configure(p->S, p->K, m);
+        p->tails.clear();
+        p->row_bytes = 0;
+        p->area_bps = 0;
+    }
+    return 0;
+}
+void hc_iq_present(void *h, const uint8_t *mask) {
+    HcIq *p = static_cast<HcIq *>(h);
+    if (!p->pres.active) p->pres.activate(p->S, p->n_seg_last);
+    p->pres.set_mask(mask);
+}
+void hc_iq_reset_stream(void *h, int s) { static_cast<HcIq *>(h)->reset_pending[(size_t)s] = 1; }
+void hc_iq_reset_all(void *h) {  // rt_reset
+    HcIq *p = static_cast<HcIq *>(h);
+    p->n_seg_last = -1;
+    if (p->pres.active) p->pres.forget_all();
+    p->chain.forget_all();
+    std::fill(p->reset_pending.begin(), p->reset_pending.end(), (uint8_t)0);
+    p->book.forget_all();
+}
+int hc_iq_chain(void *h, int links) {  // rt_set_chain
+    HcIq *p = static_cast<HcIq *>(h);
+    if (p->slot[0].pending || p->slot[1].pending || (links >= 2 && p->S % links != 0)) return -1;
+    if (links >= 2 && !p->pres.active) hc_iq_present(h, nullptr);
+    p->chain.configure(p->S, links);
+    hc_iq_reset_all(h);
+    return 0;
+}
+// rt_process*: a call of T segments in format code `fmt`, `bps` bytes a sample, rows `stride` samples apart at `data`.  Fills, if
+// given, the call's snapshot ([S] each) and returns the call's number.
+long long hc_iq_call(void *h, int T, int fmt, int bps, const void *data, long long stride, int32_t *lead_kind, int32_t *lead_row, int32_t *lead_buf,
+                     int32_t *lead_D, int32_t *write_buf) {
+    HcIq *p = static_cast<HcIq *>(h);
+    const int idx = (int)(p->n_calls % 2), S = p->S;
+    HcIq::Call &c = p->slot[idx];
+    const HcIq::Call &o = p->slot[1 - idx];
+    c = HcIq::Call();
+    c.prev_n_seg_last = p->n_seg_last;
+    c.data = static_cast<const char *>(data);
+    c.stride = stride;
+    c.bps = bps;
+    std::vector<int32_t> last;
+    if (p->pres.active) {
+        p->pres.begin_call(T, p->tail_cur, p->reset_pending, c.pc);
+        c.masked = true;
+        if (p->chain.on()) {
+            p->chain.begin_call(T, c.pc, c.cc);
+            c.chained = true;
+        }
+    } else {
+        c.took = p->reset_pending;
+        last.assign((size_t)S, (int32_t)p->n_seg_last);
+        for (int s = 0; s < S; ++s)
+            if (c.took[(size_t)s]) last[(size_t)s] = -1;
+        std::fill(p->reset_pending.begin(), p->reset_pending.end(), (uint8_t)0);
+    }
+    if (p->book.on()) {
+        if (p->tails.empty() || bps > p->area_bps) {  // (rt_analyze.hip: iq_tail_area -- every row keeps its place and its bytes)
+            const int64_t row = ((int64_t)p->book.cols() * p->N * bps + 15) / 16 * 16;
+            std::vector<char> area((size_t)(kIqRows * S) * (size_t)row);
+            for (int64_t r = 0; !p->tails.empty() && r < (int64_t)kIqRows * S; ++r)
+                std::memcpy(area.data() + r * row, p->tails.data() + r * p->row_bytes, (size_t)p->row_bytes);
+            p->tails.swap(area);
+            p->row_bytes = row;
+            p->area_bps = bps;
+        }
+        p->book.begin_call(T, fmt, c.masked ? c.pc.n_seg_last.data() : last.data(), c.masked ? c.pc.absent.data() : nullptr,
+                           c.chained ? c.cc.src_buf.data() : nullptr, c.chained ? c.cc.src_idx.data() : nullptr,
+                           o.pending && o.iq_on ? &o.iq : nullptr, c.iq);
+        c.iq_on = true;
+        for (int s = 0; s < S; ++s) {  // iq_tails
+            const int buf = c.iq.write_buf[(size_t)s], D = c.iq.write_D[(size_t)s];
+            if (buf < 0 || D <= 0) continue;
+            std::memcpy(p->tails.data() + ((int64_t)buf * S + s) * p->row_bytes, c.data + ((int64_t)s * stride + (int64_t)(T - D) * p->N) * bps,
+                        (size_t)((int64_t)D * p->N * bps));
+        }
+        const auto put = [&](int32_t *dst, const std::vector<int32_t> &v) {
+            if (dst) std::memcpy(dst, v.data(), v.size() * sizeof(int32_t));
+        };
+        put(lead_kind, c.iq.lead_kind);
+        put(lead_row, c.iq.lead_row);
+        put(lead_buf, c.iq.lead_buf);
+        put(lead_D, c.iq.lead_D);
+        put(write_buf, c.iq.write_buf);
+    }
+    c.pending = true;
+    if (c.masked) p->tail_cur = c.pc.tail_write;
+    p->n_seg_last = T;
+    return (long long)p->n_calls++;
+}
+// the newest call is undone (a failed rt_process*, or a later lane's): -1 if there is none pending
+int hc_iq_rollback(void *h) {
+    HcIq *p = static_cast<HcIq *>(h);
+    if (p->n_calls == 0) return -1;
+    HcIq::Call &c = p->slot[(p->n_calls - 1) % 2];
+    if (!c.pending) return -1;
+    if (c.iq_on) p->book.rollback(c.iq);
+    if (c.chained) p->chain.rollback(c.cc);
+    if (c.masked) {
+        p->pres.rollback(c.pc, p->reset_pending);
+        p->tail_cur = c.pc.tail_read;
+    } else {
+        for (int s = 0; s < p->S; ++s)
+            if (c.took[(size_t)s]) p->reset_pending[(size_t)s] = 1;
+    }
+    p->n_seg_last = c.prev_n_seg_last;
+    c = HcIq::Call();
+    --p->n_calls;
+    return 0;
+}
+// rt_fetch + rt_fetch_record_iq of call `k`: `rec` = n records as int32 (stream, fi, start, end), in delivery order.  Writes
+// offsets [n + 1] and first_seg [n], and -- when `cap_bytes` holds them -- the samples; the call is consumed.  Returns the bytes
+// of the samples, -1: no such pending call, -2: the call was enqueued with the feature off, -3: a descriptor out of bounds.
+long long hc_iq_fetch(void *h, unsigned long long k, const int32_t *rec, long long n, int64_t *offsets, int32_t *first_seg, void *out, long long cap_bytes,
+                      long long *n_descs) {
+    HcIq *p = static_cast<HcIq *>(h);
+    if (k >= p->n_calls || k + 2 < p->n_calls) return -1;
+    HcIq::Call &c = p->slot[k % 2];
+    if (!c.pending) return -1;
+    c.pending = false;
+    if (!c.iq_on) return -2;
+    std::vector<IqDesc> descs;
+    const int64_t total = iq_build_descs(c.iq, p->N, rec, 4 * sizeof(int32_t), (size_t)n, offsets, first_seg, &descs);
+    if (n_descs) *n_descs = (long long)descs.size();
+    if (!iq_descs_in_bounds(descs, p->S, (int64_t)c.iq.T * p->N, (int64_t)p->book.cols() * p->N, total)) return -3;
+    std::vector<int64_t> tile_first;
+    if (iq_tile_prefix(descs, c.bps, &tile_first) < (int64_t)descs.size()) return -3;  // (every descriptor holds a tile)
+    if (out && cap_bytes >= total * c.bps)
+        for (const IqDesc &d : descs) {  // record_iq_gather
+            const char *src = d.kind == kIqFromTail ? p->tails.data() + ((int64_t)d.buf * p->S + d.row) * p->row_bytes + d.src_sample * c.bps
+                                                    : c.data + ((int64_t)d.row * c.stride + d.src_sample) * c.bps;
+            std::memcpy(static_cast<char *>(out) + d.dst_sample * c.bps, src, (size_t)(d.len * c.bps));
+        }
+    return (long long)(total * c.bps);
+}
 
 }  // extern "C"
 
