@@ -58,14 +58,12 @@ thread_local bool g_creating_lane = false;  // rt_create of a laned handle is cr
 
 // bytes of a sample on a float32 handle, by input format (rt_kernels.h: kFmt*)
 constexpr size_t fmt_sample_bytes(int fmt) { return (fmt == kFmtU8 || fmt == kFmtI8) ? 2u : fmt == kFmtI16 ? 4u : sizeof(cf); }
-constexpr int kSlots = 2;
-constexpr int kTails = 3;
+constexpr int kTails = 3;  // (kSlots, kMaxPartial: rt_core.h)
 constexpr int64_t kInitialPoolRecords = 4 << 20;  // pinned record pool per slot at rt_create unless rt_config.record_pool says otherwise
                                                   // (4 Mi records = 160 MiB); a call that needs more grows it (grow_pool), up to what
                                                   // n_streams * record_capacity can ever deliver
 constexpr int64_t kInitialPoolCells = 4 << 20;    // RT_FLAG_RECORD_CELLS: device cell pool per slot at rt_create (or 16 cells per record of the record pool,
                                                   // if that is less); a call that needs more grows it (grow_cells) and is analysed again
-constexpr int kMaxPartial = 32;  // AUTO: up to this many overflowing streams of a batch are re-run dense on their own
 
 struct CallCtx {
     bool pending = false;   // enqueued, not fetched yet
@@ -87,7 +85,7 @@ struct CallCtx {
     int rec_cap_used = 0;     // the per-stream record capacity its kernels ran with (a call in flight while ANOTHER call grew the capacity was still truncated at the old one)
     bool thr_rerun = false;   // analysed again on RT_MODE_RUNFILTER with thresholds from its own row means (once per call)
     bool abs_counted = false; // a MODE 4 / 6 scan of this call left the slot's h_abs_hot
-    bool level_settled = false;  // AUTO's level bookkeeping for this call is done (fetch_one passes over a call twice: size query / peek, then delivery)
+    bool level_settled = false;  // AutoPolicy::settle has seen this call (fetch_one passes over a call twice: size query / peek, then delivery)
     bool ran_lin = false;     // its scans detrended by linearity (fetch_one: analysed again if the guard marks a stream)
     uint64_t sub_epoch = 0;   // rt_handle::sub_epoch when its kernels were enqueued
     int cells_grown = 0;      // times the slot's cell pool was enlarged for this call and the call analysed again (RT_FLAG_RECORD_CELLS)
@@ -95,7 +93,7 @@ struct CallCtx {
     bool chained = false;     // enqueued on a chained handle (rt_set_chain): the slot's `cc`, chain rows and d_chain are this call's
     bool iq_on = false;       // enqueued with rt_set_record_iq on: the slot's IqSlot::call is this call's (RecordIq)
     // handle state before this call (restored when the call is rolled back: a later lane failed to enqueue)
-    int prev_tail_cur = 0, prev_n_seg_last = -1, prev_dense_sticky = 0, prev_minsum_slot = -1;
+    int prev_tail_cur = 0, prev_n_seg_last = -1, prev_auto = 0 /* AutoPolicy::restore_point */, prev_minsum_slot = -1;
 };
 
 constexpr int kRowMeansNone = -1, kRowMeansExtract = -2;  // rt_handle::rm_slot / F64State::rm_slot without valid row means
@@ -328,21 +326,9 @@ struct rt_handle {
     uint64_t sub_epoch = 0;                // changes of the set so far (a call analysed under an older one is analysed again)
     float lin_c[3] = {0.f, 0.f, 0.f};
 
-    // AUTO mode: three ways to analyse a buffer, cheapest first -- RT_MODE_SPARSE (candidates emitted by the scan itself),
-    // RT_MODE_PREFILTER (two scan passes, rt_kernels.h; only where prefilter_ok), RT_MODE_DENSE.  A call whose candidate
-    // lists overflow is re-run one level up when it is fetched; the handle then stays on that level for `dense_sticky`
-    // calls before it probes the level below again (a failed probe costs a wasted scan: the interval doubles, 16 .. 1024).
-    bool prefilter_ok = false;
-    bool runfilter_ok = false;  // RT_MODE_RUNFILTER is possible and its scratch is allocated
+    AutoPolicy ap;              // RT_MODE_AUTO's level, probe counters and the levels that exist at this geometry (rt_core.h; `lv`: any mode)
     int minsum_slot = -1;       // the slot whose d_chunk_min holds the latest call's chunk minima (-1: none yet)
     int run_cells = 1;          // r: cells a plateau needs unless it runs through t = 0 (plan_runs)
-    int auto_level = RT_MODE_SPARSE;
-    int dense_sticky = 0;  // calls left on auto_level before the next probe
-    // the most cells at or above the absolute threshold any stream had in the last call a pre-filter level analysed: more
-    // than the sparse lists hold (kBuckets x hot_capacity per stream) means a probe of the sparse level cannot succeed
-    uint32_t abs_hot_seen = 0;
-    bool abs_hot_valid = false;
-    int sticky_len = 16;
     uint64_t n_calls = 0;  // calls enqueued so far
     uint64_t test_enqueues = 0;  // laned handle: rt_process calls seen (fault injection, read once at rt_create: RT_TEST_FAIL_LANE=<lane>:<n>)
     int test_fail_lane = -1, test_fail_nth = 0;
@@ -863,11 +849,10 @@ int enqueue_readback(rt_handle *h, Slot &sl, hipStream_t st) {
     return RT_OK;
 }
 
-// the level above / below `mode` in AUTO's order (rt_core.h: level_up / level_down / level_rank)
-static_assert(kAutoDense == RT_MODE_DENSE && kAutoSparse == RT_MODE_SPARSE && kAutoPrefilter == RT_MODE_PREFILTER && kAutoRunfilter == RT_MODE_RUNFILTER,
+// (AUTO's levels and its policy: rt_core.h)
+static_assert(kAutoAuto == RT_MODE_AUTO && kAutoDense == RT_MODE_DENSE && kAutoSparse == RT_MODE_SPARSE && kAutoPrefilter == RT_MODE_PREFILTER &&
+                  kAutoRunfilter == RT_MODE_RUNFILTER,
               "rt_core.h mirrors rt_mode");
-int level_up(const rt_handle *h, int mode) { return level_up(AutoLevels{h->prefilter_ok, h->runfilter_ok}, mode); }
-int level_down(const rt_handle *h, int mode) { return level_down(AutoLevels{h->prefilter_ok, h->runfilter_ok}, mode); }
 
 // (`st`: the handle's scan stream, or -- the selective second scans of the pre-filter levels -- the stream of what follows a call's first scan)
 template <int MODE>
@@ -1486,6 +1471,26 @@ int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
     return RT_OK;
 }
 
+// What the call in `sl` took from the handle's host bookkeeping when it was enqueued goes back (its enqueue failed: process_impl; a
+// later lane's did: rollback_newest): AUTO's probe counter, the slot of the chunk minima, the stream resets it consumed, and the
+// presence, chain and record-IQ books.
+void undo_call_books(rt_handle *h, Slot &sl) {
+    const CallCtx &c = sl.call;
+    h->ap.restore(c.prev_auto);
+    h->minsum_slot = c.prev_minsum_slot;  // (the chunk minima of the dropped buffer must not set the next call's thresholds)
+    if (c.no_last) {
+        for (int s = 0; s < h->cfg.n_streams; ++s)
+            if (sl.h_no_last[s]) h->reset_pending[(size_t)s] = 1;
+        h->any_reset_pending = true;
+    }
+    if (c.masked) {
+        h->pres.rollback(sl.pc, h->reset_pending);
+        h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
+    }
+    if (c.chained) h->chain.rollback(sl.cc);
+    if (c.iq_on) h->riq->book.rollback(h->riq->slot[&sl - h->slot].call);  // (the held sample tails are the ones before the call)
+}
+
 // Undo the newest enqueued call of a (lane-less) handle: wait for its kernels, forget it, and put the
 // look-back bookkeeping back to what it was before the call.
 void rollback_newest(rt_handle *h) {
@@ -1499,20 +1504,8 @@ void rollback_newest(rt_handle *h) {
     if (!c.is_extract) {
         h->tail_cur = c.prev_tail_cur;
         h->n_seg_last = c.prev_n_seg_last;
-        h->dense_sticky = c.prev_dense_sticky;
-        h->minsum_slot = c.prev_minsum_slot;  // (the chunk minima of the dropped buffer must not set the next call's thresholds)
-        if (best->min_seq == c.seq) best->min_items = 0;  // (... nor stand in for the slot's older ones, which they have overwritten)
-        if (c.no_last) {
-            for (int s = 0; s < h->cfg.n_streams; ++s)
-                if (best->h_no_last[s]) h->reset_pending[(size_t)s] = 1;
-            h->any_reset_pending = true;
-        }
-        if (c.masked) {
-            h->pres.rollback(best->pc, h->reset_pending);
-            h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
-        }
-        if (c.chained) h->chain.rollback(best->cc);
-        if (c.iq_on) h->riq->book.rollback(h->riq->slot[best - h->slot].call);
+        undo_call_books(h, *best);
+        if (best->min_seq == c.seq) best->min_items = 0;  // (the dropped buffer's chunk minima must not stand in for the slot's older ones, which they have overwritten)
     }
     best->call = CallCtx{};
     h->n_calls--;
@@ -1865,15 +1858,15 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
         // else holds -- (len + 1) * hop < signal_min_duration (analyze.py:427-430; rt_core.h: gate_run), with a margin of
         // 1e-9 for the rounding of the float64 expressions.  A run of >= 2 L - 1 cells covers an aligned chunk of L.
         const long long r_min = min_run_cells(h);
-        h->prefilter_ok = !general && !big && h->L >= 4 && 2ll * h->L - 1 <= r_min && h->max_seg >= 2 * h->L &&
-                          h->max_chunks <= (1 << 18);  // (plan_pass_b keeps a bit per chunk in LDS)
-        if (cfg->mode == RT_MODE_PREFILTER && !h->prefilter_ok) {
+        h->ap.lv.prefilter_ok = !general && !big && h->L >= 4 && 2ll * h->L - 1 <= r_min && h->max_seg >= 2 * h->L &&
+                                h->max_chunks <= (1 << 18);  // (plan_pass_b keeps a bit per chunk in LDS)
+        if (cfg->mode == RT_MODE_PREFILTER && !h->ap.lv.prefilter_ok) {
             delete h;
             return fail_create(RT_E_UNSUPPORTED, "RT_MODE_PREFILTER needs signal_min_duration >= 2 * segs_per_chunk STFT hops");
         }
         // nperseg 4096 without chunk bits (they need chunks of one length): a stream's earliest chunks are half as long, so that
         // the last items a launch hands out are short (rt_kernels.h: chunk_geometry).  A few chunks more than max_seg / L.
-        h->two_level = scan_wave64(R3) && !h->prefilter_ok && !RT_DIAG_ENV("RT_EXP_ONE_LEVEL");  // (the variable: A/B runs of diagnostic builds, rt_diag.h)
+        h->two_level = scan_wave64(R3) && !h->ap.lv.prefilter_ok && !RT_DIAG_ENV("RT_EXP_ONE_LEVEL");  // (the variable: A/B runs of diagnostic builds, rt_diag.h)
         if (h->two_level) {
             h->max_chunks += h->max_chunks / 4 + 2;
             max_blocks_per_stream = (h->max_chunks + h->GPW - 1) / h->GPW;
@@ -1888,8 +1881,8 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
             delete h;
             return fail_create(RT_E_UNSUPPORTED, "RT_MODE_RUNFILTER: the minimum plateau length (in STFT hops) is beyond the planner's counters");
         }
-        h->runfilter_ok = fits && (cfg->mode == RT_MODE_RUNFILTER || cfg->mode == RT_MODE_AUTO);
-        if (h->runfilter_ok && cfg->mode == RT_MODE_AUTO) {
+        h->ap.lv.runfilter_ok = fits && (cfg->mode == RT_MODE_RUNFILTER || cfg->mode == RT_MODE_AUTO);
+        if (h->ap.lv.runfilter_ok && cfg->mode == RT_MODE_AUTO) {
             // In AUTO mode the level is optional -- the only one between the sparse and the dense path at the reference's
             // default geometry, the one above the chunk bits elsewhere (noise far over the absolute threshold: every chunk
             // bit set, while SNR-aware cell bits stay selective): its scratch (two slots of threshold bits + kept cells +
@@ -1897,7 +1890,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
             // the only middle level, an eighth where the chunk bits exist -- and AUTO does without it otherwise.
             const size_t per_slot = (size_t)cfg->n_streams * std::max(h->max_seg, 1) * (size_t)(h->LG * 4 + 4) + (size_t)cfg->n_streams * h->N * 4 * (size_t)(h->max_blocks + 2);
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (size_t)kSlots * per_slot > free_b / (h->prefilter_ok ? 8 : 2)) h->runfilter_ok = false;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (size_t)kSlots * per_slot > free_b / (h->ap.lv.prefilter_ok ? 8 : 2)) h->ap.lv.runfilter_ok = false;
         }
     }
     if (!general && ((long long)h->N << key_tbits(std::max(h->max_seg, 2))) > 0x100000000ll) {
@@ -2050,10 +2043,10 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     for (auto &sl : h->slot) {
         sl.pool_cap = h->pool_want;
         RT_CREATE_HIP(hipMalloc(&sl.d_psum, std::max<size_t>(psum_bytes, 4)));
-        if (h->prefilter_ok && cfg->mode != RT_MODE_DENSE)
+        if (h->ap.lv.prefilter_ok && cfg->mode != RT_MODE_DENSE)
             RT_CREATE_HIP(hipMalloc(&sl.d_full, (size_t)S * (h->max_chunks + h->L) * LG * sizeof(uint16_t)));  // + the bits of chunk 0 by segment
         if (sl.d_full) RT_CREATE_HIP(hipMalloc(&sl.d_items, ((size_t)S * h->max_blocks * h->GPW + S) * sizeof(int32_t)));
-        if (h->runfilter_ok) {
+        if (h->ap.lv.runfilter_ok) {
             const size_t cells = (size_t)S * std::max(h->max_seg, 1) * LG;
             RT_CREATE_HIP(hipMalloc(&sl.d_cell_hot, cells * sizeof(uint16_t)));
             RT_DEVICE_ZEROS(RT_CREATE_HIP, sl.d_cell_need, cells * sizeof(uint16_t));  // (all zeros between calls: plan_runs writes only the words that keep anything)
@@ -2453,7 +2446,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     CallCtx &c = sl.call;
     c.prev_tail_cur = h->tail_cur;
     c.prev_n_seg_last = h->n_seg_last;
-    c.prev_dense_sticky = h->dense_sticky;
+    c.prev_auto = h->ap.restore_point();
     c.prev_minsum_slot = h->minsum_slot;
     c.iq = iq_dev;
     c.fmt = fmt;
@@ -2516,24 +2509,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             if (rcq != RT_OK) return rcq;
             c.iq_on = true;
         }
-        c.mode_used = h->cfg.mode;
-        if (h->cfg.mode == RT_MODE_AUTO) {
-            // the level the input last needed, for `dense_sticky` more calls; then a probe of the level below
-            if (h->dense_sticky > 0) {
-                c.mode_used = h->auto_level;
-                --h->dense_sticky;
-            } else {
-                c.mode_used = level_down(h, h->auto_level);
-                // (no probe, no back-off where the last count rules the level below out -- rt_core.h: probe_ruled_out; the next
-                // call looks again)
-                if (probe_ruled_out(c.mode_used, h->auto_level, h->abs_hot_valid, h->abs_hot_seen, (uint64_t)kBuckets * (uint64_t)h->hot_cap,
-                                    (uint64_t)T * (uint64_t)h->N))
-                    c.mode_used = h->auto_level;
-                // one probe at a time: the calls enqueued before this one's verdict is in (the caller may keep a slot's
-                // worth of calls in flight) stay on the handle's level instead of each paying for a failed probe
-                if (c.mode_used != h->auto_level) h->dense_sticky = kSlots;
-            }
-        }
+        c.mode_used = h->ap.begin_call(h->cfg.mode, (uint64_t)kBuckets * (uint64_t)h->hot_cap, (uint64_t)T * (uint64_t)h->N);
         if (T == 0) {
             // empty spectrogram: no signals; `_spectrogram_last` becomes an empty map
             const size_t sb = (size_t)h->cfg.n_streams * sizeof(int32_t);
@@ -2552,19 +2528,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     };
     rc = enqueue();
     if (rc != RT_OK) {
-        h->dense_sticky = c.prev_dense_sticky;
-        h->minsum_slot = c.prev_minsum_slot;
-        if (c.no_last) {
-            for (int s = 0; s < h->cfg.n_streams; ++s)
-                if (sl.h_no_last[s]) h->reset_pending[(size_t)s] = 1;
-            h->any_reset_pending = true;
-        }
-        if (c.masked) {
-            h->pres.rollback(sl.pc, h->reset_pending);
-            h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
-        }
-        if (c.chained) h->chain.rollback(sl.cc);
-        if (c.iq_on) h->riq->book.rollback(h->riq->slot[&sl - h->slot].call);  // (the held sample tails are the ones before the call)
+        undo_call_books(h, sl);
         if (launched) {
             (void)hipStreamSynchronize(h->s_scan);
             (void)hipStreamSynchronize(h->s_detect);
@@ -2722,24 +2686,35 @@ static int before_rerun(rt_handle *h, Slot &sl) {
     return RT_OK;
 }
 
-// rt_fetch of one (lane-less) handle.  `peek`: wait, settle fall-backs and count, but deliver nothing and
-// keep the call pending even when it has no records (the laned rt_fetch sizes all lanes before it copies).
-static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bool peek) {
-    *n_out = 0;
-    Slot *slp = oldest_pending(h);
-    if (!slp) {
-        h->err = "rt_fetch without a preceding successful rt_process/rt_extract";
-        return RT_E_INVALID;
-    }
-    Slot &sl = *slp;
-    CallCtx &c = sl.call;
-    RT_HIP(h, hipSetDevice(h->cfg.device));
+// ... and the re-run itself: the same buffer with the same look-back state on `mode`, waited for; `flags` become its flag word.
+enum : unsigned {
+    kRerunClearMarks = 1,     // the per-stream overflow / inconsistency marks of the run before are dropped unread (and with them its partial dense streams)
+    kRerunMask = 2,           // a masked call's mask rows are built and uploaded again (the rows the scans take have changed)
+    kRerunSecondPassOnly = 4, // enqueue_analysis: second_pass_only
+    kRerunOwnMeans = 8,       // enqueue_analysis: own_means
+    kRerunNoWait = 16,        // the caller enqueues more behind it and calls await_call itself
+};
+static int await_call(rt_handle *h, Slot &sl, unsigned long long &flags) {
     RT_HIP(h, hipEventSynchronize(sl.ev_done));
-    unsigned long long flags = sl.h_counters[2];
-    h->info = rt_call_info{};
-    h->info.n_seg = c.n_seg;
-    h->info.segs_per_chunk = h->L;
-    h->info.n_hot = 0;
+    flags = sl.h_counters[2];
+    return RT_OK;
+}
+static int rerun(rt_handle *h, Slot &sl, int mode, unsigned long long &flags, unsigned how = 0) {
+    if (how & kRerunClearMarks) {
+        for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
+        sl.call.n_dense_streams = 0;
+    }
+    int rc = before_rerun(h, sl);
+    if (rc == RT_OK && (how & kRerunMask) && sl.call.masked) rc = upload_mask(h, sl);
+    if (rc == RT_OK) rc = enqueue_analysis(h, sl, mode, nullptr, (how & kRerunSecondPassOnly) != 0, (how & kRerunOwnMeans) != 0);
+    if (rc != RT_OK || (how & kRerunNoWait)) return rc;
+    return await_call(h, sl, flags);
+}
+
+// fetch_one, step 2: a stream the scans have newly marked for SciPy's order of the detrend has this call (and the one in flight
+// behind it) analysed again; `flags` become the re-run's.
+static int guard_detrend(rt_handle *h, Slot &sl, unsigned long long &flags) {
+    CallCtx &c = sl.call;
     // Guard of the detrend by linearity (rt_kernels.h: StftParams::dc_flag).  The form carries a stream's constant offset through
     // the transform: harmless while the offset is <= 60 dB over the per-sample noise (any <= 16-bit front end; <= 0.02 dB against
     // the oracle), 0.06 - 0.17 dB at 80 dB.  A scan that meets such a stream marks it; from then on that stream -- and only that
@@ -2765,11 +2740,8 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
             ++h->sub_epoch;
         }
         if (c.sub_epoch != h->sub_epoch) {
-            for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
-            c.n_dense_streams = 0;
-            int rc = before_rerun(h, sl);
-            if (rc == RT_OK && c.masked) rc = upload_mask(h, sl);  // (the marked streams are part of the rows the scans take)
-            if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used);  // (takes the current epoch)
+            // (the marked streams are part of the mask rows the scans take; the re-run takes the current epoch)
+            int rc = rerun(h, sl, c.mode_used, flags, kRerunClearMarks | kRerunMask | kRerunNoWait);
             if (rc != RT_OK) return rc;
             // The call enqueued behind this one (at most one is in flight) was analysed under the old set as well, and the next
             // rt_process will read the look-back columns it wrote: it is analysed again HERE, in sequence order, before anything
@@ -2791,64 +2763,60 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
                 rc = enqueue_analysis(h, o, o.call.mode_used);  // (behind this call's re-run on s_scan; its scratch is its slot's)
                 if (rc != RT_OK) return rc;
             }
-            RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            flags = sl.h_counters[2];
+            rc = await_call(h, sl, flags);
+            if (rc != RT_OK) return rc;
             for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_dc_flag[s] = 0;  // (marked streams mark themselves again: nothing new)
         }
     }
-  for (;;) {  // (a second round only after the record pool had to grow)
-    RT_TRACE_FETCH(h, sl, "round");
-    while ((flags & kFlagHotOverflow) && !c.is_extract && c.mode_used != RT_MODE_DENSE) {
-        RT_TRACE_FETCH(h, sl, "hot overflow");
-        // which streams overflowed?  (the flags are consumed here, whatever happens next)  The scan stops emitting for a
-        // stream once one of its lists has overflowed, so a "run without its preceding cell" in such a stream is not an
-        // internal error; in any other stream it is.
-        int n_bad = 0;
-        bool incons_elsewhere = false;
-        for (int s = 0; s < h->cfg.n_streams; ++s) {
-            if (sl.h_incons[s] && !sl.h_overflow[s]) incons_elsewhere = true;
-            sl.h_incons[s] = 0;
-            if (sl.h_overflow[s]) {
-                if (n_bad < kMaxPartial) sl.h_list[n_bad] = s;
-                ++n_bad;
-                sl.h_overflow[s] = 0;
+    return RT_OK;
+}
+
+// fetch_one, step 3: while the call's analysis does not stand -- candidate lists overflowed (what then: rt_core.h, overflow_step), or
+// a capacity or pool was too small -- it is analysed again.  `peek`: see fetch_one.
+static int rerun_until_it_stands(rt_handle *h, Slot &sl, unsigned long long &flags, bool peek) {
+    CallCtx &c = sl.call;
+    const bool can_rerun = !c.is_extract && c.n_seg > 0;  // (rt_extract: the caller's spectrogram is not kept)
+    for (;;) {  // (a second round only after something had to grow)
+        RT_TRACE_FETCH(h, sl, "round");
+        while ((flags & kFlagHotOverflow) && !c.is_extract && c.mode_used != RT_MODE_DENSE) {
+            RT_TRACE_FETCH(h, sl, "hot overflow");
+            // which streams overflowed?  (the flags are consumed here, whatever happens next)  The scan stops emitting for a
+            // stream once one of its lists has overflowed, so a "run without its preceding cell" in such a stream is not an
+            // internal error; in any other stream it is.
+            int n_bad = 0;
+            bool incons_elsewhere = false;
+            for (int s = 0; s < h->cfg.n_streams; ++s) {
+                if (sl.h_incons[s] && !sl.h_overflow[s]) incons_elsewhere = true;
+                sl.h_incons[s] = 0;
+                if (sl.h_overflow[s]) {
+                    if (n_bad < kMaxPartial) sl.h_list[n_bad] = s;
+                    ++n_bad;
+                    sl.h_overflow[s] = 0;
+                }
             }
-        }
-        // The per-bin thresholds of the exact pre-filter were too high for some streams (their noise floor fell from the
-        // buffer before to this one): not a matter of capacity.  A few streams of many go dense on their own below (AUTO);
-        // otherwise the call is analysed again on the same level, its thresholds now taken from its own row means --
-        // the handle's level does not change, and an explicit RT_MODE_RUNFILTER handle does not fail.
-        const bool stale = (flags & kFlagThrStale) && c.mode_used == RT_MODE_RUNFILTER && !c.thr_rerun;
-        flags &= ~kFlagThrStale;
-        const bool few = n_bad > 0 && n_bad <= kMaxPartial && 4 * n_bad <= h->cfg.n_streams &&
-                         !(c.mode_used == RT_MODE_SPARSE && level_up(h, RT_MODE_SPARSE) != RT_MODE_DENSE);
-        if (stale && !(h->cfg.mode == RT_MODE_AUTO && few)) {
-            c.thr_rerun = true;
-            int rc = before_rerun(h, sl);
-            if (rc == RT_OK) rc = enqueue_analysis(h, sl, RT_MODE_RUNFILTER, nullptr, false, true);
-            if (rc != RT_OK) return rc;
-            RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            flags = sl.h_counters[2];
-            continue;
-        }
-        if (h->cfg.mode != RT_MODE_AUTO) {
-            h->err = "candidate-cell capacity exceeded (hot_capacity)";
-            if (peek) return kCallFailed;  // the laned rt_fetch drops this call in every lane together
-            c.pending = false;
-            return RT_E_HOT_OVERFLOW;
-        }
-        {
-            // a few of many: only they go dense, the handle stays on its level
-            // (where the pre-filter level is still ahead, the whole batch goes there first: its second pass costs less
-            // than the fixed ~1 ms of a dense re-run of a few streams -- one workgroup per stream in detect_dense)
-            if (few) {
+            const AutoOverflow step = overflow_step(c.mode_used, c.thr_rerun, (flags & kFlagThrStale) != 0, n_bad, h->cfg.n_streams, h->cfg.mode, h->ap.lv);
+            flags &= ~kFlagThrStale;
+            if (step == kOverflowOwnMeans) {
+                c.thr_rerun = true;
+                const int rc = rerun(h, sl, RT_MODE_RUNFILTER, flags, kRerunOwnMeans);
+                if (rc != RT_OK) return rc;
+                continue;
+            }
+            if (step == kOverflowFail) {
+                h->err = "candidate-cell capacity exceeded (hot_capacity)";
+                if (peek) return kCallFailed;  // the laned rt_fetch drops this call in every lane together
+                c.pending = false;
+                return RT_E_HOT_OVERFLOW;
+            }
+            if (step == kOverflowPartialDense) {
                 const unsigned long long other = flags & ~(kFlagHotOverflow | (incons_elsewhere ? 0ull : kFlagInconsistent));
                 const unsigned long long wanted_so_far = sl.h_counters[4];  // (a stream OUTSIDE the few may have outgrown its record capacity)
                 int rc = before_rerun(h, sl);
                 if (rc == RT_OK) rc = enqueue_partial_dense(h, sl, n_bad, sl.h_counters[0]);
                 if (rc == RT_OK) {
-                    RT_HIP(h, hipEventSynchronize(sl.ev_done));
-                    flags = other | sl.h_counters[2];
+                    rc = await_call(h, sl, flags);
+                    if (rc != RT_OK) return rc;
+                    flags |= other;
                     sl.h_counters[2] = flags;  // (the laned rt_fetch looks at this call twice: sizing, then delivery)
                     // ... and what that stream wanted survives the partial run's own counter words: the record-overflow flag kept in `other`
                     // without it was a truncated delivery (round 6's soak, seed 64 case 56)
@@ -2861,84 +2829,73 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
                 // level up instead, which needs no scratch of its own or reports its own failure
                 if (rc != RT_E_NOMEM) return rc;
             }
-        }
-        // Re-run of the same buffer with the same look-back state, one level up.  Its scan queues up behind whatever is in
-        // flight on the handle's scan stream and behind the later call's detection (before_rerun: that call read the tail
-        // columns this call's first scan already wrote -- the re-run writes the same values); other lanes' streams are left alone.
-        const int from = c.mode_used;
-        c.mode_used = level_up(h, from);
-        // stay on that level for a while; every further failed probe doubles the while (a probe costs a wasted scan;
-        // a call that climbs two levels counts once)
-        h->auto_level = c.mode_used;
-        if (!c.fell_back) {
-            h->dense_sticky = h->sticky_len;
-            h->sticky_len = std::min(h->sticky_len * 2, 1024);
-        }
-        c.fell_back = true;
-        int rc = before_rerun(h, sl);
-        if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used, nullptr, from == RT_MODE_SPARSE && c.mode_used == RT_MODE_PREFILTER);
-        if (rc != RT_OK) return rc;
-        RT_HIP(h, hipEventSynchronize(sl.ev_done));
-        flags = sl.h_counters[2];
-    }
-    // The call found more records than the slot's pinned pool holds (word 0 = records wanted): streams beyond its end
-    // got truncated lists.  The pool grows and the call is analysed again on the level it ended on -- same buffer, same
-    // look-back state, like a fall-back re-run -- so the caller loses nothing; later calls find the larger pool.  Not
-    // possible for rt_extract (the caller's spectrogram is not kept) or when the host has no memory left: then the
-    // truncated lists are delivered with RT_E_CAPACITY.
-    // A stream wanted more records than the handle's per-stream capacity holds (word 4): the capacity grows and the call is
-    // analysed again, like a call that outgrew the pool -- the reference has no limit (analyze.py:449-450).  Up to three times per
-    // call (a re-run on a higher level may find more).  rt_extract cannot (the caller's spectrogram is not kept).
-    // (Measured against the capacity the call's kernels RAN with: with two calls in flight the first one's growth may already cover what
-    // the second one wanted -- its lists were still cut at the old capacity.)
-    if ((flags & kFlagRecOverflow) && !c.is_extract && c.n_seg > 0 && sl.h_counters[4] > (unsigned long long)c.rec_cap_used && c.cap_grown < 3) {
-        if (grow_record_capacity(h, sl.h_counters[4]) == RT_OK) {
-            RT_TRACE_FETCH(h, sl, "capacity grown");
-            ++c.cap_grown;
-            for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
-            c.n_dense_streams = 0;
-            int rc = before_rerun(h, sl);
-            if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used);
+            // Re-run of the same buffer with the same look-back state, one level up.  Its scan queues up behind whatever is in
+            // flight on the handle's scan stream and behind the later call's detection (before_rerun: that call read the tail
+            // columns this call's first scan already wrote -- the re-run writes the same values); other lanes' streams are left alone.
+            const int from = c.mode_used;
+            c.mode_used = h->ap.climb(from, !c.fell_back);
+            c.fell_back = true;
+            const int rc = rerun(h, sl, c.mode_used, flags, from == RT_MODE_SPARSE && c.mode_used == RT_MODE_PREFILTER ? kRerunSecondPassOnly : 0u);
             if (rc != RT_OK) return rc;
-            RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            flags = sl.h_counters[2];
-            continue;
         }
-    }
-    if ((flags & kFlagRecOverflow) && !c.is_extract && c.n_seg > 0 && sl.h_counters[0] > (unsigned long long)sl.pool_cap &&
-        sl.pool_cap < h->pool_max && c.pool_grown < 3) {
-        if (grow_pool(h, sl, (int64_t)std::min<unsigned long long>(sl.h_counters[0], (unsigned long long)h->pool_max)) == RT_OK) {
-            RT_TRACE_FETCH(h, sl, "pool grown");
-            ++c.pool_grown;  // (up to three times: a partial dense re-run finds more records in its streams than the run the pool was sized from counted)
-            for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
-            c.n_dense_streams = 0;
-            int rc = before_rerun(h, sl);
-            if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used);
-            if (rc != RT_OK) return rc;
-            RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            flags = sl.h_counters[2];
-            continue;
-        }
-    }
-    // RT_FLAG_RECORD_CELLS: the call's records hold more cells than the slot's pool (word 0 of the gather's words): the pool grows
-    // and the call is analysed again, like a call that outgrew the record pool -- the gather reads a map that is gone by now.
-    if (sl.d_cells && !c.is_extract && c.n_seg > 0 && sl.h_cells_info[0] > (unsigned long long)sl.cell_cap && c.cells_grown < 3) {
-        if (grow_cells(h, sl.d_cells, sl.cell_cap, (int64_t)sl.h_cells_info[0]) == RT_OK) {
-            RT_TRACE_FETCH(h, sl, "cell pool grown");
-            ++c.cells_grown;
+        // Something was too small for what the call found; it grows and the call is analysed again on the level it ended on -- same
+        // buffer, same look-back state, like a fall-back re-run -- so the caller loses nothing.  Up to three times each per call (a
+        // re-run on a higher level, or a partial dense one, may find more).  Where it cannot grow (rt_extract; no memory left) the
+        // truncated lists are delivered with RT_E_CAPACITY.
+        const char *grown = nullptr;
+        int *times = nullptr;
+        if ((flags & kFlagRecOverflow) && can_rerun && sl.h_counters[4] > (unsigned long long)c.rec_cap_used && c.cap_grown < 3 &&
+            grow_record_capacity(h, sl.h_counters[4]) == RT_OK) {
+            // A stream wanted more records than the handle's per-stream capacity holds (word 4) -- the reference has no limit
+            // (analyze.py:449-450).  (Measured against the capacity the call's kernels RAN with: with two calls in flight the first one's
+            // growth may already cover what the second one wanted -- its lists were still cut at the old capacity.)
+            grown = "capacity grown";
+            times = &c.cap_grown;
+        } else if ((flags & kFlagRecOverflow) && can_rerun && sl.h_counters[0] > (unsigned long long)sl.pool_cap && sl.pool_cap < h->pool_max &&
+                   c.pool_grown < 3 && grow_pool(h, sl, (int64_t)std::min<unsigned long long>(sl.h_counters[0], (unsigned long long)h->pool_max)) == RT_OK) {
+            // The call found more records than the slot's pinned pool holds (word 0 = records wanted): streams beyond its end got
+            // truncated lists.  Later calls find the larger pool.
+            grown = "pool grown";
+            times = &c.pool_grown;
+        } else if (sl.d_cells && can_rerun && sl.h_cells_info[0] > (unsigned long long)sl.cell_cap && c.cells_grown < 3 &&
+                   grow_cells(h, sl.d_cells, sl.cell_cap, (int64_t)sl.h_cells_info[0]) == RT_OK) {
+            // RT_FLAG_RECORD_CELLS: the call's records hold more cells than the slot's pool (word 0 of the gather's words) -- the
+            // gather reads a map that is gone by now.
+            grown = "cell pool grown";
+            times = &c.cells_grown;
             h->cells_want = std::max(h->cells_want, sl.cell_cap);
-            for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_overflow[s] = sl.h_incons[s] = 0;
-            c.n_dense_streams = 0;
-            int rc = before_rerun(h, sl);
-            if (rc == RT_OK) rc = enqueue_analysis(h, sl, c.mode_used);
-            if (rc != RT_OK) return rc;
-            RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            flags = sl.h_counters[2];
-            continue;
         }
+        if (!grown) return RT_OK;
+        RT_TRACE_FETCH(h, sl, grown);
+        ++*times;
+        const int rc = rerun(h, sl, c.mode_used, flags, kRerunClearMarks);
+        if (rc != RT_OK) return rc;
     }
-    break;
-  }
+}
+
+// rt_fetch of one (lane-less) handle: wait for the call, guard its detrend, analyse it again until its result stands, tell the
+// AUTO policy, deliver.  `peek`: all but the delivery, and the call stays pending even when it has no records (the laned rt_fetch
+// sizes all lanes before it copies).
+static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bool peek) {
+    *n_out = 0;
+    Slot *slp = oldest_pending(h);
+    if (!slp) {
+        h->err = "rt_fetch without a preceding successful rt_process/rt_extract";
+        return RT_E_INVALID;
+    }
+    Slot &sl = *slp;
+    CallCtx &c = sl.call;
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    unsigned long long flags = 0;
+    int rc = await_call(h, sl, flags);
+    if (rc != RT_OK) return rc;
+    h->info = rt_call_info{};
+    h->info.n_seg = c.n_seg;
+    h->info.segs_per_chunk = h->L;
+    h->info.n_hot = 0;
+    rc = guard_detrend(h, sl, flags);
+    if (rc == RT_OK) rc = rerun_until_it_stands(h, sl, flags, peek);
+    if (rc != RT_OK) return rc;
     RT_TRACE_FETCH(h, sl, "settled");
     if (c.mode_used != RT_MODE_DENSE && !c.is_extract && c.n_seg > 0)
         for (int s = 0; s < h->cfg.n_streams; ++s) h->info.n_hot += sl.h_hot_total[s];
@@ -2947,33 +2904,8 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
     // (a call with a presence mask: the streams that took part -- an absent one adds nothing to either side of these ratios)
     const int64_t n_took_part = c.masked ? sl.pc.n_present : h->cfg.n_streams;
     if (c.mode_used != RT_MODE_DENSE && !c.is_extract && c.n_seg > 0) h->group_light = h->info.n_hot * 2 <= (int64_t)kGroupCells * n_took_part;
-    // (the exact pre-filter on input where it is not selective: see below)
-    bool unselective = h->cfg.mode == RT_MODE_AUTO && c.mode_used == RT_MODE_RUNFILTER && !c.is_extract && c.n_seg > 0 && sl.h_seg_total &&
-                       (int64_t)*sl.h_seg_total * 2 > n_took_part * c.n_seg;
-    // ... or a pre-filter level that went through with more than 1/32 of all cells on its candidate lists (possible where
-    // hot_capacity was raised: signals whose side lobes fill every bin put 9 % of the cells there, and ordering lists of
-    // 16 k cells per bucket took 14 - 18 ms per call where the dense path takes 1.9)
-    if (h->cfg.mode == RT_MODE_AUTO && (c.mode_used == RT_MODE_RUNFILTER || c.mode_used == RT_MODE_PREFILTER) && !c.is_extract && c.n_seg > 0 &&
-        h->info.n_hot * 32 > n_took_part * c.n_seg * h->N)
-        unselective = true;
-    if (c.level_settled) {
-        unselective = false;  // (settled on the first pass: the probe interval doubles once per call, not once per pass)
-    } else if (h->cfg.mode == RT_MODE_AUTO && !c.is_extract && !c.fell_back && c.n_seg > 0 && level_rank(c.mode_used) < level_rank(h->auto_level) && !unselective) {
-        // a probe of a lower level went through: the handle moves there (and from the pre-filter level it will
-        // probe the plain sparse path after the usual interval)
-        h->auto_level = c.mode_used;
-        h->sticky_len = 16;
-        h->dense_sticky = (c.mode_used == RT_MODE_SPARSE) ? 0 : 16;
-    }
-    if (unselective) {
-        // The pre-filter went through, but more than half of all segments held cells it has to keep (or see above): its second scan
-        // is then most of a scan, and the dense path (one scan, 16 B per sample) is faster -- measured at the reference's
-        // default geometry with the noise floor 2 dB over the threshold: 213 k against 241 k MS/s.  The handle moves up like
-        // after an overflow (without analysing this call again: its result stands) and probes this level later.
-        h->auto_level = level_up(h, c.mode_used);
-        h->dense_sticky = h->sticky_len;
-        h->sticky_len = std::min(h->sticky_len * 2, 1024);
-    }
+    h->ap.settle(c.level_settled, h->cfg.mode, c.mode_used, c.fell_back, !c.is_extract && c.n_seg > 0, h->info.n_hot, sl.h_seg_total ? (int64_t)*sl.h_seg_total : -1,
+                 n_took_part, c.n_seg, h->N);
     c.level_settled = true;
     if (flags & kFlagInconsistent) {
         std::memset(sl.h_incons, 0, (size_t)h->cfg.n_streams * sizeof(int32_t));
@@ -2987,12 +2919,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
         (void)hipEventElapsedTime(&h->info.ms_detect, sl.ev_scan, sl.ev_done);
         (void)hipEventElapsedTime(&h->info.ms_total, sl.ev_begin, sl.ev_done);
     }
-    if (c.abs_counted && sl.h_abs_hot) {
-        h->abs_hot_seen = *sl.h_abs_hot;
-        h->abs_hot_valid = true;
-    } else if (c.mode_used == RT_MODE_DENSE && c.n_dense_streams == 0) {
-        h->abs_hot_valid = false;  // (the dense path keeps no count: what was seen is history by the time it is left)
-    }
+    h->ap.keep_abs_hot(c.abs_counted && sl.h_abs_hot, sl.h_abs_hot ? *sl.h_abs_hot : 0u, c.mode_used, c.n_dense_streams);
     h->info.mode_used = c.mode_used;
     h->info.fell_back = c.fell_back ? 1 : 0;
     h->info.n_dense_streams = c.n_dense_streams;

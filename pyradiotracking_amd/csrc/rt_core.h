@@ -13,6 +13,7 @@
 //                                      (delta_new / accum), used by the shadow
 //                                      filter analyze.py:300-311 (T16)
 // and the geometry a handle derives from its configuration on the host (look-back columns, chunk length, kernel family),
+// RT_MODE_AUTO's choice of level from call to call (AutoPolicy),
 // and the per-stream bookkeeping of a handle whose streams may sit out a call (rt_set_present: PresenceBook).
 #ifndef RT_CORE_H
 #define RT_CORE_H
@@ -89,7 +90,7 @@ struct same_t {  // (keeps an argument out of template deduction: the power type
 // ---- RT_MODE_AUTO's levels (host-side bookkeeping of rt_analyze.hip; here so that the CPU suite can test it) ----
 // Order: sparse < chunk-bit pre-filter (where the geometry allows it) < exact pre-filter (where its scratch exists) < dense.
 // The mode numbers are rt_mode's (include/rt_analyze.h).
-enum : int { kAutoDense = 1, kAutoSparse = 2, kAutoPrefilter = 3, kAutoRunfilter = 4 };
+enum : int { kAutoAuto = 0, kAutoDense = 1, kAutoSparse = 2, kAutoPrefilter = 3, kAutoRunfilter = 4 };
 struct AutoLevels {
     bool prefilter_ok;  // the chunk-bit pre-filter exists at this geometry
     bool runfilter_ok;  // the exact pre-filter exists (and its scratch is allocated)
@@ -117,6 +118,120 @@ RT_HD bool probe_ruled_out(int target, int level, bool valid, uint64_t abs_hot, 
     if (target == kAutoPrefilter && level == kAutoRunfilter) return cells_per_stream > 0 && abs_hot * 4u > 3u * cells_per_stream;
     return false;
 }
+
+constexpr int kSlots = 2;        // calls a handle keeps in flight (rt_analyze.hip: one slot each)
+constexpr int kMaxPartial = 32;  // AUTO: up to this many overflowing streams of a batch are re-run dense on their own
+
+// What rt_fetch does with a call whose candidate lists overflowed (not rt_extract, not on the dense level): analyse it again on
+// the same level with thresholds from its own row means, fail with RT_E_HOT_OVERFLOW, re-run the overflowing streams dense on
+// their own, or re-run the whole call one level up (AutoPolicy::climb).
+enum AutoOverflow : int { kOverflowOwnMeans = 0, kOverflowFail = 1, kOverflowPartialDense = 2, kOverflowLevelUp = 3 };
+// `mode`: the level the call ran on; `thr_rerun`: it has been analysed on its own means already (once per call); `thr_stale`: its
+// kFlagThrStale bit; `n_bad` of `n_streams` streams overflowed; `cfg_mode`: rt_config.mode.
+//   * Stale: the per-bin thresholds of the exact pre-filter were too high for some streams (their noise floor fell from the buffer
+//     before to this one) -- not a matter of capacity.  A few streams of many go dense on their own (AUTO); otherwise the call is
+//     analysed again on the same level, its thresholds now taken from its own row means: the handle's level does not change, and
+//     an explicit RT_MODE_RUNFILTER handle does not fail.
+//   * Few: at most kMaxPartial streams and a quarter of the batch -- only they go dense, the handle stays on its level.  (Where a
+//     pre-filter level is still ahead of the sparse one, the whole batch goes there first: its second pass costs less than the fixed
+//     ~1 ms of a dense re-run of a few streams -- one workgroup per stream in detect_dense.)
+inline AutoOverflow overflow_step(int mode, bool thr_rerun, bool thr_stale, int n_bad, int n_streams, int cfg_mode, AutoLevels lv) {
+    const bool is_auto = cfg_mode == kAutoAuto;
+    const bool stale = thr_stale && mode == kAutoRunfilter && !thr_rerun;
+    const bool few = n_bad > 0 && n_bad <= kMaxPartial && 4 * n_bad <= n_streams && !(mode == kAutoSparse && level_up(lv, kAutoSparse) != kAutoDense);
+    if (stale && !(is_auto && few)) return kOverflowOwnMeans;
+    if (!is_auto) return kOverflowFail;
+    return few ? kOverflowPartialDense : kOverflowLevelUp;
+}
+
+// RT_MODE_AUTO's state machine: the one place its rules live.  Three ways to analyse a buffer and a fourth between
+// them, cheapest first -- RT_MODE_SPARSE (candidates emitted by the scan itself), RT_MODE_PREFILTER (two scan passes, rt_kernels.h;
+// only where lv.prefilter_ok), RT_MODE_RUNFILTER (where lv.runfilter_ok), RT_MODE_DENSE.  A call whose candidate lists overflow is
+// re-run one level up when it is fetched (overflow_step, climb); the handle then stays on that level for `dense_sticky` calls
+// before it probes the level below again (a failed probe costs a wasted scan: the interval doubles, 16 .. 1024).  Plain integers
+// in, plain integers out: rt_analyze.hip feeds it from a call's counters, the CPU suite from literal traces (hc_auto_*).
+struct AutoPolicy {
+    AutoLevels lv{false, false};
+    int level = kAutoSparse;  // the level the input last needed
+    int dense_sticky = 0;     // calls left on `level` before the next probe
+    int sticky_len = 16;      // ... and how many there will be after the next climb
+    // the most cells at or above the absolute threshold any stream had in the last call a pre-filter level analysed: more
+    // than the sparse lists hold (kBuckets x hot_capacity per stream) means a probe of the sparse level cannot succeed
+    uint32_t abs_hot_seen = 0;
+    bool abs_hot_valid = false;
+
+    // The mode a new call is enqueued with: the level the input last needed, for `dense_sticky` more calls; then a probe of the level
+    // below.  `list_cells` = kBuckets x hot_capacity, `cells_per_stream` = T x N (probe_ruled_out).  A handle pinned to a mode runs it.
+    int begin_call(int cfg_mode, uint64_t list_cells, uint64_t cells_per_stream) {
+        if (cfg_mode != kAutoAuto) return cfg_mode;
+        if (dense_sticky > 0) {
+            --dense_sticky;
+            return level;
+        }
+        int mode = level_down(lv, level);
+        // (no probe, no back-off where the last count rules the level below out: the next call looks again)
+        if (probe_ruled_out(mode, level, abs_hot_valid, abs_hot_seen, list_cells, cells_per_stream)) mode = level;
+        // one probe at a time: the calls enqueued before this one's verdict is in (the caller may keep a slot's
+        // worth of calls in flight) stay on the handle's level instead of each paying for a failed probe
+        if (mode != level) dense_sticky = kSlots;
+        return mode;
+    }
+    // What a call whose enqueue fails or that is rolled back puts back: taken before begin_call, nothing else of the policy has moved by then.
+    int restore_point() const { return dense_sticky; }
+    void restore(int point) { dense_sticky = point; }
+
+    // A call that ran on `from` is analysed again one level up (returned), and the handle goes there.  It stays for a while; every
+    // further failed probe doubles the while (a probe costs a wasted scan; `first`: a call that climbs two levels counts once).
+    int climb(int from, bool first) {
+        level = level_up(lv, from);
+        if (first) back_off();
+        return level;
+    }
+
+    // A call's analysis stands (every re-run is behind it): what it says about the handle's level.  `settled`: this call has been
+    // here before (rt_fetch passes over a call twice: size query / peek, then delivery) -- the probe interval doubles once per call,
+    // not once per pass.  `counts`: not an rt_extract, and it had segments.  `n_hot`: cells on the candidate lists; `seg_total`:
+    // segments the exact pre-filter's second scan took (< 0: no such count); `n_took_part`: streams present.
+    void settle(bool settled, int cfg_mode, int mode, bool fell_back, bool counts, int64_t n_hot, int64_t seg_total, int64_t n_took_part, int64_t n_seg,
+                int64_t N) {
+        if (settled || cfg_mode != kAutoAuto || !counts) return;
+        // The exact pre-filter went through, but more than half of all segments held cells it has to keep: its second scan is then
+        // most of a scan, and the dense path (one scan, 16 B per sample) is faster -- measured at the reference's default geometry
+        // with the noise floor 2 dB over the threshold: 213 k against 241 k MS/s ...
+        bool unselective = mode == kAutoRunfilter && seg_total >= 0 && seg_total * 2 > n_took_part * n_seg;
+        // ... or a pre-filter level went through with more than 1/32 of all cells on its candidate lists (possible where
+        // hot_capacity was raised: signals whose side lobes fill every bin put 9 % of the cells there, and ordering lists of
+        // 16 k cells per bucket took 14 - 18 ms per call where the dense path takes 1.9)
+        if ((mode == kAutoRunfilter || mode == kAutoPrefilter) && n_hot * 32 > n_took_part * n_seg * N) unselective = true;
+        if (unselective) {
+            // The handle moves up like after an overflow (without analysing this call again: its result stands) and probes this level later.
+            level = level_up(lv, mode);
+            back_off();
+        } else if (!fell_back && level_rank(mode) < level_rank(level)) {
+            // a probe of a lower level went through: the handle moves there (and from the pre-filter level it will
+            // probe the plain sparse path after the usual interval)
+            level = mode;
+            sticky_len = 16;
+            dense_sticky = (mode == kAutoSparse) ? 0 : 16;
+        }
+    }
+    // ... and about the next probe: the count of a call that kept one (`abs_counted`) stands until a whole batch runs dense
+    // (the dense path keeps no count: what was seen is history by the time it is left; a partial dense re-run leaves it alone).
+    void keep_abs_hot(bool abs_counted, uint32_t abs_hot, int mode, int n_dense_streams) {
+        if (abs_counted) {
+            abs_hot_seen = abs_hot;
+            abs_hot_valid = true;
+        } else if (mode == kAutoDense && n_dense_streams == 0) {
+            abs_hot_valid = false;
+        }
+    }
+
+private:
+    void back_off() {
+        dense_sticky = sticky_len;
+        sticky_len = std::min(sticky_len * 2, 1024);
+    }
+};
 
 // Chunks per "quiet level" sample of the exact pre-filter's per-bin thresholds (make_bin_thresholds): the quietest sum
 // over `g` consecutive complete chunks of a workgroup's item, g the smallest power of two with g * L >= 32 segments (at

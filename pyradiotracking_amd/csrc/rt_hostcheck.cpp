@@ -96,6 +96,41 @@ int hc_probe_ruled_out(int target, int level, int valid, unsigned long long abs_
     return probe_ruled_out(target, level, valid != 0, abs_hot, list_cells, cells_per_stream) ? 1 : 0;
 }
 
+// ---- RT_MODE_AUTO's state machine (rt_core.h: AutoPolicy, overflow_step), operation by operation as rt_analyze.hip calls it ----
+void *hc_auto_new(int prefilter_ok, int runfilter_ok) {
+    AutoPolicy *p = new AutoPolicy();
+    p->lv = AutoLevels{prefilter_ok != 0, runfilter_ok != 0};
+    return p;
+}
+void hc_auto_free(void *p) { delete static_cast<AutoPolicy *>(p); }
+// returns the mode the call is enqueued with; *restore_point = what hc_auto_restore takes to undo it
+int hc_auto_begin_call(void *p, int cfg_mode, unsigned long long list_cells, unsigned long long cells_per_stream, int *restore_point) {
+    AutoPolicy *a = static_cast<AutoPolicy *>(p);
+    *restore_point = a->restore_point();
+    return a->begin_call(cfg_mode, list_cells, cells_per_stream);
+}
+void hc_auto_restore(void *p, int restore_point) { static_cast<AutoPolicy *>(p)->restore(restore_point); }
+int hc_auto_overflow_step(int mode, int thr_rerun, int thr_stale, int n_bad, int n_streams, int cfg_mode, int prefilter_ok, int runfilter_ok) {
+    return overflow_step(mode, thr_rerun != 0, thr_stale != 0, n_bad, n_streams, cfg_mode, AutoLevels{prefilter_ok != 0, runfilter_ok != 0});
+}
+int hc_auto_climb(void *p, int from, int first) { return static_cast<AutoPolicy *>(p)->climb(from, first != 0); }
+// (both halves of what fetch_one tells the policy about a call whose result stands)
+void hc_auto_settle(void *p, int settled, int cfg_mode, int mode, int fell_back, int counts, long long n_hot, long long seg_total, long long n_took_part,
+                    long long n_seg, long long N, int abs_counted, unsigned abs_hot, int n_dense_streams) {
+    AutoPolicy *a = static_cast<AutoPolicy *>(p);
+    a->settle(settled != 0, cfg_mode, mode, fell_back != 0, counts != 0, n_hot, seg_total, n_took_part, n_seg, N);
+    a->keep_abs_hot(abs_counted != 0, abs_hot, mode, n_dense_streams);
+}
+// out[5]: level, dense_sticky, sticky_len, abs_hot_seen, abs_hot_valid
+void hc_auto_state(void *p, long long *out) {
+    const AutoPolicy *a = static_cast<AutoPolicy *>(p);
+    out[0] = a->level;
+    out[1] = a->dense_sticky;
+    out[2] = a->sticky_len;
+    out[3] = a->abs_hot_seen;
+    out[4] = a->abs_hot_valid ? 1 : 0;
+}
+
 // how often a cell of a chunk of L segments is counted by the sampled absolute-threshold bits (rt_core.h: abs_sampled):
 // the sampled steps of i = 1 .. L under `phase`, times the period
 int hc_abs_sample_period(int L) { return abs_sample_period(L); }
