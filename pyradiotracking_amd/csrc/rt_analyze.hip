@@ -37,6 +37,7 @@
 #include "rt_present.h"
 #include "rt_chain.h"
 #include "rt_record_iq.h"
+#include "rt_ledger.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -78,7 +79,6 @@ struct CallCtx {
     bool fell_back = false;
     bool is_extract = false;
     int fmt = kFmtC64;      // the format the IQ was enqueued in: complex64, interleaved uint8 (RTL-SDR wire format), int16 (CS16) or int8 (CS8)
-    bool no_last = false;   // the slot's h_no_last flags apply (some stream was reset, rt_reset_stream)
     int n_dense_streams = 0;  // streams of this call that were re-run dense on their own (AUTO, partial fall-back)
     int pool_grown = 0;       // times the record pool was enlarged for this call and the call analysed again (fetch_one)
     int cap_grown = 0;        // times the handle's per-stream record capacity was enlarged for this call (fetch_one: grow_record_capacity)
@@ -89,11 +89,8 @@ struct CallCtx {
     bool ran_lin = false;     // its scans detrended by linearity (fetch_one: analysed again if the guard marks a stream)
     uint64_t sub_epoch = 0;   // rt_handle::sub_epoch when its kernels were enqueued
     int cells_grown = 0;      // times the slot's cell pool was enlarged for this call and the call analysed again (RT_FLAG_RECORD_CELLS)
-    bool masked = false;      // enqueued on a handle with a presence mask (rt_set_present): the slot's `pc` and mask arrays are this call's
-    bool chained = false;     // enqueued on a chained handle (rt_set_chain): the slot's `cc`, chain rows and d_chain are this call's
-    bool iq_on = false;       // enqueued with rt_set_record_iq on: the slot's IqSlot::call is this call's (RecordIq)
     // handle state before this call (restored when the call is rolled back: a later lane failed to enqueue)
-    int prev_tail_cur = 0, prev_n_seg_last = -1, prev_auto = 0 /* AutoPolicy::restore_point */, prev_minsum_slot = -1;
+    int prev_auto = 0 /* AutoPolicy::restore_point */, prev_minsum_slot = -1;
 };
 
 constexpr int kRowMeansNone = -1, kRowMeansExtract = -2;  // rt_handle::rm_slot / F64State::rm_slot without valid row means
@@ -140,17 +137,16 @@ struct Slot {
     unsigned long long *h_cells_info = nullptr;                // pinned: [0] cells the call wants, [1] a record's cells were not all found
     // rt_set_present only (allocated by the handle's first call of the entry).  The snapshot a call was enqueued with -- every
     // analysis of the call inside rt_fetch uses it again -- and its device form, kMaskRows rows of [S] (pinned copy beside it):
-    PresenceCall pc;
     int32_t *h_mask = nullptr, *d_mask = nullptr;
     int n_lin_present = 0, n_sub_present = 0, n_absent = 0;  // entries of the rows kMaskLinList / kMaskSubList / kMaskAbsentList
     // rt_set_chain only (allocated by the handle's first call of the entry with links >= 2).  The sources a call was enqueued with
     // (rt_core.h: ChainCall), their device form -- two rows of [S]: ChainCall::src_buf, src_idx (pinned copy beside it) -- and the
     // look-back columns its detection reads, [S][K][N] as a rotation buffer (rt_chain.h: chain_tails writes them):
-    ChainCall cc;
     int32_t *h_chain_rows = nullptr, *d_chain_rows = nullptr;
     float *d_chain = nullptr;
     hipEvent_t ev_begin = nullptr, ev_first = nullptr, ev_scan = nullptr, ev_done = nullptr;  // first launch; end of the first scan; end of the scans; end of the call
     CallCtx call;
+    LedgerCall lc;  // what the ledger decided for `call` (rt_ledger.h): the mask, chain and record-IQ rows above are its device form
 };
 // rows of Slot::d_mask
 enum : int {
@@ -169,7 +165,7 @@ enum : int {
 struct F64Slot {
     bool pending = false;
     uint64_t seq = 0;
-    bool is_extract = false, no_last = false;
+    bool is_extract = false;
     int fmt = kFmtC64;  // (as CallCtx::fmt)
     const void *iq = nullptr;  // device IQ of the call (the caller's, or d_stage)
     int64_t stream_stride = 0;
@@ -180,7 +176,6 @@ struct F64Slot {
     rt_record_f64 *d_raw = nullptr;                    // [S][rec_cap]
     int32_t *d_raw_count = nullptr;                    // [S]
     int32_t *d_no_last = nullptr;                      // [S]
-    std::vector<int32_t> no_last_h;
     rt_record_f64 *h_out = nullptr;                    // pinned, device-visible: [S * rec_cap] the call's records
     double *d_row_means = nullptr;                     // [S][N] the call's row means (RT_FLAG_ROW_MEANS only; rt_fetch_row_means_f64 copies them)
     int32_t *h_meta = nullptr;                         // pinned, device-visible: [S + 1] offsets + total, then [S] wanted
@@ -192,8 +187,6 @@ struct F64Slot {
     long long *d_stream_cells = nullptr, *d_stream_base = nullptr;
     unsigned long long *h_cells_info = nullptr;
     // rt_set_present only, as in Slot (rows kMaskAbsent, kMaskNSegLast and kMaskAbsentList are used)
-    PresenceCall pc;
-    bool masked = false;
     int32_t *h_mask = nullptr, *d_mask = nullptr;
     int n_absent = 0;
     // RT_FLAG_F64_SPARSE only: the call's candidate lists (rt_f64_sparse.h)
@@ -202,8 +195,8 @@ struct F64Slot {
     int32_t *d_cell_count = nullptr;  // [S], zero between calls
     int32_t *h_hot = nullptr;      // pinned, device-visible: [S] cells each stream emitted
     int n_rescued = -1;            // RT_FLAG_F64_RESCUE: streams of the enqueued call rt_fetch_f64 has analysed again (-1: not looked at yet)
-    bool iq_on = false;            // enqueued with rt_set_record_iq on (as CallCtx::iq_on)
     hipEvent_t ev_done = nullptr;
+    LedgerCall lc;                 // as Slot::lc
 };
 struct F64State {
     rt_config_f64 c{};
@@ -213,20 +206,16 @@ struct F64State {
     cd *d_cwin = nullptr, *d_bfilt = nullptr, *d_tw = nullptr;
     double *d_map = nullptr;
     double *d_tail[kTails] = {nullptr, nullptr, nullptr};
-    int tail_cur = 0, n_seg_last = -1;
     double *d_thr_s = nullptr, *d_cal_s = nullptr;
     std::vector<double> h_thr_s;
     StreamSettings64 *d_set_s = nullptr;  // [S] rt_set_stream_settings_f64, or null: rt_config's for every stream
     std::vector<StreamSettings64> h_set_s;
-    std::vector<uint8_t> reset_pending;
-    bool any_reset = false;
     int rec_cap = 1024;
     uint64_t n_calls = 0;
     F64Slot slot[kSlots];
     int rm_slot = -1;  // the slot of the call rt_fetch_f64 delivered last, while its row means are valid (kRowMeansNone / kRowMeansExtract)
     bool cells_full = false;  // ... and that call was delivered in full (rt_fetch_record_cells_f64)
     int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
-    PresenceBook pres;        // rt_set_present: per-stream segment counts and the mask in force (inactive until the entry is called)
     // RT_FLAG_F64_SPARSE: no d_map; the scan's chunk geometry, the partial row sums (rewritten by every call) and the folded sums
     bool sparse = false;
     int group = 1, chunk = 1, chunk_cap = 0, hot_cap = 0, sort_cap = 0;
@@ -246,7 +235,6 @@ struct F64State {
 constexpr int kIqNone = -1, kIqExtract = -2, kIqTruncated = -3, kIqOff = -4;  // RecordIq::delivered without a slot
 constexpr size_t kInitialIqPoolBytes = 1u << 20;  // a slot's byte pool at first need; a call that wants more grows it inside rt_fetch
 struct IqSlot {
-    IqCall call;                                     // what the slot's call was enqueued with
     int32_t *h_rows = nullptr, *d_rows = nullptr;    // [S] IqCall::write_buf, pinned / device (iq_tails reads it)
     char *d_pool = nullptr;                          // the snippets of the slot's delivered call, in record order
     size_t pool_bytes = 0;
@@ -259,7 +247,6 @@ struct IqSlot {
     std::string why;
 };
 struct RecordIq {
-    IqTailBook book;
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
     int64_t row_bytes = 0;     // (K + m) * N * area_bps, rounded up to 16
     int area_bps = 0;          // bytes per sample of the widest format seen so far
@@ -333,10 +320,8 @@ struct rt_handle {
     uint64_t test_enqueues = 0;  // laned handle: rt_process calls seen (fault injection, read once at rt_create: RT_TEST_FAIL_LANE=<lane>:<n>)
     int test_fail_lane = -1, test_fail_nth = 0;
     int tail_mode = 0;     // 0: a call's planning kernels and second scan in order on s_scan; 1: on s_detect with the detection (enqueue_analysis)
-    int tail_cur = 0;      // tail buffer holding the most recent buffer's columns
-    int n_seg_last = -1;
-    std::vector<uint8_t> reset_pending;  // [S] streams whose look-back is dropped at the next rt_process
-    bool any_reset_pending = false;
+    StreamLedger ledger;   // the look-back state, float32 and float64 handles alike (rt_ledger.h); a laned handle: its lanes hold theirs
+    LedgerCall lc_saved;   // the snapshot of the call a new one displaced from its slot, while that call may still be put back (claim_slot)
     float *d_thr_s = nullptr, *d_cal_s = nullptr;  // [S] per-stream thresholds / calibration (rt_set_stream_params)
     // [S] per-stream snr_threshold, duration gates and probe stride (rt_set_stream_settings), or null: rt_config's for every stream.
     // K, prefilter_ok and run_cells stay derived from rt_config's durations, the envelope of every stream's.
@@ -357,12 +342,8 @@ struct rt_handle {
     bool cells_full = false;  // RT_FLAG_RECORD_CELLS: ... and that call was delivered in full: its cells can be fetched (rt_fetch_record_cells)
     int64_t cells_want = 0;   // cells every slot's pool should hold: the largest size any call has needed so far
 
-    // rt_set_present (rt_core.h: PresenceBook): inactive -- and nothing below used -- until the entry is called
-    PresenceBook pres;
     size_t chunk_min_bytes = 0;         // bytes of a slot's d_chunk_min (0: none)
     const Slot *launch_mask = nullptr;  // while a masked call's kernels are being enqueued: the slot whose mask rows its scans take (launch_stft)
-    // rt_set_chain (rt_core.h: ChainBook): off -- and nothing of it used -- until the entry is called with links >= 2
-    ChainBook chain;
     std::vector<float> h_cal_s;  // host copy of the per-stream calibration (empty: rt_config's for every stream): rt_set_chain's uniformity check
 
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
@@ -501,7 +482,7 @@ void launch_stft(rt_handle *h, const StftParams &p, int blocks, hipStream_t st) 
     const Slot *const mk = (MODE != 3 && !p.stream_list) ? h->launch_mask : nullptr;
     if (mk) {
         const int S = h->cfg.n_streams;
-        const int n_present = mk->pc.n_present;
+        const int n_present = mk->lc.pc.n_present;
         if (n_present == 0) return;
         StftParams q = p;
         if (h->lin && !U8) {
@@ -714,8 +695,8 @@ DetectArgs make_detect_args(rt_handle *h, Slot &sl, int n_seg, int n_bins, int n
     a.thr_s = h->d_thr_s;
     a.cal_s = h->d_cal_s;
     a.set_s = h->d_set_s;
-    a.no_last = sl.call.no_last ? sl.h_no_last : nullptr;
-    if (sl.call.masked) {  // rt_set_present: each stream's own previous segment count (a reset taken: -1), and who sits the call out
+    a.no_last = sl.lc.took.empty() ? nullptr : sl.h_no_last;
+    if (sl.lc.masked) {  // rt_set_present: each stream's own previous segment count (a reset taken: -1), and who sits the call out
         a.absent = sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams;
         a.n_seg_last_s = sl.d_mask + (size_t)kMaskNSegLast * h->cfg.n_streams;
     }
@@ -742,14 +723,14 @@ int enqueue_row_means(rt_handle *h, Slot &sl, int chunks, int n_seg, hipStream_t
     if (!sl.d_row_means) return RT_OK;
     const int64_t cells = (int64_t)h->cfg.n_streams * h->N;
     hipLaunchKernelGGL(row_means_from_partials, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, sl.d_psum, chunks, h->cfg.n_streams, h->N,
-                       n_seg, sl.d_row_means, sl.call.masked ? sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams : nullptr);
+                       n_seg, sl.d_row_means, sl.lc.masked ? sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams : nullptr);
     RT_HIP(h, hipGetLastError());
     return RT_OK;
 }
 
 // ---- rt_set_chain: the look-back a call's detection (and its cell gather) reads, and the copy that fills it ----
 // The slot's chained columns if the call is chained, else the rotation buffer the call reads.
-const float *call_prev(rt_handle *h, const Slot &sl) { return sl.call.chained ? sl.d_chain : h->d_tail[sl.call.tail_read]; }
+const float *call_prev(rt_handle *h, const Slot &sl) { return sl.lc.chained ? sl.d_chain : h->d_tail[sl.call.tail_read]; }
 
 // chain_tails for the call of `sl` on `st`: behind the scans of this analysis (they write the rotation buffer the copy reads for
 // every stream that follows one of the same call), in front of its detection.  Every analysis of the call runs it again: a
@@ -757,7 +738,7 @@ const float *call_prev(rt_handle *h, const Slot &sl) { return sl.call.chained ? 
 int enqueue_chain(rt_handle *h, Slot &sl, hipStream_t st) {
     const CallCtx &c = sl.call;
     const int64_t per = (int64_t)h->K * h->N;
-    if (!c.chained || per <= 0) return RT_OK;
+    if (!sl.lc.chained || per <= 0) return RT_OK;
     const int S = h->cfg.n_streams, bps = chain_blocks<float>(per);
     hipLaunchKernelGGL((chain_tails<float>), dim3((unsigned)((int64_t)S * bps)), dim3(kChainBlock), 0, st, sl.d_chain_rows, sl.d_chain_rows + S, S, bps,
                        h->d_tail[c.tail_write], h->d_tail[c.tail_read], sl.d_chain, per);
@@ -868,7 +849,7 @@ void launch_scan(rt_handle *h, const StftParams &sp, int blocks, int fmt, hipStr
 // The scans enqueued while one of these is alive take the slot's mask (launch_stft)
 struct MaskedLaunches {
     rt_handle *h;
-    MaskedLaunches(rt_handle *h_, const Slot &sl) : h(h_) { h->launch_mask = sl.call.masked ? &sl : nullptr; }
+    MaskedLaunches(rt_handle *h_, const Slot &sl) : h(h_) { h->launch_mask = sl.lc.masked ? &sl : nullptr; }
     ~MaskedLaunches() { h->launch_mask = nullptr; }
 };
 
@@ -893,7 +874,7 @@ void fill_mask_rows(const PresenceCall &pc, int S, const int32_t *sub_first, int
 // (again when the detrend guard's set has changed: fetch_one).  Nothing of the slot is in flight: the pinned rows may be rewritten.
 int upload_mask(rt_handle *h, Slot &sl) {
     const int S = h->cfg.n_streams;
-    fill_mask_rows(sl.pc, S, h->lin ? h->h_sub_first.data() : nullptr, sl.h_mask, &sl.n_lin_present, &sl.n_sub_present, &sl.n_absent);
+    fill_mask_rows(sl.lc.pc, S, h->lin ? h->h_sub_first.data() : nullptr, sl.h_mask, &sl.n_lin_present, &sl.n_sub_present, &sl.n_absent);
     RT_HIP(h, hipMemcpyAsync(sl.d_mask, sl.h_mask, (size_t)kMaskRows * S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
     return RT_OK;
 }
@@ -901,8 +882,8 @@ int upload_mask(rt_handle *h, Slot &sl) {
 // rt_set_chain: the call's source rows to the device (once per call: a re-analysis reads them again).  As upload_mask.
 int upload_chain_rows(rt_handle *h, Slot &sl) {
     const size_t S = (size_t)h->cfg.n_streams;
-    std::memcpy(sl.h_chain_rows, sl.cc.src_buf.data(), S * sizeof(int32_t));
-    std::memcpy(sl.h_chain_rows + S, sl.cc.src_idx.data(), S * sizeof(int32_t));
+    std::memcpy(sl.h_chain_rows, sl.lc.cc.src_buf.data(), S * sizeof(int32_t));
+    std::memcpy(sl.h_chain_rows + S, sl.lc.cc.src_idx.data(), S * sizeof(int32_t));
     RT_HIP(h, hipMemcpyAsync(sl.d_chain_rows, sl.h_chain_rows, 2 * S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
     return RT_OK;
 }
@@ -934,7 +915,7 @@ int enqueue_analysis(rt_handle *h, Slot &sl, int mode, bool *launched = nullptr,
     if (mode == RT_MODE_RUNFILTER && c.thr_rerun && !second_pass_only) own_means = true;
     if (launched) *launched = false;
     const MaskedLaunches masked_launches(h, sl);
-    const int32_t *const absent = c.masked ? sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams : nullptr;
+    const int32_t *const absent = sl.lc.masked ? sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams : nullptr;
     if (h->general) {
         // any other power-of-two nperseg: the general transform into the dense map, then the dense extractor (which sums the rows itself)
         int rc = ensure_dense_spec(h);
@@ -1296,7 +1277,7 @@ int iq_sample_bytes(const rt_handle *h, int fmt) { return (h->f64 && fmt == kFmt
 int iq_tail_area(rt_handle *h, int bps) {
     RecordIq &q = *h->riq;
     if (q.d_tails && bps <= q.area_bps) return RT_OK;
-    const int64_t row = ((int64_t)q.book.cols() * iq_nperseg(h) * bps + 15) / 16 * 16;
+    const int64_t row = ((int64_t)h->ledger.iq.cols() * iq_nperseg(h) * bps + 15) / 16 * 16;
     const size_t rows = (size_t)kIqRows * (size_t)h->cfg.n_streams;
     char *area = nullptr;
     if (hipMalloc(&area, std::max<size_t>(rows * (size_t)row, 16)) != hipSuccess) {
@@ -1321,22 +1302,28 @@ int iq_tail_area(rt_handle *h, int bps) {
     return RT_OK;
 }
 
-// At enqueue, in front of the scan: the book's decisions for the call that takes slot `idx` (its snapshot stays in the slot for its
-// fetch), the rows it writes to the device, iq_tails on the scan's stream.  `slot_done`: the event behind the slot's previous call
-// (null: it never held one) -- the pinned rows are rewritten.  A failure leaves the book as it was.
-int iq_begin(rt_handle *h, int idx, hipEvent_t slot_done, int T, int fmt, const void *iq, int64_t stream_stride, const int32_t *n_seg_last,
-             const uint8_t *absent, const int32_t *src_buf, const int32_t *src_idx, const IqCall *other) {
+// At enqueue, in front of the scan, on a float32 and a float64 handle alike: the ledger's decisions for the call that takes slot
+// `idx` go into `lc` (they stay in the slot for the call's fetch and every re-analysis), and with rt_set_record_iq on the rows the
+// call writes go to the device and iq_tails onto the scan's stream.  `other`: the other slot's snapshot while its call is pending,
+// else null.  `slot_done`: the event behind the slot's previous call (null: it never held one) -- the pinned rows are rewritten.
+// Everything that can fail comes before the ledger moves or puts it back: a failure leaves the ledger as it was.
+int begin_ledger_call(rt_handle *h, int idx, LedgerCall &lc, const LedgerCall *other, hipEvent_t slot_done, int T, int fmt, const void *iq,
+                      int64_t stream_stride) {
+    StreamLedger &led = h->ledger;
+    const int S = h->cfg.n_streams, N = iq_nperseg(h), bps = iq_sample_bytes(h, fmt);
+    if (led.iq.on()) {
+        const int rc = iq_tail_area(h, bps);
+        if (rc != RT_OK) return rc;
+        if (slot_done) RT_HIP(h, hipEventSynchronize(slot_done));
+    }
+    led.begin_call(T, fmt, other && other->iq_on ? &other->iq : nullptr, lc);
+    if (!lc.iq_on) return RT_OK;
     RecordIq &q = *h->riq;
     IqSlot &qs = q.slot[idx];
-    const int S = h->cfg.n_streams, N = iq_nperseg(h), bps = iq_sample_bytes(h, fmt);
-    const int rc = iq_tail_area(h, bps);
-    if (rc != RT_OK) return rc;
-    if (slot_done) RT_HIP(h, hipEventSynchronize(slot_done));
-    q.book.begin_call(T, fmt, n_seg_last, absent, src_buf, src_idx, other, qs.call);
-    const int D = std::min(T, q.book.cols());
+    const int D = std::min(T, led.iq.cols());
     bool any = false;
     for (int s = 0; s < S; ++s) {
-        qs.h_rows[s] = qs.call.write_buf[(size_t)s];
+        qs.h_rows[s] = lc.iq.write_buf[(size_t)s];
         any = any || qs.h_rows[s] >= 0;
     }
     if (D <= 0 || !any) return RT_OK;
@@ -1357,10 +1344,36 @@ int iq_begin(rt_handle *h, int idx, hipEvent_t slot_done, int T, int fmt, const 
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
-        q.book.rollback(qs.call);
-        qs.call.on = false;
+        led.rollback(lc);
         h->err = std::string("iq_tails: ") + hipGetErrorString(e);
         return RT_E_HIP;
+    }
+    return RT_OK;
+}
+
+// The argument check of rt_process* on a float32 and a float64 handle alike; *T = the call's whole segments.  `device_ptr`: the
+// scan kernel loads whole samples from `iq` (8-byte complex64 -- 16-byte complex128 on a float64 handle -- / 2-byte uint8 or int8
+// / 4-byte int16 I,Q pairs): a misaligned pointer would fault on the device, so it is refused here (a host buffer is staged).
+int check_process_args(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, int fmt, bool device_ptr, int *T) {
+    if (!iq && n_samples > 0) {
+        h->err = "null IQ pointer";
+        return RT_E_INVALID;
+    }
+    if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples) {
+        h->err = "n_samples/stream_stride out of range for this handle";
+        return RT_E_INVALID;
+    }
+    if (device_ptr && reinterpret_cast<uintptr_t>(iq) % (size_t)iq_sample_bytes(h, fmt) != 0) {
+        h->err = fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
+                 : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)"
+                 : fmt == kFmtI8 ? "IQ pointer must be 2-byte aligned (int8 I,Q pairs)"
+                 : h->f64 ? "IQ pointer must be 16-byte aligned (complex128 on a float64 handle)" : "IQ pointer must be 8-byte aligned (complex64)";
+        return RT_E_INVALID;
+    }
+    *T = (int)(n_samples / iq_nperseg(h));
+    if (*T == 1) {
+        h->err = "exactly one segment: the reference raises IndexError (times[1])";
+        return RT_E_ONE_SEGMENT;
     }
     return RT_OK;
 }
@@ -1368,24 +1381,24 @@ int iq_begin(rt_handle *h, int idx, hipEvent_t slot_done, int T, int fmt, const 
 // Inside rt_fetch*, behind the delivery of the call in slot `idx` in full: its records -> offsets, first segments and the copy
 // list; the pool grown to what they need; the gather, waited for (the call's IQ need not outlive the fetch).  What goes wrong is
 // kept for rt_fetch_record_iq to report: the fetch itself has delivered.
-void iq_gather(rt_handle *h, int idx, const void *rec, size_t rec_stride, size_t n, const void *iq, int64_t stream_stride) {
+void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_t rec_stride, size_t n, const void *iq, int64_t stream_stride) {
     RecordIq &q = *h->riq;
     IqSlot &qs = q.slot[idx];
-    const int S = h->cfg.n_streams, N = iq_nperseg(h), bps = iq_sample_bytes(h, qs.call.fmt);
+    const int S = h->cfg.n_streams, N = iq_nperseg(h), bps = iq_sample_bytes(h, call.fmt);
     q.delivered = idx;
     qs.state = RT_OK;
     qs.bps = bps;
     qs.offsets.assign(n + 1, 0);
     qs.first_seg.assign(n, 0);
     std::vector<IqDesc> descs;
-    const int64_t total = iq_build_descs(qs.call, N, rec, rec_stride, n, qs.offsets.data(), qs.first_seg.data(), &descs);
+    const int64_t total = iq_build_descs(call, N, rec, rec_stride, n, qs.offsets.data(), qs.first_seg.data(), &descs);
     if (descs.empty()) return;
     const auto fail = [&](int code, const std::string &why) {
         (void)hipGetLastError();
         qs.state = code;
         qs.why = why;
     };
-    if (!iq_descs_in_bounds(descs, S, (int64_t)qs.call.T * N, (int64_t)q.book.cols() * N, total) || !q.d_tails)
+    if (!iq_descs_in_bounds(descs, S, (int64_t)call.T * N, (int64_t)h->ledger.iq.cols() * N, total) || !q.d_tails)
         return fail(RT_E_HIP, "internal: a record's samples lie outside the buffers the handle holds");
     const size_t bytes = (size_t)total * (size_t)bps;
     if (qs.pool_bytes < bytes) {
@@ -1465,6 +1478,8 @@ int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
         if (sl.call.seq == 0 || hipEventSynchronize(sl.ev_done) == hipSuccess) (void)grow_cells(h, sl.d_cells, sl.cell_cap, h->cells_want);
     }
     *saved = sl.call;  // put back if the new call fails before it has launched anything
+    std::swap(sl.lc, h->lc_saved);  // (... with the ledger's snapshot of it: process_impl swaps it back)
+    sl.lc.clear();
     sl.call = CallCtx{};
     sl.call.seq = h->n_calls + 1;
     *out = &sl;
@@ -1472,23 +1487,13 @@ int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
 }
 
 // What the call in `sl` took from the handle's host bookkeeping when it was enqueued goes back (its enqueue failed: process_impl; a
-// later lane's did: rollback_newest): AUTO's probe counter, the slot of the chunk minima, the stream resets it consumed, and the
-// presence, chain and record-IQ books.
+// later lane's did: rollback_newest): AUTO's probe counter, the slot of the chunk minima, and all the ledger gave it -- the
+// rotation, the segment counts, the stream resets it consumed, the presence, chain and record-IQ books.
 void undo_call_books(rt_handle *h, Slot &sl) {
     const CallCtx &c = sl.call;
     h->ap.restore(c.prev_auto);
     h->minsum_slot = c.prev_minsum_slot;  // (the chunk minima of the dropped buffer must not set the next call's thresholds)
-    if (c.no_last) {
-        for (int s = 0; s < h->cfg.n_streams; ++s)
-            if (sl.h_no_last[s]) h->reset_pending[(size_t)s] = 1;
-        h->any_reset_pending = true;
-    }
-    if (c.masked) {
-        h->pres.rollback(sl.pc, h->reset_pending);
-        h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
-    }
-    if (c.chained) h->chain.rollback(sl.cc);
-    if (c.iq_on) h->riq->book.rollback(h->riq->slot[&sl - h->slot].call);  // (the held sample tails are the ones before the call)
+    h->ledger.rollback(sl.lc);
 }
 
 // Undo the newest enqueued call of a (lane-less) handle: wait for its kernels, forget it, and put the
@@ -1502,8 +1507,6 @@ void rollback_newest(rt_handle *h) {
     (void)hipEventSynchronize(best->ev_done);
     const CallCtx &c = best->call;
     if (!c.is_extract) {
-        h->tail_cur = c.prev_tail_cur;
-        h->n_seg_last = c.prev_n_seg_last;
         undo_call_books(h, *best);
         if (best->min_seq == c.seq) best->min_items = 0;  // (the dropped buffer's chunk minima must not stand in for the slot's older ones, which they have overwritten)
     }
@@ -1652,6 +1655,70 @@ static void build_stream_settings(const rt_config &cfg, int N, P cfg_snr, const 
         if (!next.empty()) next[(size_t)s] = is;
     }
     cur.swap(next);
+}
+
+// rt_set_stream_params[_f64] of one lane-less handle, on the power type P: `cfg_thr` = the handle's one threshold, `h_thr_s` / `d_thr_s` /
+// `d_cal_s` its per-stream arrays, `h_cal_s` (or null) the host copy of the calibration a chained handle checks.
+template <class P>
+static int set_stream_params_one(rt_handle *h, P cfg_thr, std::vector<P> &h_thr_s, std::vector<P> *h_cal_s, P *&d_thr_s, P *&d_cal_s, const P *threshold,
+                                 const P *calibration_db) {
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    // kernels in flight read the arrays: let them finish first (a configuration call, not on the hot path)
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    RT_HIP(h, hipStreamSynchronize(h->s_detect));
+    const int S = h->cfg.n_streams;
+    const size_t bytes = (size_t)S * sizeof(P);
+    auto put = [&](P *&dst, const P *src) -> int {
+        if (!src) {
+            if (dst) (void)hipFree(dst);
+            dst = nullptr;
+            return RT_OK;
+        }
+        if (!dst) RT_HIP(h, hipMalloc(&dst, bytes));
+        RT_HIP(h, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return RT_OK;
+    };
+    // A stream whose threshold changes starts without look-back: the reference fixes the threshold when a SignalAnalyzer is
+    // built (analyze.py:115), a new one needs a new analyzer (_spectrogram_last = None) -- and the sparse scans keep only
+    // those tail cells a walk with the threshold of their own call can reach (rt_kernels.h: sparse tail).
+    std::vector<uint8_t> changed((size_t)S, (uint8_t)0);
+    for (int s = 0; s < S; ++s) {
+        const P was = h_thr_s.empty() ? cfg_thr : h_thr_s[(size_t)s];
+        const P is = threshold ? threshold[s] : cfg_thr;
+        changed[(size_t)s] = !(was == is);
+    }
+    h->ledger.mark_changed(changed);
+    if (threshold) h_thr_s.assign(threshold, threshold + S); else h_thr_s.clear();
+    if (h_cal_s) {
+        if (calibration_db) h_cal_s->assign(calibration_db, calibration_db + S); else h_cal_s->clear();
+    }
+    const int rc = put(d_thr_s, threshold);
+    if (rc != RT_OK) return rc;
+    return put(d_cal_s, calibration_db);
+}
+
+// rt_set_stream_settings[_f64] of one lane-less handle, on the power type P: `h_set_s` / `d_set_s` its table, `cfg_snr` the handle's one value
+template <class P>
+static int set_stream_settings_one(rt_handle *h, P cfg_snr, std::vector<StreamSettingsT<P>> &h_set_s, StreamSettingsT<P> *&d_set_s, const P *snr,
+                                   const double *min_d, const double *max_d) {
+    RT_HIP(h, hipSetDevice(h->cfg.device));
+    // kernels in flight read the table: let them finish first (a configuration call, not on the hot path)
+    RT_HIP(h, hipStreamSynchronize(h->s_scan));
+    RT_HIP(h, hipStreamSynchronize(h->s_detect));
+    const size_t bytes = (size_t)h->cfg.n_streams * sizeof(StreamSettingsT<P>);
+    if ((snr || min_d || max_d) && !d_set_s) RT_HIP(h, hipMalloc(&d_set_s, bytes));
+    // A stream whose settings change starts without look-back, as after rt_reset_stream: in the reference they are fixed when the
+    // SignalAnalyzer is built (analyze.py:113-116), new ones mean a new analyzer (_spectrogram_last = None, analyze.py:128).
+    std::vector<uint8_t> changed;
+    build_stream_settings<P>(h->cfg, iq_nperseg(h), cfg_snr, snr, min_d, max_d, h_set_s, changed);
+    h->ledger.mark_changed(changed);
+    if (h_set_s.empty()) {
+        if (d_set_s) (void)hipFree(d_set_s);
+        d_set_s = nullptr;
+        return RT_OK;
+    }
+    RT_HIP(h, hipMemcpy(d_set_s, h_set_s.data(), bytes, hipMemcpyHostToDevice));
+    return RT_OK;
 }
 
 extern "C" {
@@ -1972,7 +2039,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     }
 
     const int S = cfg->n_streams, N = h->N, LG = h->LG;
-    h->reset_pending.assign((size_t)S, 0);
+    h->ledger.configure(S);
     if (general) {
         const int M = h->gen_m;
         const std::vector<cf> twg = transform_twiddles<cf, double>(M);
@@ -2127,20 +2194,8 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
 int rt_reset(rt_handle *h) {
     if (!h) return RT_E_INVALID;
     forget_row_means(h);
-    if (h->riq) h->riq->book.forget_all();  // (no look-back, no lead: the held sample tails go with it)
-    if (h->f64) {
-        h->f64->n_seg_last = -1;
-        if (h->f64->pres.active) h->f64->pres.forget_all();
-        std::fill(h->f64->reset_pending.begin(), h->f64->reset_pending.end(), (uint8_t)0);
-        h->f64->any_reset = false;
-        return RT_OK;
-    }
     for (rt_handle *k : h->kids) rt_reset(k);
-    h->n_seg_last = -1;
-    if (h->pres.active) h->pres.forget_all();
-    h->chain.forget_all();
-    std::fill(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)0);
-    h->any_reset_pending = false;
+    h->ledger.forget_all();  // (no look-back, no lead: the held sample tails go with it)
     return RT_OK;
 }
 
@@ -2150,18 +2205,12 @@ int rt_reset_stream(rt_handle *h, int32_t stream) {
         h->err = "stream index out of range";
         return RT_E_INVALID;
     }
-    if (h->f64) {
-        h->f64->reset_pending[(size_t)stream] = 1;
-        h->f64->any_reset = true;
-        return RT_OK;
-    }
     if (!h->kids.empty()) {
         for (size_t k = 0; k < h->kids.size(); ++k)
             if (stream < h->kid_base[k + 1]) return rt_reset_stream(h->kids[k], stream - h->kid_base[k]);
         return RT_E_INVALID;
     }
-    h->reset_pending[(size_t)stream] = 1;
-    h->any_reset_pending = true;
+    h->ledger.reset_stream(stream);
     return RT_OK;
 }
 
@@ -2182,63 +2231,8 @@ int rt_set_stream_params(rt_handle *h, const float *threshold, const float *cali
         h->err = "rt_set_stream_params with unfetched calls pending: fetch them first";
         return RT_E_INVALID;
     }
-    { const int rcu = chain_runs_uniform(h, h->chain, "rt_set_stream_params", threshold, calibration_db, nullptr, nullptr, nullptr); if (rcu != RT_OK) return rcu; }
-    RT_HIP(h, hipSetDevice(h->cfg.device));
-    // kernels in flight read the arrays: let them finish first (a configuration call, not on the hot path)
-    RT_HIP(h, hipStreamSynchronize(h->s_scan));
-    RT_HIP(h, hipStreamSynchronize(h->s_detect));
-    const size_t bytes = (size_t)h->cfg.n_streams * sizeof(float);
-    auto put = [&](float *&dst, const float *src) -> int {
-        if (!src) {
-            if (dst) (void)hipFree(dst);
-            dst = nullptr;
-            return RT_OK;
-        }
-        if (!dst) RT_HIP(h, hipMalloc(&dst, bytes));
-        RT_HIP(h, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-        return RT_OK;
-    };
-    // A stream whose threshold changes starts without look-back: the reference fixes the threshold when a SignalAnalyzer is
-    // built (analyze.py:115), a new one needs a new analyzer (_spectrogram_last = None) -- and the sparse scans keep only
-    // those tail cells a walk with the threshold of their own call can reach (rt_kernels.h: sparse tail).
-    for (int s = 0; s < h->cfg.n_streams; ++s) {
-        const float was = h->h_thr_s.empty() ? h->cfg.threshold : h->h_thr_s[(size_t)s];
-        const float is = threshold ? threshold[s] : h->cfg.threshold;
-        if (!(was == is)) {
-            h->reset_pending[(size_t)s] = 1;
-            h->any_reset_pending = true;
-        }
-    }
-    if (threshold) h->h_thr_s.assign(threshold, threshold + h->cfg.n_streams); else h->h_thr_s.clear();
-    if (calibration_db) h->h_cal_s.assign(calibration_db, calibration_db + h->cfg.n_streams); else h->h_cal_s.clear();
-    int rc = put(h->d_thr_s, threshold);
-    if (rc != RT_OK) return rc;
-    return put(h->d_cal_s, calibration_db);
-}
-
-static int set_stream_settings_lane(rt_handle *h, const float *snr, const double *min_d, const double *max_d) {
-    RT_HIP(h, hipSetDevice(h->cfg.device));
-    // kernels in flight read the table: let them finish first (a configuration call, not on the hot path)
-    RT_HIP(h, hipStreamSynchronize(h->s_scan));
-    RT_HIP(h, hipStreamSynchronize(h->s_detect));
-    const size_t bytes = (size_t)h->cfg.n_streams * sizeof(StreamSettings);
-    if ((snr || min_d || max_d) && !h->d_set_s) RT_HIP(h, hipMalloc(&h->d_set_s, bytes));
-    // A stream whose settings change starts without look-back, as after rt_reset_stream: in the reference they are fixed when the
-    // SignalAnalyzer is built (analyze.py:113-116), new ones mean a new analyzer (_spectrogram_last = None, analyze.py:128).
-    std::vector<uint8_t> changed;
-    build_stream_settings<float>(h->cfg, h->N, h->cfg.snr_threshold, snr, min_d, max_d, h->h_set_s, changed);
-    for (int s = 0; s < h->cfg.n_streams; ++s)
-        if (changed[(size_t)s]) {
-            h->reset_pending[(size_t)s] = 1;
-            h->any_reset_pending = true;
-        }
-    if (h->h_set_s.empty()) {
-        if (h->d_set_s) (void)hipFree(h->d_set_s);
-        h->d_set_s = nullptr;
-        return RT_OK;
-    }
-    RT_HIP(h, hipMemcpy(h->d_set_s, h->h_set_s.data(), bytes, hipMemcpyHostToDevice));
-    return RT_OK;
+    { const int rcu = chain_runs_uniform(h, h->ledger.chain, "rt_set_stream_params", threshold, calibration_db, nullptr, nullptr, nullptr); if (rcu != RT_OK) return rcu; }
+    return set_stream_params_one<float>(h, h->cfg.threshold, h->h_thr_s, &h->h_cal_s, h->d_thr_s, h->d_cal_s, threshold, calibration_db);
 }
 
 int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const double *min_duration_s, const double *max_duration_s) {
@@ -2248,7 +2242,7 @@ int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const doubl
     // stream as the caller counts it -- the lanes share rt_config's envelope), then the pending calls
     const int rc = check_stream_settings<float>(h, "rt_set_stream_settings", snr_threshold, min_duration_s, max_duration_s);
     if (rc != RT_OK) return rc;
-    { const int rcu = chain_runs_uniform(h, h->chain, "rt_set_stream_settings", nullptr, nullptr, snr_threshold, min_duration_s, max_duration_s); if (rcu != RT_OK) return rcu; }
+    { const int rcu = chain_runs_uniform(h, h->ledger.chain, "rt_set_stream_settings", nullptr, nullptr, snr_threshold, min_duration_s, max_duration_s); if (rcu != RT_OK) return rcu; }
     bool pending = h->kids.empty() && oldest_pending(h);
     for (rt_handle *k : h->kids) pending = pending || oldest_pending(k);
     if (pending) {
@@ -2258,10 +2252,10 @@ int rt_set_stream_settings(rt_handle *h, const float *snr_threshold, const doubl
     }
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) {
-            return set_stream_settings_lane(k, snr_threshold ? snr_threshold + s0 : nullptr, min_duration_s ? min_duration_s + s0 : nullptr,
-                                            max_duration_s ? max_duration_s + s0 : nullptr);
+            return set_stream_settings_one<float>(k, k->cfg.snr_threshold, k->h_set_s, k->d_set_s, snr_threshold ? snr_threshold + s0 : nullptr,
+                                                  min_duration_s ? min_duration_s + s0 : nullptr, max_duration_s ? max_duration_s + s0 : nullptr);
         });
-    return set_stream_settings_lane(h, snr_threshold, min_duration_s, max_duration_s);
+    return set_stream_settings_one<float>(h, h->cfg.snr_threshold, h->h_set_s, h->d_set_s, snr_threshold, min_duration_s, max_duration_s);
 }
 
 // rt_set_present (include/rt_analyze.h).  The first call on a handle allocates the two call slots' mask rows and moves the handle
@@ -2272,8 +2266,7 @@ int rt_set_present(rt_handle *h, const uint8_t *present) {
     if (!h->kids.empty())
         return for_each_lane(h, [&](rt_handle *k, int64_t s0) { return rt_set_present(k, present ? present + s0 : nullptr); });
     const int S = h->cfg.n_streams;
-    PresenceBook &book = h->f64 ? h->f64->pres : h->pres;
-    if (!book.active) {
+    if (!h->ledger.pres.active) {
         RT_HIP(h, hipSetDevice(h->cfg.device));
         const size_t bytes = (size_t)kMaskRows * (size_t)S * sizeof(int32_t);
         int32_t *hm[kSlots] = {nullptr, nullptr}, *dm[kSlots] = {nullptr, nullptr};
@@ -2304,9 +2297,9 @@ int rt_set_present(rt_handle *h, const uint8_t *present) {
         if (!h->f64)
             for (int i = 0; i < kSlots; ++i)
                 if (h->slot[i].d_chunk_min && h->chunk_min_bytes) RT_HIP(h, hipMemsetAsync(h->slot[i].d_chunk_min, 0x7f, h->chunk_min_bytes, h->s_scan));
-        book.activate(S, h->f64 ? h->f64->n_seg_last : h->n_seg_last);
+        h->ledger.activate_presence();
     }
-    book.set_mask(present);
+    h->ledger.set_mask(present);
     return RT_OK;
 }
 
@@ -2337,7 +2330,7 @@ int rt_set_chain(rt_handle *h, int32_t links) {
         h->err = "rt_set_chain with unfetched calls pending: fetch them first";
         return RT_E_INVALID;
     }
-    if (want == h->chain.links) return RT_OK;
+    if (want == h->ledger.chain.links) return RT_OK;
     if (want) {
         ChainBook next;
         next.configure(S, want);
@@ -2376,13 +2369,14 @@ int rt_set_chain(rt_handle *h, int32_t links) {
                 h->slot[i].d_chain = dc[i];
             }
         }
-        if (!h->pres.active) {
+        if (!h->ledger.pres.active) {
             const int rcp = rt_set_present(h, nullptr);  // (every stream present: the mask rows exist from here on)
             if (rcp != RT_OK) return rcp;
         }
     }
-    h->chain.configure(S, want);
-    return rt_reset(h);  // a change of the grouping forgets all look-back
+    forget_row_means(h);
+    h->ledger.set_chain(want);  // (a change of the grouping forgets all look-back, as rt_reset does)
+    return RT_OK;
 }
 
 static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int64_t stream_stride, int fmt);
@@ -2416,36 +2410,17 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             return process_impl(k, base, n_samples, stream_stride, fmt);
         }, true);
     }
-    if (!iq_dev && n_samples > 0) {
-        h->err = "null IQ pointer";
-        return RT_E_INVALID;
-    }
-    if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples) {
-        h->err = "n_samples/stream_stride out of range for this handle";
-        return RT_E_INVALID;
-    }
-    // the scan kernel loads whole samples (8-byte complex64 / 2-byte uint8 or int8 / 4-byte int16 I,Q pairs): a misaligned pointer
-    // would fault on the device, so it is refused here
-    if (reinterpret_cast<uintptr_t>(iq_dev) % fmt_sample_bytes(fmt) != 0) {
-        h->err = fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
-                 : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)"
-                 : fmt == kFmtI8 ? "IQ pointer must be 2-byte aligned (int8 I,Q pairs)" : "IQ pointer must be 8-byte aligned (complex64)";
-        return RT_E_INVALID;
-    }
+    int T = 0;
+    int rc = check_process_args(h, iq_dev, n_samples, stream_stride, fmt, true, &T);
+    if (rc != RT_OK) return rc;
     RT_HIP(h, hipSetDevice(h->cfg.device));
-    const int T = (int)(n_samples / h->N);
-    if (T == 1) {
-        h->err = "exactly one segment: the reference raises IndexError (times[1])";
-        return RT_E_ONE_SEGMENT;
-    }
     Slot *slp = nullptr;
     CallCtx saved;
-    int rc = claim_slot(h, &slp, &saved);
+    rc = claim_slot(h, &slp, &saved);
     if (rc != RT_OK) return rc;
     Slot &sl = *slp;
     CallCtx &c = sl.call;
-    c.prev_tail_cur = h->tail_cur;
-    c.prev_n_seg_last = h->n_seg_last;
+    LedgerCall &lc = sl.lc;
     c.prev_auto = h->ap.restore_point();
     c.prev_minsum_slot = h->minsum_slot;
     c.iq = iq_dev;
@@ -2453,66 +2428,38 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     c.n_samples = n_samples;
     c.stream_stride = stream_stride;
     c.n_seg = T;
-    c.tail_read = h->tail_cur;
-    c.tail_write = (h->tail_cur + 1) % kTails;
-    c.n_seg_last = h->n_seg_last;
     // Everything that can fail from here on runs inside `enqueue`; one block below undoes a failed call: nothing stays
-    // enqueued, the look-back state and the pending stream resets are the ones before the call, and the call the slot
+    // enqueued, the ledger (look-back state, pending stream resets, books) is the one before the call, and the call the slot
     // held (possibly still unfetched) is put back unless a launch has already rewritten its scratch (include/rt_analyze.h).
     bool launched = false;
     auto enqueue = [&]() -> int {
-        if (h->pres.active) {
-            // rt_set_present: the call keeps the mask in force, every stream's own previous segment count and the resets it takes in
-            // its slot (absent streams keep theirs pending), and carries the absent streams' look-back columns along the rotation.
-            // (The slot's previous call -- two calls back -- may still be reading the rows if it was never fetched.)
-            if (sl.ev_done && h->n_calls >= (uint64_t)kSlots) RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            launched = true;  // (the slot's snapshot is rewritten from here on)
-            h->pres.begin_call(T, h->tail_cur, h->reset_pending, sl.pc);
-            c.masked = true;
-            h->any_reset_pending = std::find(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)1) != h->reset_pending.end();
-            int rcm = RT_OK;
-            if (h->chain.on()) {
-                // rt_set_chain: who follows whom (the snapshot's n_seg_last row becomes the count of the buffer each stream follows)
-                h->chain.begin_call(T, sl.pc, sl.cc);
-                c.chained = true;
-                rcm = upload_chain_rows(h, sl);
-            }
+        const int S = h->cfg.n_streams, idx = (int)(&sl - h->slot);
+        const Slot &o = h->slot[1 - idx];
+        // the ledger's decisions for this call, and with rt_set_record_iq on the tails of its samples in front of its scan
+        const int rcl = begin_ledger_call(h, idx, lc, o.call.pending ? &o.lc : nullptr, saved.seq ? sl.ev_done : nullptr, T, fmt, iq_dev, stream_stride);
+        if (rcl != RT_OK) return rcl;
+        c.tail_read = lc.tail_read;
+        c.tail_write = lc.tail_write;
+        c.n_seg_last = lc.n_seg_last;
+        // (the slot's pinned rows are rewritten from here on: its previous call -- two calls back -- may still be reading them if it
+        // was never fetched)
+        if ((lc.masked || !lc.took.empty()) && sl.ev_done && h->n_calls >= (uint64_t)kSlots) RT_HIP(h, hipEventSynchronize(sl.ev_done));
+        if (lc.masked || lc.iq_on) launched = true;
+        if (lc.masked) {
+            // rt_set_present: the mask in force, every stream's own previous segment count and the resets it takes go to the device, and
+            // the absent streams' look-back columns are carried along the rotation; rt_set_chain: who follows whom
+            int rcm = lc.chained ? upload_chain_rows(h, sl) : RT_OK;
             if (rcm == RT_OK) rcm = upload_mask(h, sl);
             if (rcm == RT_OK)
-                rcm = enqueue_carry<float>(h, sl.d_mask + (size_t)kMaskAbsentList * h->cfg.n_streams, sl.n_absent, h->d_tail[c.tail_read], h->d_tail[c.tail_write],
-                                           h->K, h->N);
+                rcm = enqueue_carry<float>(h, sl.d_mask + (size_t)kMaskAbsentList * S, sl.n_absent, h->d_tail[c.tail_read], h->d_tail[c.tail_write], h->K, h->N);
             if (rcm != RT_OK) return rcm;
-        } else if (h->any_reset_pending) {
-            // the slot's previous call (two calls back) may still be reading its flags if it was never fetched
-            if (sl.ev_done && h->n_calls >= (uint64_t)kSlots) RT_HIP(h, hipEventSynchronize(sl.ev_done));
-            for (int s = 0; s < h->cfg.n_streams; ++s) sl.h_no_last[s] = h->reset_pending[(size_t)s];
-            std::fill(h->reset_pending.begin(), h->reset_pending.end(), (uint8_t)0);
-            h->any_reset_pending = false;
-            c.no_last = true;
-        }
-        if (h->riq && h->riq->book.on()) {
-            // rt_set_record_iq: the tails of this call's samples, in front of its scan; who each stream's detection looks back into
-            // is what the rows above say (per stream), or the handle's one count less the resets this call takes
-            const int S = h->cfg.n_streams, idx = (int)(&sl - h->slot);
-            const Slot &o = h->slot[1 - idx];
-            std::vector<int32_t> last;
-            if (!c.masked) {
-                last.assign((size_t)S, (int32_t)c.n_seg_last);
-                if (c.no_last)
-                    for (int s = 0; s < S; ++s)
-                        if (sl.h_no_last[s]) last[(size_t)s] = -1;
-            }
-            launched = true;  // (the slot's snapshot is rewritten from here on)
-            const int rcq = iq_begin(h, idx, saved.seq ? sl.ev_done : nullptr, T, fmt, iq_dev, stream_stride, c.masked ? sl.pc.n_seg_last.data() : last.data(),
-                                     c.masked ? sl.pc.absent.data() : nullptr, c.chained ? sl.cc.src_buf.data() : nullptr,
-                                     c.chained ? sl.cc.src_idx.data() : nullptr, o.call.pending && o.call.iq_on ? &h->riq->slot[1 - idx].call : nullptr);
-            if (rcq != RT_OK) return rcq;
-            c.iq_on = true;
+        } else if (!lc.took.empty()) {
+            std::memcpy(sl.h_no_last, lc.took.data(), (size_t)S * sizeof(int32_t));  // (lock-step: the streams that take a reset)
         }
         c.mode_used = h->ap.begin_call(h->cfg.mode, (uint64_t)kBuckets * (uint64_t)h->hot_cap, (uint64_t)T * (uint64_t)h->N);
         if (T == 0) {
             // empty spectrogram: no signals; `_spectrogram_last` becomes an empty map
-            const size_t sb = (size_t)h->cfg.n_streams * sizeof(int32_t);
+            const size_t sb = (size_t)S * sizeof(int32_t);
             launched = true;  // (the slot's result arrays are rewritten from here on)
             RT_HIP(h, hipMemsetAsync(sl.d_counters, 0, kCounterWords * sizeof(unsigned long long), h->s_scan));
             RT_HIP(h, hipMemsetAsync(sl.h_rec_count, 0, sb, h->s_scan));
@@ -2535,13 +2482,12 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
             sl.call = CallCtx{};
         } else {
             sl.call = saved;
+            std::swap(sl.lc, h->lc_saved);
         }
         return rc;
     }
     c.pending = true;
     h->n_calls++;
-    h->tail_cur = c.tail_write;
-    h->n_seg_last = T;
     return RT_OK;
 }
 
@@ -2705,7 +2651,7 @@ static int rerun(rt_handle *h, Slot &sl, int mode, unsigned long long &flags, un
         sl.call.n_dense_streams = 0;
     }
     int rc = before_rerun(h, sl);
-    if (rc == RT_OK && (how & kRerunMask) && sl.call.masked) rc = upload_mask(h, sl);
+    if (rc == RT_OK && (how & kRerunMask) && sl.lc.masked) rc = upload_mask(h, sl);
     if (rc == RT_OK) rc = enqueue_analysis(h, sl, mode, nullptr, (how & kRerunSecondPassOnly) != 0, (how & kRerunOwnMeans) != 0);
     if (rc != RT_OK || (how & kRerunNoWait)) return rc;
     return await_call(h, sl, flags);
@@ -2755,8 +2701,8 @@ static int guard_detrend(rt_handle *h, Slot &sl, unsigned long long &flags) {
                 for (int s = 0; s < h->cfg.n_streams; ++s) o.h_overflow[s] = o.h_incons[s] = o.h_dc_flag[s] = 0;
                 // (its absent streams' look-back columns again as well: the re-run in front of it has rewritten the marked streams' columns
                 // in the buffer they were carried from)
-                if (o.call.masked) rc = upload_mask(h, o);
-                if (rc == RT_OK && o.call.masked)
+                if (o.lc.masked) rc = upload_mask(h, o);
+                if (rc == RT_OK && o.lc.masked)
                     rc = enqueue_carry<float>(h, o.d_mask + (size_t)kMaskAbsentList * h->cfg.n_streams, o.n_absent, h->d_tail[o.call.tail_read],
                                               h->d_tail[o.call.tail_write], h->K, h->N);
                 if (rc != RT_OK) return rc;
@@ -2902,7 +2848,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
     // one wave per stream in the next calls' sparse detection while a stream holds half of what such a wave takes on average (heavier
     // batches -- BASELINE config 4: 1 500 cells per stream -- are faster with the per-list waves: most of their streams would be left to them anyway)
     // (a call with a presence mask: the streams that took part -- an absent one adds nothing to either side of these ratios)
-    const int64_t n_took_part = c.masked ? sl.pc.n_present : h->cfg.n_streams;
+    const int64_t n_took_part = sl.lc.masked ? sl.lc.pc.n_present : h->cfg.n_streams;
     if (c.mode_used != RT_MODE_DENSE && !c.is_extract && c.n_seg > 0) h->group_light = h->info.n_hot * 2 <= (int64_t)kGroupCells * n_took_part;
     h->ap.settle(c.level_settled, h->cfg.mode, c.mode_used, c.fell_back, !c.is_extract && c.n_seg > 0, h->info.n_hot, sl.h_seg_total ? (int64_t)*sl.h_seg_total : -1,
                  n_took_part, c.n_seg, h->N);
@@ -2950,7 +2896,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
             RecordIq &q = *h->riq;
             if (c.is_extract) {
                 q.delivered = kIqExtract;
-            } else if (!c.iq_on) {
+            } else if (!sl.lc.iq_on) {
                 q.delivered = kIqOff;
             } else if (!h->cells_full) {
                 q.delivered = kIqTruncated;
@@ -2961,7 +2907,7 @@ static int fetch_one(rt_handle *h, rt_record *out, size_t cap, size_t *n_out, bo
                     const rt_record *r = sl.h_records + sl.h_rec_offset[s];
                     for (int i = 0; i < sl.h_rec_count[s]; ++i) keys.insert(keys.end(), {(int32_t)s, r[i].fi, r[i].start, r[i].end});
                 }
-                iq_gather(h, (int)(&sl - h->slot), keys.data(), 4 * sizeof(int32_t), total, c.iq, c.stream_stride);
+                iq_gather(h, (int)(&sl - h->slot), sl.lc.iq, keys.data(), 4 * sizeof(int32_t), total, c.iq, c.stream_stride);
             }
         }
     }
@@ -3274,10 +3220,8 @@ static int set_record_iq_one(rt_handle *h, int32_t m) {
     const int S = h->cfg.n_streams, K = h->f64 ? h->f64->K : h->K;
     h->iq_margin = m < 0 ? -1 : m;
     if (m < 0) {
-        if (h->riq) {
-            h->riq->book.configure(S, K, -1);
-            h->riq->delivered = kIqNone;
-        }
+        h->ledger.set_iq_margin(K, -1);
+        if (h->riq) h->riq->delivered = kIqNone;
         return RT_OK;
     }
     RT_HIP(h, hipSetDevice(h->cfg.device));
@@ -3294,15 +3238,15 @@ static int set_record_iq_one(rt_handle *h, int32_t m) {
             h->err = "rt_set_record_iq: no memory for the rows of the sample tails";
             return RT_E_NOMEM;
         }
-        h->riq->book.configure(S, K, m);
-    } else if (h->riq->book.margin != m) {
+        h->ledger.set_iq_margin(K, m);
+    } else if (h->ledger.iq.margin != m) {
         // another margin is another row length: the area is made again by the next rt_process*, the held tails are forgotten
         RT_HIP(h, hipStreamSynchronize(h->s_scan));
         (void)hipFree(h->riq->d_tails);
         h->riq->d_tails = nullptr;
         h->riq->row_bytes = 0;
         h->riq->area_bps = 0;
-        h->riq->book.configure(S, K, m);
+        h->ledger.set_iq_margin(K, m);
     }
     h->riq->delivered = kIqNone;
     return RT_OK;
@@ -3497,8 +3441,8 @@ F64DetectArgs f64_detect_args(rt_handle *h, F64Slot &sl) {
         a.prev_cols = f->K;
         a.dp.n_seg_last = sl.n_seg_last;
         a.dp.tail_cols = sl.n_seg_last < 0 ? 0 : std::min(f->K, sl.n_seg_last);
-        a.no_last = sl.no_last ? sl.d_no_last : nullptr;
-        if (sl.masked) {  // rt_set_present: each stream's own previous segment count, and who sits the call out
+        a.no_last = sl.lc.took.empty() ? nullptr : sl.d_no_last;
+        if (sl.lc.masked) {  // rt_set_present: each stream's own previous segment count, and who sits the call out
             a.absent = sl.d_mask + (size_t)kMaskAbsent * h->cfg.n_streams;
             a.n_seg_last_s = sl.d_mask + (size_t)kMaskNSegLast * h->cfg.n_streams;
             a.tail_k = f->K;
@@ -3552,7 +3496,7 @@ int f64_enqueue_sparse(rt_handle *h, F64Slot &sl) {
         p.window = f->d_window;
         p.tw = f->d_tw;
         p.tail = f->d_tail[sl.tail_write];
-        p.absent = sl.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr;
+        p.absent = sl.lc.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr;
         p.partial = f->d_partial;
         p.keys = sl.d_keys;
         p.vals = sl.d_vals;
@@ -3722,7 +3666,7 @@ int f64_enqueue(rt_handle *h, F64Slot &sl) {
         p.tw = f->d_tw;
         p.spec = f->d_map;
         p.tail = f->d_tail[sl.tail_write];
-        p.absent = sl.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr;
+        p.absent = sl.lc.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr;
         const int64_t grid = (int64_t)S * ((sl.n_seg + f->SPB - 1) / f->SPB);
         const size_t lds = (size_t)f->SPB * f->M * sizeof(cd);
         if (sl.fmt == kFmtU8) {
@@ -3841,31 +3785,22 @@ static void destroy_f64(rt_handle *h) {
 
 static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t stream_stride, int fmt, bool host) {
     F64State *f = h->f64;
-    if (!iq && n_samples > 0) return f64_err(h, RT_E_INVALID, "null IQ pointer");
-    if (n_samples < 0 || n_samples > h->cfg.max_samples || stream_stride < n_samples)
-        return f64_err(h, RT_E_INVALID, "n_samples/stream_stride out of range for this handle");
-    const size_t sample_bytes = fmt == kFmtC64 ? 16u : fmt_sample_bytes(fmt);  // (complex128 on a float64 handle)
-    if (!host && reinterpret_cast<uintptr_t>(iq) % sample_bytes != 0)
-        return f64_err(h, RT_E_INVALID, fmt == kFmtU8 ? "IQ pointer must be 2-byte aligned (uint8 I,Q pairs)"
-                                        : fmt == kFmtI16 ? "IQ pointer must be 4-byte aligned (int16 I,Q pairs)"
-                                        : fmt == kFmtI8  ? "IQ pointer must be 2-byte aligned (int8 I,Q pairs)"
-                                                         : "IQ pointer must be 16-byte aligned (complex128 on a float64 handle)");
-    const int T = (int)(n_samples / f->N);
-    if (T == 1) return f64_err(h, RT_E_ONE_SEGMENT, "exactly one segment: the reference raises IndexError (times[1])");
+    int T = 0;
+    int rc = check_process_args(h, iq, n_samples, stream_stride, fmt, !host, &T);
+    if (rc != RT_OK) return rc;
     RT_HIP(h, hipSetDevice(h->cfg.device));
     const int S = h->cfg.n_streams;
     F64Slot &sl = f64_claim(f);
+    LedgerCall &lc = sl.lc;
     sl.pending = false;
     sl.is_extract = false;
     sl.fmt = fmt;
     sl.stream_stride = stream_stride;
     sl.n_seg = T;
-    sl.n_seg_last = f->n_seg_last;
-    sl.tail_read = f->tail_cur;
-    sl.tail_write = (f->tail_cur + 1) % kTails;
     sl.iq = iq;
+    lc.clear();
     if (host && n_samples > 0) {
-        const size_t bytes = (size_t)S * (size_t)stream_stride * sample_bytes;
+        const size_t bytes = (size_t)S * (size_t)stream_stride * (size_t)iq_sample_bytes(h, fmt);
         if (sl.stage_bytes < bytes) {
             RT_HIP(h, hipStreamSynchronize(h->s_scan));  // (the slot's last call may still read its staging buffer)
             (void)hipFree(sl.d_stage);
@@ -3881,79 +3816,35 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
         RT_HIP(h, hipStreamSynchronize(h->s_scan));  // (blocking: the caller may reuse its buffer when this returns)
         sl.iq = sl.d_stage;
     }
-    sl.masked = f->pres.active;
-    sl.iq_on = false;
-    // rt_set_record_iq: as on a float32 handle (process_impl) -- the tails of this call's samples in front of its scan
-    const auto iq_tails_of_call = [&]() -> int {
-        if (!h->riq || !h->riq->book.on()) return RT_OK;
-        const int idx = (int)(&sl - f->slot);
-        const F64Slot &o = f->slot[1 - idx];
-        std::vector<int32_t> last;
-        if (!sl.masked) {
-            last.assign((size_t)S, (int32_t)sl.n_seg_last);
-            if (f->any_reset)
-                for (int s = 0; s < S; ++s)
-                    if (f->reset_pending[(size_t)s]) last[(size_t)s] = -1;
-        }
-        const int rcq = iq_begin(h, idx, sl.seq ? sl.ev_done : nullptr, T, fmt, sl.iq, stream_stride, sl.masked ? sl.pc.n_seg_last.data() : last.data(),
-                                 sl.masked ? sl.pc.absent.data() : nullptr, nullptr, nullptr, o.pending && o.iq_on ? &h->riq->slot[1 - idx].call : nullptr);
-        sl.iq_on = rcq == RT_OK;
-        return rcq;
-    };
-    const auto iq_undo = [&]() {
-        if (sl.iq_on) h->riq->book.rollback(h->riq->slot[&sl - f->slot].call);
-        sl.iq_on = false;
-    };
-    const auto any_pending = [&]() { return std::find(f->reset_pending.begin(), f->reset_pending.end(), (uint8_t)1) != f->reset_pending.end(); };
-    if (sl.masked) {
-        // rt_set_present: as on a float32 handle (process_impl) -- the snapshot into the slot, the rows to the device, the absent
-        // streams' look-back columns carried from the buffer the call reads to the one it writes
-        int n_sub = 0, n_lin = 0;
-        f->pres.begin_call(T, f->tail_cur, f->reset_pending, sl.pc);
-        f->any_reset = any_pending();
-        sl.no_last = false;
-        fill_mask_rows(sl.pc, S, nullptr, sl.h_mask, &n_lin, &n_sub, &sl.n_absent);
-        int rcm = RT_OK;
-        const auto upload = [&]() -> int {
+    const int idx = (int)(&sl - f->slot);
+    const F64Slot &o = f->slot[1 - idx];
+    rc = begin_ledger_call(h, idx, lc, o.pending ? &o.lc : nullptr, sl.seq ? sl.ev_done : nullptr, T, fmt, sl.iq, stream_stride);
+    if (rc != RT_OK) return rc;
+    sl.n_seg_last = lc.n_seg_last;
+    sl.tail_read = lc.tail_read;
+    sl.tail_write = lc.tail_write;
+    // The call's rows to the device.  (Blocking: a float64 handle picks any free slot for a call, so no event of the slot's says when
+    // a copy has left the host rows.  The float32 path waits for its slot's ev_done.)
+    const auto upload = [&]() -> int {
+        if (lc.masked) {
+            // rt_set_present: the snapshot's rows, and the absent streams' look-back columns carried from the buffer the call reads
+            // to the one it writes
+            int n_sub = 0, n_lin = 0;
+            fill_mask_rows(lc.pc, S, nullptr, sl.h_mask, &n_lin, &n_sub, &sl.n_absent);
             RT_HIP(h, hipMemcpyAsync(sl.d_mask, sl.h_mask, (size_t)kMaskRows * S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
-            // (Blocking, like the upload of a pending reset's flags just below: a float64 handle picks any free slot for a call, so
-            // no event of the slot's says when the copy has left the pinned rows.  The float32 path waits for its slot's ev_done.)
             RT_HIP(h, hipStreamSynchronize(h->s_scan));
             return enqueue_carry<double>(h, sl.d_mask + (size_t)kMaskAbsentList * S, sl.n_absent, f->d_tail[sl.tail_read], f->d_tail[sl.tail_write], f->K, f->N);
-        };
-        rcm = upload();
-        if (rcm == RT_OK) rcm = iq_tails_of_call();
-        if (rcm == RT_OK) rcm = f64_start(h, sl);
-        if (rcm != RT_OK) {
-            iq_undo();
-            f->pres.rollback(sl.pc, f->reset_pending);
-            f->any_reset = any_pending();
-            sl.masked = false;
-            return rcm;
         }
-        f->tail_cur = sl.tail_write;
-        f->n_seg_last = T;
+        if (!lc.took.empty()) {  // lock-step: the streams that take a reset
+            RT_HIP(h, hipMemcpyAsync(sl.d_no_last, lc.took.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
+            RT_HIP(h, hipStreamSynchronize(h->s_scan));
+        }
         return RT_OK;
-    }
-    sl.no_last = f->any_reset;
-    if (f->any_reset) {
-        sl.no_last_h.assign(f->reset_pending.begin(), f->reset_pending.end());
-        RT_HIP(h, hipMemcpyAsync(sl.d_no_last, sl.no_last_h.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, h->s_scan));
-        RT_HIP(h, hipStreamSynchronize(h->s_scan));
-    }
-    int rc = iq_tails_of_call();
+    };
+    rc = upload();
     if (rc == RT_OK) rc = f64_start(h, sl);
-    if (rc != RT_OK) {
-        iq_undo();
-        return rc;
-    }
-    if (f->any_reset) {
-        std::fill(f->reset_pending.begin(), f->reset_pending.end(), (uint8_t)0);
-        f->any_reset = false;
-    }
-    f->tail_cur = sl.tail_write;
-    f->n_seg_last = T;
-    return RT_OK;
+    if (rc != RT_OK) h->ledger.rollback(lc);
+    return rc;
 }
 
 extern "C" {
@@ -4020,7 +3911,7 @@ int rt_create_f64(const rt_config *cfg, const rt_config_f64 *f64, rt_handle **ou
     f->K = tail_cols(n, cfg->sample_rate, cfg->max_duration_s);
     f->max_seg = (int)(cfg->max_samples / n);
     f->rec_cap = cfg->record_capacity > 0 ? cfg->record_capacity : 1024;
-    f->reset_pending.assign((size_t)cfg->n_streams, 0);
+    h->ledger.configure(cfg->n_streams);
     const size_t S = (size_t)cfg->n_streams;
     if (sparse) {
         f->sparse = true;
@@ -4127,33 +4018,7 @@ int rt_set_stream_params_f64(rt_handle *h, const double *threshold, const double
     }
     F64State *f = h->f64;
     if (f64_oldest(f)) return f64_err(h, RT_E_INVALID, "rt_set_stream_params_f64 with unfetched calls pending: fetch them first");
-    RT_HIP(h, hipSetDevice(h->cfg.device));
-    RT_HIP(h, hipStreamSynchronize(h->s_scan));
-    const int S = h->cfg.n_streams;
-    const size_t bytes = (size_t)S * sizeof(double);
-    auto put = [&](double *&dst, const double *src) -> int {
-        if (!src) {
-            if (dst) (void)hipFree(dst);
-            dst = nullptr;
-            return RT_OK;
-        }
-        if (!dst) RT_HIP(h, hipMalloc(&dst, bytes));
-        RT_HIP(h, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-        return RT_OK;
-    };
-    // a stream whose threshold changes starts without look-back (a new analyzer in the reference, analyze.py:115)
-    for (int s = 0; s < S; ++s) {
-        const double was = f->h_thr_s.empty() ? f->c.threshold : f->h_thr_s[(size_t)s];
-        const double is = threshold ? threshold[s] : f->c.threshold;
-        if (!(was == is)) {
-            f->reset_pending[(size_t)s] = 1;
-            f->any_reset = true;
-        }
-    }
-    if (threshold) f->h_thr_s.assign(threshold, threshold + S); else f->h_thr_s.clear();
-    const int rc = put(f->d_thr_s, threshold);
-    if (rc != RT_OK) return rc;
-    return put(f->d_cal_s, calibration_db);
+    return set_stream_params_one<double>(h, f->c.threshold, f->h_thr_s, nullptr, f->d_thr_s, f->d_cal_s, threshold, calibration_db);
 }
 
 int rt_set_stream_settings_f64(rt_handle *h, const double *snr_threshold, const double *min_duration_s, const double *max_duration_s) {
@@ -4166,26 +4031,7 @@ int rt_set_stream_settings_f64(rt_handle *h, const double *snr_threshold, const 
     const int rc = check_stream_settings<double>(h, "rt_set_stream_settings_f64", snr_threshold, min_duration_s, max_duration_s);
     if (rc != RT_OK) return rc;
     if (f64_oldest(f)) return f64_err(h, RT_E_INVALID, "rt_set_stream_settings_f64 with unfetched calls pending: fetch them first");
-    RT_HIP(h, hipSetDevice(h->cfg.device));
-    RT_HIP(h, hipStreamSynchronize(h->s_scan));
-    const int S = h->cfg.n_streams;
-    const size_t bytes = (size_t)S * sizeof(StreamSettings64);
-    if ((snr_threshold || min_duration_s || max_duration_s) && !f->d_set_s) RT_HIP(h, hipMalloc(&f->d_set_s, bytes));
-    // a stream whose settings change starts without look-back (a new analyzer in the reference, analyze.py:113-116, 128)
-    std::vector<uint8_t> changed;
-    build_stream_settings<double>(h->cfg, f->N, f->c.snr_threshold, snr_threshold, min_duration_s, max_duration_s, f->h_set_s, changed);
-    for (int s = 0; s < S; ++s)
-        if (changed[(size_t)s]) {
-            f->reset_pending[(size_t)s] = 1;
-            f->any_reset = true;
-        }
-    if (f->h_set_s.empty()) {
-        if (f->d_set_s) (void)hipFree(f->d_set_s);
-        f->d_set_s = nullptr;
-        return RT_OK;
-    }
-    RT_HIP(h, hipMemcpy(f->d_set_s, f->h_set_s.data(), bytes, hipMemcpyHostToDevice));
-    return RT_OK;
+    return set_stream_settings_one<double>(h, f->c.snr_threshold, f->h_set_s, f->d_set_s, snr_threshold, min_duration_s, max_duration_s);
 }
 
 int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t n_bins, const double *last_dev, int32_t n_seg_last) {
@@ -4207,14 +4053,12 @@ int rt_extract_f64(rt_handle *h, const double *spec_dev, int32_t n_seg, int32_t 
     F64Slot &sl = f64_claim(f);
     sl.pending = false;
     sl.is_extract = true;
-    sl.iq_on = false;
+    sl.lc.clear();  // (rt_extract_f64 takes nothing from the ledger and ignores the presence mask)
     sl.n_seg = n_seg;
     sl.ex_spec = spec_dev;
     sl.ex_bins = n_bins;
     sl.ex_last = last_dev;
     sl.ex_last_cols = last_dev ? n_seg_last : 0;
-    sl.no_last = false;
-    sl.masked = false;  // (rt_extract_f64 ignores the presence mask)
     return f64_start(h, sl);
 }
 
@@ -4321,9 +4165,9 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     if (h->riq) {  // rt_fetch_record_iq, as in fetch_one
         RecordIq &q = *h->riq;
         if (sl.is_extract) q.delivered = kIqExtract;
-        else if (!sl.iq_on) q.delivered = kIqOff;
+        else if (!sl.lc.iq_on) q.delivered = kIqOff;
         else if (!f->cells_full) q.delivered = kIqTruncated;
-        else iq_gather(h, (int)(&sl - f->slot), sl.h_out, sizeof(rt_record_f64), total, sl.iq, sl.stream_stride);
+        else iq_gather(h, (int)(&sl - f->slot), sl.lc.iq, sl.h_out, sizeof(rt_record_f64), total, sl.iq, sl.stream_stride);
     }
     if (truncated) return f64_err(h, RT_E_CAPACITY, "rt_extract_f64: a stream found more records than record_capacity");
     if (n < total) return f64_err(h, RT_E_CAPACITY, "output buffer too small: records lost");

@@ -15,7 +15,7 @@
 
 #include "../../include/rt_analyze.h"
 #include "rt_core.h"
-#include "rt_record_iq_book.h"
+#include "rt_ledger.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -321,163 +321,183 @@ void hc_bluestein_tables_f64(const double *window, int N, int M, int log2m, cd *
     std::memcpy(bfilt, t.bfilt.data(), t.bfilt.size() * sizeof(cd));
 }
 
-// ---- streams that sit out a call (rt_core.h: PresenceBook) ----
-// The bookkeeping as a handle drives it: one book, the pending resets, the rotation of the look-back tails, and the two call
-// slots' snapshots (call k in slot k % 2).  `all`: the one segment count the handle had when rt_set_present was first called.
-struct HcPresence {
-    PresenceBook book;
-    std::vector<uint8_t> reset_pending;
-    int tail_cur = 0;
+// ---- the look-back ledger (rt_ledger.h: StreamLedger, LedgerCall) ----
+// The driver a handle runs, with a handle's two call slots (call k in slot k % 2): hc_presence_*, hc_chain_*, hc_iq_* and
+// hc_ledger_* are views of this one object.  Only hc_iq_* use the members below `pending`: host-memory stand-ins for the tail
+// area and the two kernels of rt_record_iq.h, which are not part of the driver.
+struct HcLedger {
+    StreamLedger led;
+    LedgerCall slot[2];
     unsigned long long n_calls = 0;
-    PresenceCall slot[2];
-    ChainBook chain;  // (hc_chain_*, below: off until hc_chain_set)
-    ChainCall chain_slot[2];
+    bool pending[2] = {false, false};
+    int K = 0, N = 0;
+    struct Source {  // the caller's arrays: they must stay alive until their call is fetched, as a handle's callers' must
+        const char *data = nullptr;
+        int64_t stride = 0;
+        int bps = 0;
+    } src[2];
+    std::vector<char> tails;
+    int64_t row_bytes = 0;
+    int area_bps = 0;
 };
-static void hc_presence_copy(const PresenceCall &c, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
-    if (absent) std::memcpy(absent, c.absent.data(), c.absent.size());
-    if (n_seg_last) std::memcpy(n_seg_last, c.n_seg_last.data(), c.n_seg_last.size() * sizeof(int32_t));
+static HcLedger *hc_led(void *h) { return static_cast<HcLedger *>(h); }
+static void hc_put(int32_t *dst, const std::vector<int32_t> &v) {
+    if (dst) std::memcpy(dst, v.data(), v.size() * sizeof(int32_t));
+}
+static void hc_presence_copy(const LedgerCall &c, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
+    if (absent) std::memcpy(absent, c.pc.absent.data(), c.pc.absent.size());
+    hc_put(n_seg_last, c.pc.n_seg_last);
     if (tails) {
         tails[0] = c.tail_read;
         tails[1] = c.tail_write;
     }
 }
-void *hc_presence_new(int n_streams, int all) {
-    HcPresence *p = new HcPresence();
-    p->book.activate(n_streams, all);
-    p->reset_pending.assign((size_t)n_streams, (uint8_t)0);
+static LedgerCall &hc_begin(HcLedger *p, int T, int fmt) {
+    const int idx = (int)(p->n_calls++ % 2);
+    const LedgerCall &o = p->slot[1 - idx];
+    p->led.begin_call(T, fmt, p->pending[1 - idx] && o.iq_on ? &o.iq : nullptr, p->slot[idx]);
+    return p->slot[idx];
+}
+static bool hc_in_slots(const HcLedger *p, unsigned long long k) { return k < p->n_calls && k + 2 >= p->n_calls; }
+
+// `n_seg_last`: the handle's one segment count so far (-1: none)
+void *hc_ledger_new(int n_streams, int n_seg_last) {
+    HcLedger *p = new HcLedger();
+    p->led.configure(n_streams);
+    p->led.n_seg_last = n_seg_last;
     return p;
 }
-void hc_presence_free(void *h) { delete static_cast<HcPresence *>(h); }
-int hc_presence_set(void *h, const uint8_t *mask) { return static_cast<HcPresence *>(h)->book.set_mask(mask) ? 1 : 0; }
-void hc_presence_reset_stream(void *h, int s) { static_cast<HcPresence *>(h)->reset_pending[(size_t)s] = 1; }
-void hc_presence_reset_all(void *h) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    p->book.forget_all();
-    std::fill(p->reset_pending.begin(), p->reset_pending.end(), (uint8_t)0);
+// one call of T segments: rows[S] = look_back_rows, tails[2] = buffer read / written, took[S] = the lock-step resets it took
+// (all zero: none); returns the call's number
+long long hc_ledger_call(void *h, int T, int32_t *rows, int32_t *tails, uint8_t *took) {
+    HcLedger *p = hc_led(h);
+    LedgerCall &c = hc_begin(p, T, 0);
+    if (rows) std::memcpy(rows, p->led.look_back_rows(c), (size_t)p->led.S * sizeof(int32_t));
+    tails[0] = c.tail_read;
+    tails[1] = c.tail_write;
+    for (int s = 0; took && s < p->led.S; ++s) took[s] = (size_t)s < c.took.size() && c.took[(size_t)s] ? 1 : 0;
+    return (long long)p->n_calls - 1;
 }
+// what call `k` (one of the latest two) was enqueued with
+int hc_ledger_snapshot(void *h, unsigned long long k, int32_t *rows, int32_t *tails) {
+    HcLedger *p = hc_led(h);
+    if (!hc_in_slots(p, k)) return -1;
+    LedgerCall &c = p->slot[k % 2];
+    std::memcpy(rows, p->led.look_back_rows(c), (size_t)p->led.S * sizeof(int32_t));
+    tails[0] = c.tail_read;
+    tails[1] = c.tail_write;
+    return c.masked ? 1 : 0;
+}
+void hc_ledger_mark_changed(void *h, const uint8_t *changed) { hc_led(h)->led.mark_changed(std::vector<uint8_t>(changed, changed + hc_led(h)->led.S)); }
+void hc_ledger_activate_presence(void *h) { hc_led(h)->led.activate_presence(); }
+// scalars[4]: tail_cur, n_seg_last, any_reset(), the per-stream regime is on; reset_pending[S]; per_stream[S] (that regime only)
+void hc_ledger_state(void *h, int32_t *scalars, uint8_t *reset_pending, int32_t *per_stream) {
+    const StreamLedger &l = hc_led(h)->led;
+    scalars[0] = l.tail_cur;
+    scalars[1] = l.n_seg_last;
+    scalars[2] = l.any_reset() ? 1 : 0;
+    scalars[3] = l.pres.active ? 1 : 0;
+    std::memcpy(reset_pending, l.reset_pending.data(), l.reset_pending.size());
+    if (l.pres.active) hc_put(per_stream, l.pres.n_seg_last);
+}
+// every vector of slot `idx`'s LedgerCall as (data(), capacity()) in out[2 * n]; returns n
+int hc_ledger_call_footprint(void *h, int idx, unsigned long long *out) {
+    const LedgerCall &c = hc_led(h)->slot[idx];
+    int n = 0;
+    const auto put = [&](const auto &v) {
+        out[2 * n] = (unsigned long long)reinterpret_cast<uintptr_t>(v.data());
+        out[2 * n++ + 1] = (unsigned long long)v.capacity();
+    };
+    put(c.took), put(c.last);
+    put(c.pc.absent), put(c.pc.n_seg_last), put(c.pc.before), put(c.pc.took_reset);
+    put(c.cc.src_buf), put(c.cc.src_idx), put(c.cc.before_idx), put(c.cc.before_T);
+    put(c.iq.lead_kind), put(c.iq.lead_row), put(c.iq.lead_buf), put(c.iq.lead_D), put(c.iq.lead_held);
+    put(c.iq.write_buf), put(c.iq.write_D), put(c.iq.before_cur), put(c.iq.before_held), put(c.iq.before_fmt);
+    return n;
+}
+
+// ---- streams that sit out a call (rt_core.h: PresenceBook, driven by the ledger) ----
+// `all`: the one segment count the handle had when rt_set_present was first called.
+void *hc_presence_new(int n_streams, int all) {
+    void *h = hc_ledger_new(n_streams, all);
+    hc_ledger_activate_presence(h);
+    return h;
+}
+void hc_presence_free(void *h) { delete hc_led(h); }
+int hc_presence_set(void *h, const uint8_t *mask) { return hc_led(h)->led.set_mask(mask) ? 1 : 0; }
+void hc_presence_reset_stream(void *h, int s) { hc_led(h)->led.reset_stream(s); }
+void hc_presence_reset_all(void *h) { hc_led(h)->led.forget_all(); }  // rt_reset
 // one call of T segments: its snapshot (absent[S], n_seg_last[S], tails[2] = buffer read / written); returns the streams present
 int hc_presence_call(void *h, int T, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    PresenceCall &c = p->slot[p->n_calls % 2];
-    p->book.begin_call(T, p->tail_cur, p->reset_pending, c);
-    p->tail_cur = c.tail_write;
-    ++p->n_calls;
+    const LedgerCall &c = hc_begin(hc_led(h), T, 0);
     hc_presence_copy(c, absent, n_seg_last, tails);
-    return c.n_present;
+    return c.pc.n_present;
 }
 // the snapshot call number `k` (0-based; one of the latest two) was enqueued with: what a re-analysis inside rt_fetch reads
 int hc_presence_snapshot(void *h, unsigned long long k, uint8_t *absent, int32_t *n_seg_last, int32_t *tails) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    if (k >= p->n_calls || k + 2 < p->n_calls) return -1;
+    HcLedger *p = hc_led(h);
+    if (!hc_in_slots(p, k)) return -1;
     hc_presence_copy(p->slot[k % 2], absent, n_seg_last, tails);
-    return p->slot[k % 2].n_present;
+    return p->slot[k % 2].pc.n_present;
 }
 // the newest call is undone
 void hc_presence_rollback(void *h) {
-    HcPresence *p = static_cast<HcPresence *>(h);
+    HcLedger *p = hc_led(h);
     if (p->n_calls == 0) return;
     --p->n_calls;
-    const PresenceCall &c = p->slot[p->n_calls % 2];
-    p->book.rollback(c, p->reset_pending);
-    p->tail_cur = c.tail_read;
+    p->led.rollback(p->slot[p->n_calls % 2]);
+    p->pending[p->n_calls % 2] = false;
 }
 void hc_presence_state(void *h, int32_t *n_seg_last, uint8_t *reset_pending, uint8_t *present) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    std::memcpy(n_seg_last, p->book.n_seg_last.data(), p->book.n_seg_last.size() * sizeof(int32_t));
-    std::memcpy(reset_pending, p->reset_pending.data(), p->reset_pending.size());
-    std::memcpy(present, p->book.present.data(), p->book.present.size());
+    const StreamLedger &l = hc_led(h)->led;
+    hc_put(n_seg_last, l.pres.n_seg_last);
+    std::memcpy(reset_pending, l.reset_pending.data(), l.reset_pending.size());
+    std::memcpy(present, l.pres.present.data(), l.pres.present.size());
 }
 
-// ---- consecutive buffers as the streams of one call (rt_core.h: ChainBook) ----
-// On top of the presence bookkeeping above, as a chained handle drives both: `h` is an hc_presence_new handle.
-void hc_chain_set(void *h, int links) {  // (a change forgets all look-back, as rt_set_chain does)
-    HcPresence *p = static_cast<HcPresence *>(h);
-    p->chain.configure(p->book.S, links);
-    hc_presence_reset_all(h);
-}
-void hc_chain_reset_all(void *h) {  // rt_reset
-    hc_presence_reset_all(h);
-    static_cast<HcPresence *>(h)->chain.forget_all();
-}
-static void hc_chain_copy(const ChainCall &c, int32_t *src_buf, int32_t *src_idx) {
-    if (src_buf) std::memcpy(src_buf, c.src_buf.data(), c.src_buf.size() * sizeof(int32_t));
-    if (src_idx) std::memcpy(src_idx, c.src_idx.data(), c.src_idx.size() * sizeof(int32_t));
-}
+// ---- consecutive buffers as the streams of one call (rt_core.h: ChainBook, driven by the ledger) ----
+// `h` is an hc_presence_new handle.
+void hc_chain_set(void *h, int links) { hc_led(h)->led.set_chain(links); }  // (a change forgets all look-back, as rt_set_chain does)
+void hc_chain_reset_all(void *h) { hc_led(h)->led.forget_all(); }           // rt_reset
 // one chained call of T segments: hc_presence_call's outputs (n_seg_last as the chain rewrites it) and each stream's source
 // (src_buf[S]: 0 none, 1 the buffer the call writes, 2 the buffer it reads; src_idx[S])
 int hc_chain_call(void *h, int T, uint8_t *absent, int32_t *n_seg_last, int32_t *tails, int32_t *src_buf, int32_t *src_idx, uint8_t *took_reset) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    const int slot = (int)(p->n_calls % 2);
-    PresenceCall &c = p->slot[slot];
-    p->book.begin_call(T, p->tail_cur, p->reset_pending, c);
-    p->chain.begin_call(T, c, p->chain_slot[slot]);
-    p->tail_cur = c.tail_write;
-    ++p->n_calls;
+    const LedgerCall &c = hc_begin(hc_led(h), T, 0);
     hc_presence_copy(c, absent, n_seg_last, tails);
-    hc_chain_copy(p->chain_slot[slot], src_buf, src_idx);
-    if (took_reset) std::memcpy(took_reset, c.took_reset.data(), c.took_reset.size());
-    return c.n_present;
+    hc_put(src_buf, c.cc.src_buf);
+    hc_put(src_idx, c.cc.src_idx);
+    if (took_reset) std::memcpy(took_reset, c.pc.took_reset.data(), c.pc.took_reset.size());
+    return c.pc.n_present;
 }
 int hc_chain_snapshot(void *h, unsigned long long k, int32_t *n_seg_last, int32_t *src_buf, int32_t *src_idx) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    if (k >= p->n_calls || k + 2 < p->n_calls) return -1;
-    hc_presence_copy(p->slot[k % 2], nullptr, n_seg_last, nullptr);
-    hc_chain_copy(p->chain_slot[k % 2], src_buf, src_idx);
+    HcLedger *p = hc_led(h);
+    if (!hc_in_slots(p, k)) return -1;
+    hc_put(n_seg_last, p->slot[k % 2].pc.n_seg_last);
+    hc_put(src_buf, p->slot[k % 2].cc.src_buf);
+    hc_put(src_idx, p->slot[k % 2].cc.src_idx);
     return 0;
 }
-void hc_chain_rollback(void *h) {
-    HcPresence *p = static_cast<HcPresence *>(h);
-    if (p->n_calls == 0) return;
-    p->chain.rollback(p->chain_slot[(p->n_calls - 1) % 2]);
-    hc_presence_rollback(h);
-}
+void hc_chain_rollback(void *h) { hc_presence_rollback(h); }
 // the first run in which `v` ([S] floats) is not uniform, or -1 (rt_set_stream_params / rt_set_stream_settings on a chained handle)
-int hc_chain_first_mixed_run(void *h, const float *v) { return static_cast<HcPresence *>(h)->chain.first_mixed_run(v); }
+int hc_chain_first_mixed_run(void *h, const float *v) { return hc_led(h)->led.chain.first_mixed_run(v); }
 
-// ---- the samples behind every record (rt_record_iq_book.h: IqTailBook, iq_build_descs) ----
-// The bookkeeping as a handle drives it (rt_analyze.hip: iq_begin at enqueue, iq_gather inside rt_fetch), with the two kernels of
-// rt_record_iq.h restated as memcpy on host memory: one handle-wide segment count until hc_iq_present / hc_iq_chain move the handle
-// to per-stream rows, the pending resets, two call slots (call k in slot k % 2), three tail rows per stream.  The caller's arrays
-// must stay alive until their call is fetched, as a handle's callers' must.
-struct HcIq {
-    int S = 0, K = 0, N = 0;
-    IqTailBook book;
-    PresenceBook pres;
-    ChainBook chain;
-    std::vector<uint8_t> reset_pending;
-    int tail_cur = 0, n_seg_last = -1;
-    unsigned long long n_calls = 0;
-    struct Call {
-        bool pending = false, iq_on = false, masked = false, chained = false;
-        PresenceCall pc;
-        ChainCall cc;
-        IqCall iq;
-        std::vector<uint8_t> took;  // unmasked: the resets the call took
-        int prev_n_seg_last = -1;
-        const char *data = nullptr;
-        int64_t stride = 0;
-        int bps = 0;
-    } slot[2];
-    std::vector<char> tails;
-    int64_t row_bytes = 0;
-    int area_bps = 0;
-};
+// ---- the samples behind every record (rt_record_iq_book.h: IqTailBook driven by the ledger, iq_build_descs) ----
+// A handle in lock-step until hc_iq_present / hc_iq_chain move it to per-stream rows; three tail rows per stream in host memory,
+// the two kernels of rt_record_iq.h restated as memcpy.
 void *hc_iq_new(int n_streams, int tail_cols, int nperseg) {
-    HcIq *p = new HcIq();
-    p->S = n_streams;
+    HcLedger *p = hc_led(hc_ledger_new(n_streams, -1));
     p->K = tail_cols;
     p->N = nperseg;
-    p->reset_pending.assign((size_t)n_streams, (uint8_t)0);
-    p->book.configure(n_streams, tail_cols, -1);
+    p->led.set_iq_margin(tail_cols, -1);
     return p;
 }
-void hc_iq_free(void *h) { delete static_cast<HcIq *>(h); }
+void hc_iq_free(void *h) { delete hc_led(h); }
 // rt_set_record_iq: -1 = refused (calls pending, or m out of range)
 int hc_iq_set_margin(void *h, int m) {
-    HcIq *p = static_cast<HcIq *>(h);
-    if (m > kIqMaxMargin || p->slot[0].pending || p->slot[1].pending) return -1;
-    if ((m < 0 ? -1 : m) != p->book.margin) {
-        p->book.configure(p->S, p->K, m);
+    HcLedger *p = hc_led(h);
+    if (m > kIqMaxMargin || p->pending[0] || p->pending[1]) return -1;
+    if ((m < 0 ? -1 : m) != p->led.iq.margin) {
+        p->led.set_iq_margin(p->K, m);
         p->tails.clear();
         p->row_bytes = 0;
         p->area_bps = 0;
@@ -485,107 +505,55 @@ int hc_iq_set_margin(void *h, int m) {
     return 0;
 }
 void hc_iq_present(void *h, const uint8_t *mask) {
-    HcIq *p = static_cast<HcIq *>(h);
-    if (!p->pres.active) p->pres.activate(p->S, p->n_seg_last);
-    p->pres.set_mask(mask);
+    hc_led(h)->led.activate_presence();
+    hc_led(h)->led.set_mask(mask);
 }
-void hc_iq_reset_stream(void *h, int s) { static_cast<HcIq *>(h)->reset_pending[(size_t)s] = 1; }
-void hc_iq_reset_all(void *h) {  // rt_reset
-    HcIq *p = static_cast<HcIq *>(h);
-    p->n_seg_last = -1;
-    if (p->pres.active) p->pres.forget_all();
-    p->chain.forget_all();
-    std::fill(p->reset_pending.begin(), p->reset_pending.end(), (uint8_t)0);
-    p->book.forget_all();
-}
+void hc_iq_reset_stream(void *h, int s) { hc_led(h)->led.reset_stream(s); }
+void hc_iq_reset_all(void *h) { hc_led(h)->led.forget_all(); }  // rt_reset
 int hc_iq_chain(void *h, int links) {  // rt_set_chain
-    HcIq *p = static_cast<HcIq *>(h);
-    if (p->slot[0].pending || p->slot[1].pending || (links >= 2 && p->S % links != 0)) return -1;
-    if (links >= 2 && !p->pres.active) hc_iq_present(h, nullptr);
-    p->chain.configure(p->S, links);
-    hc_iq_reset_all(h);
+    HcLedger *p = hc_led(h);
+    if (p->pending[0] || p->pending[1] || (links >= 2 && p->led.S % links != 0)) return -1;
+    p->led.set_chain(links);
     return 0;
 }
 // rt_process*: a call of T segments in format code `fmt`, `bps` bytes a sample, rows `stride` samples apart at `data`.  Fills, if
 // given, the call's snapshot ([S] each) and returns the call's number.
 long long hc_iq_call(void *h, int T, int fmt, int bps, const void *data, long long stride, int32_t *lead_kind, int32_t *lead_row, int32_t *lead_buf,
                      int32_t *lead_D, int32_t *write_buf) {
-    HcIq *p = static_cast<HcIq *>(h);
-    const int idx = (int)(p->n_calls % 2), S = p->S;
-    HcIq::Call &c = p->slot[idx];
-    const HcIq::Call &o = p->slot[1 - idx];
-    c = HcIq::Call();
-    c.prev_n_seg_last = p->n_seg_last;
-    c.data = static_cast<const char *>(data);
-    c.stride = stride;
-    c.bps = bps;
-    std::vector<int32_t> last;
-    if (p->pres.active) {
-        p->pres.begin_call(T, p->tail_cur, p->reset_pending, c.pc);
-        c.masked = true;
-        if (p->chain.on()) {
-            p->chain.begin_call(T, c.pc, c.cc);
-            c.chained = true;
-        }
-    } else {
-        c.took = p->reset_pending;
-        last.assign((size_t)S, (int32_t)p->n_seg_last);
-        for (int s = 0; s < S; ++s)
-            if (c.took[(size_t)s]) last[(size_t)s] = -1;
-        std::fill(p->reset_pending.begin(), p->reset_pending.end(), (uint8_t)0);
+    HcLedger *p = hc_led(h);
+    const int idx = (int)(p->n_calls % 2), S = p->led.S;
+    p->src[idx] = HcLedger::Source{static_cast<const char *>(data), stride, bps};
+    if (p->led.iq.on() && (p->tails.empty() || bps > p->area_bps)) {  // (rt_analyze.hip: iq_tail_area -- every row keeps its place and its bytes)
+        const int64_t row = ((int64_t)p->led.iq.cols() * p->N * bps + 15) / 16 * 16;
+        std::vector<char> area((size_t)(kIqRows * S) * (size_t)row);
+        for (int64_t r = 0; !p->tails.empty() && r < (int64_t)kIqRows * S; ++r)
+            std::memcpy(area.data() + r * row, p->tails.data() + r * p->row_bytes, (size_t)p->row_bytes);
+        p->tails.swap(area);
+        p->row_bytes = row;
+        p->area_bps = bps;
     }
-    if (p->book.on()) {
-        if (p->tails.empty() || bps > p->area_bps) {  // (rt_analyze.hip: iq_tail_area -- every row keeps its place and its bytes)
-            const int64_t row = ((int64_t)p->book.cols() * p->N * bps + 15) / 16 * 16;
-            std::vector<char> area((size_t)(kIqRows * S) * (size_t)row);
-            for (int64_t r = 0; !p->tails.empty() && r < (int64_t)kIqRows * S; ++r)
-                std::memcpy(area.data() + r * row, p->tails.data() + r * p->row_bytes, (size_t)p->row_bytes);
-            p->tails.swap(area);
-            p->row_bytes = row;
-            p->area_bps = bps;
-        }
-        p->book.begin_call(T, fmt, c.masked ? c.pc.n_seg_last.data() : last.data(), c.masked ? c.pc.absent.data() : nullptr,
-                           c.chained ? c.cc.src_buf.data() : nullptr, c.chained ? c.cc.src_idx.data() : nullptr,
-                           o.pending && o.iq_on ? &o.iq : nullptr, c.iq);
-        c.iq_on = true;
+    const LedgerCall &c = hc_begin(p, T, fmt);
+    p->pending[idx] = true;
+    if (c.iq_on) {
         for (int s = 0; s < S; ++s) {  // iq_tails
             const int buf = c.iq.write_buf[(size_t)s], D = c.iq.write_D[(size_t)s];
             if (buf < 0 || D <= 0) continue;
-            std::memcpy(p->tails.data() + ((int64_t)buf * S + s) * p->row_bytes, c.data + ((int64_t)s * stride + (int64_t)(T - D) * p->N) * bps,
+            std::memcpy(p->tails.data() + ((int64_t)buf * S + s) * p->row_bytes, p->src[idx].data + ((int64_t)s * stride + (int64_t)(T - D) * p->N) * bps,
                         (size_t)((int64_t)D * p->N * bps));
         }
-        const auto put = [&](int32_t *dst, const std::vector<int32_t> &v) {
-            if (dst) std::memcpy(dst, v.data(), v.size() * sizeof(int32_t));
-        };
-        put(lead_kind, c.iq.lead_kind);
-        put(lead_row, c.iq.lead_row);
-        put(lead_buf, c.iq.lead_buf);
-        put(lead_D, c.iq.lead_D);
-        put(write_buf, c.iq.write_buf);
+        hc_put(lead_kind, c.iq.lead_kind);
+        hc_put(lead_row, c.iq.lead_row);
+        hc_put(lead_buf, c.iq.lead_buf);
+        hc_put(lead_D, c.iq.lead_D);
+        hc_put(write_buf, c.iq.write_buf);
     }
-    c.pending = true;
-    if (c.masked) p->tail_cur = c.pc.tail_write;
-    p->n_seg_last = T;
-    return (long long)p->n_calls++;
+    return (long long)p->n_calls - 1;
 }
 // the newest call is undone (a failed rt_process*, or a later lane's): -1 if there is none pending
 int hc_iq_rollback(void *h) {
-    HcIq *p = static_cast<HcIq *>(h);
-    if (p->n_calls == 0) return -1;
-    HcIq::Call &c = p->slot[(p->n_calls - 1) % 2];
-    if (!c.pending) return -1;
-    if (c.iq_on) p->book.rollback(c.iq);
-    if (c.chained) p->chain.rollback(c.cc);
-    if (c.masked) {
-        p->pres.rollback(c.pc, p->reset_pending);
-        p->tail_cur = c.pc.tail_read;
-    } else {
-        for (int s = 0; s < p->S; ++s)
-            if (c.took[(size_t)s]) p->reset_pending[(size_t)s] = 1;
-    }
-    p->n_seg_last = c.prev_n_seg_last;
-    c = HcIq::Call();
-    --p->n_calls;
+    HcLedger *p = hc_led(h);
+    if (p->n_calls == 0 || !p->pending[(p->n_calls - 1) % 2]) return -1;
+    hc_presence_rollback(h);
     return 0;
 }
 // rt_fetch + rt_fetch_record_iq of call `k`: `rec` = n records as int32 (stream, fi, start, end), in delivery order.  Writes
@@ -593,25 +561,25 @@ int hc_iq_rollback(void *h) {
 // of the samples, -1: no such pending call, -2: the call was enqueued with the feature off, -3: a descriptor out of bounds.
 long long hc_iq_fetch(void *h, unsigned long long k, const int32_t *rec, long long n, int64_t *offsets, int32_t *first_seg, void *out, long long cap_bytes,
                       long long *n_descs) {
-    HcIq *p = static_cast<HcIq *>(h);
-    if (k >= p->n_calls || k + 2 < p->n_calls) return -1;
-    HcIq::Call &c = p->slot[k % 2];
-    if (!c.pending) return -1;
-    c.pending = false;
+    HcLedger *p = hc_led(h);
+    if (!hc_in_slots(p, k) || !p->pending[k % 2]) return -1;
+    const LedgerCall &c = p->slot[k % 2];
+    const HcLedger::Source &src = p->src[k % 2];
+    p->pending[k % 2] = false;
     if (!c.iq_on) return -2;
     std::vector<IqDesc> descs;
     const int64_t total = iq_build_descs(c.iq, p->N, rec, 4 * sizeof(int32_t), (size_t)n, offsets, first_seg, &descs);
     if (n_descs) *n_descs = (long long)descs.size();
-    if (!iq_descs_in_bounds(descs, p->S, (int64_t)c.iq.T * p->N, (int64_t)p->book.cols() * p->N, total)) return -3;
+    if (!iq_descs_in_bounds(descs, p->led.S, (int64_t)c.iq.T * p->N, (int64_t)p->led.iq.cols() * p->N, total)) return -3;
     std::vector<int64_t> tile_first;
-    if (iq_tile_prefix(descs, c.bps, &tile_first) < (int64_t)descs.size()) return -3;  // (every descriptor holds a tile)
-    if (out && cap_bytes >= total * c.bps)
+    if (iq_tile_prefix(descs, src.bps, &tile_first) < (int64_t)descs.size()) return -3;  // (every descriptor holds a tile)
+    if (out && cap_bytes >= total * src.bps)
         for (const IqDesc &d : descs) {  // record_iq_gather
-            const char *src = d.kind == kIqFromTail ? p->tails.data() + ((int64_t)d.buf * p->S + d.row) * p->row_bytes + d.src_sample * c.bps
-                                                    : c.data + ((int64_t)d.row * c.stride + d.src_sample) * c.bps;
-            std::memcpy(static_cast<char *>(out) + d.dst_sample * c.bps, src, (size_t)(d.len * c.bps));
+            const char *from = d.kind == kIqFromTail ? p->tails.data() + ((int64_t)d.buf * p->led.S + d.row) * p->row_bytes + d.src_sample * src.bps
+                                                     : src.data + ((int64_t)d.row * src.stride + d.src_sample) * src.bps;
+            std::memcpy(static_cast<char *>(out) + d.dst_sample * src.bps, from, (size_t)(d.len * src.bps));
         }
-    return (long long)(total * c.bps);
+    return (long long)(total * src.bps);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // rt_record_iq_book.h -- host side of rt_set_record_iq / rt_fetch_record_iq (include/rt_analyze.h): which sample tails a handle
-// holds, and the copy list that cuts every record's IQ out of them and of the call's buffer.  Host-only (no HIP): rt_analyze.hip
-// drives it for every handle kind, rt_hostcheck.cpp exports it so that the CPU suite can hold it to a NumPy model; the kernels
+// holds, and the copy list that cuts every record's IQ out of them and of the call's buffer.  Host-only (no HIP): a handle's
+// look-back ledger (rt_ledger.h) drives it for every handle kind, and through rt_hostcheck.cpp for the CPU suite's NumPy model; the kernels
 // that execute what it decides are in rt_record_iq.h.
 //
 // A record's `start` may be negative: it then counts whole segments back from the end of the buffer the detection looked back
