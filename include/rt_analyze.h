@@ -364,7 +364,7 @@ const char *rt_last_error(rt_handle *h);
  *     again.  The records of such a stream are the ones a large enough hot_capacity would have given, byte for byte, the
  *     row means (RT_FLAG_ROW_MEANS) as well.  rt_call_info of a delivered call of such a handle: mode_used =
  *     RT_MODE_SPARSE, n_dense_streams = the streams analysed again, fell_back = 1 if there were any, n_hot = the cells the
- *     present streams emitted (the counters, not the cells stored).  No memory for the scratch: rt_fetch_f64 returns
+ *     present streams emitted (the counters, not the cells stored; so on every RT_FLAG_F64_SPARSE handle).  No memory for the scratch: rt_fetch_f64 returns
  *     RT_E_NOMEM and consumes the call, whose look-back tail stays the next call's.  The cost is a second transform and
  *     a serial walk over T cells per bin for each such stream: a handle many of whose streams overflow belongs on the
  *     dense path (measured break-even at 4 096 streams x 300 kS, nperseg 256: about 4 % of the streams);

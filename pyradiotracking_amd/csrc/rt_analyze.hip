@@ -4154,8 +4154,9 @@ int rt_fetch_f64(rt_handle *h, rt_record_f64 *out, size_t cap, size_t *n_out) {
     if (rescue_call) {
         h->info.n_dense_streams = sl.n_rescued;
         h->info.fell_back = sl.n_rescued > 0 ? 1 : 0;
-        for (int s = 0; s < S; ++s) h->info.n_hot += sl.h_hot[s];  // (the counters: cells emitted, not cells stored)
     }
+    // (the counters: cells emitted, not cells stored -- of every map-free call, with RT_FLAG_F64_RESCUE or without)
+    for (int s = 0; sparse_call && s < S; ++s) h->info.n_hot += sl.h_hot[s];
     if (total && (!out || !cap)) return truncated ? RT_E_CAPACITY : RT_OK;  // size query: the call stays pending
     const size_t n = std::min(total, cap);
     if (n) std::memcpy(out, sl.h_out, n * sizeof(rt_record_f64));

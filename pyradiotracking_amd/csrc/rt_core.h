@@ -310,6 +310,17 @@ inline int key_tbits(int n_seg) {
     return t;
 }
 
+// The size edges of the sparse detection (rt_kernels.h: detect_bucket_one, detect_group, detect_runs).  They stand here, beside
+// key_tbits, so that the host build (rt_hostcheck.cpp: hc_detect_order_constants) hands them to tests/detect_order_cases.py, which
+// restates the choice of ordering routine from them.
+constexpr int kBuckets = 16;  // candidate lists per stream: bucket = bin & 15 (a bin never spans buckets).
+                              // 64 was measured: detect -6 %, but the scan +2 % (N=256) .. +8 % (N=1024)
+constexpr int kSmallBucket = 1024;  // buckets up to this many cells use the small-LDS instantiation
+constexpr int kQuarters = 4;        // detect_group: a wave takes a stream's buckets all together or a quarter of them
+constexpr int kCandCapMax = 64;     // plateaus a bucket wave stages in LDS before it finishes them (a.cand_cap <= this); no limit per bucket
+constexpr int kGroupCells = 896;    // detect_group: cells of a whole stream one wave takes
+constexpr int kGroupBins = 256;     // (kSmallBucket - kGroupCells) * 8 / 4: the group's row means lie behind its cells
+
 // Which kernel family an nperseg runs on:
 //   256 r, r in {1, 2, 4, 8, 16}   the fused scans (rt_kernels.h: stft_scan<R3 = r>; 4096: rt_scan64.h), lane groups of 16 r lanes
 //   16 q, q in {2, 4, 8}           the fused scans with lane groups of q lanes (stft_scan<1, .., QS = q>)

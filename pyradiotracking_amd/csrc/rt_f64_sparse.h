@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void detect_sparse_f64(const F64SparseArgs sa)
     double *const sval = reinterpret_cast<double *>(f64d_smem);            // [sort_cap]
     uint32_t *const skey = reinterpret_cast<uint32_t *>(sval + sa.sort_cap);  // [sort_cap]
     int M = 1;
-    while (M < n) M <<= 1;
+    while (M < n) M <<= 1;  // (the lengths at their edges, up to hot_cap and one past it: tests/detect_order_cases.py)
     for (int j = tid; j < M; j += 256) {
         skey[j] = j < n ? sa.keys[(int64_t)s * sa.hot_cap + j] : 0xFFFFFFFFu;
         sval[j] = j < n ? sa.vals[(int64_t)s * sa.hot_cap + j] : 0.0;

@@ -274,6 +274,11 @@ int hc_choose_chunk(int nperseg, int block, double fs, double min_d, int segs_pe
 }
 long long hc_min_run_cells(int nperseg, double fs, double min_d) { return min_run_cells(nperseg, fs, min_d); }
 int hc_key_tbits(int n_seg) { return key_tbits(n_seg); }
+// out[6]: kBuckets, kSmallBucket, kGroupCells, kGroupBins, kQuarters, kCandCapMax (the size edges of the sparse detection)
+void hc_detect_order_constants(int *out) {
+    const int v[6] = {kBuckets, kSmallBucket, kGroupCells, kGroupBins, kQuarters, kCandCapMax};
+    std::memcpy(out, v, sizeof v);
+}
 int hc_next_pow2(int v) { return next_pow2(v); }
 
 // n[2]: entries of tw1 / tw2; the tables are copied where the pointers are not null

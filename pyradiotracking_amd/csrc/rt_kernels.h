@@ -129,8 +129,7 @@ struct StftParams {
 // In noise with P(cell >= thr) = p a chunk bit is set with probability p^L: at L = 32 pass B touches nothing but the
 // neighbourhoods of real signals until the threshold sits ~7 dB under the noise floor.
 
-constexpr int kBuckets = 16;  // candidate lists per stream: bucket = bin & 15 (a bin never spans buckets).
-                              // 64 was measured: detect -6 %, but the scan +2 % (N=256) .. +8 % (N=1024)
+// (kBuckets, the candidate lists per stream: rt_core.h)
 
 constexpr int kStageCap = 128;  // candidate cells staged per wave before a flush (1 KiB)
 
@@ -2478,9 +2477,7 @@ __device__ __forceinline__ int settled_count(const DetectArgs &a, RecLds &l) {
 // ---------------------------------------------------------------------------
 // sparse detection: one WAVE per (stream, bucket), bucket = bin & (kBuckets-1)
 // ---------------------------------------------------------------------------
-constexpr int kSmallBucket = 1024;  // buckets up to this many cells use the small-LDS instantiation
-constexpr int kQuarters = 4;        // detect_group: a wave takes a stream's buckets all together or a quarter of them
-constexpr int kCandCapMax = 64;     // plateaus a bucket wave stages in LDS before it finishes them (a.cand_cap <= this); no limit per bucket
+// (kSmallBucket, kQuarters, kCandCapMax: rt_core.h)
 
 // Bitonic sort of 64*M (key, value) pairs held in registers, element i = m*64 + lane.
 // Compare-exchange distances >= 64 pair two registers of the same lane (no data
@@ -2902,6 +2899,7 @@ __device__ __forceinline__ void detect_bucket_one(const DetectArgs &a, const int
         while ((1 << hb) < F / kBuckets) ++hb;
         const bool packed = hb + a.tbits + 10 <= 32;
         const bool bitmap = hb + a.tbits <= 15 && n2 >= 128;  // (64 cells: the network is as cheap)
+        // (every routine and instantiation below at its size edges: tests/detect_order_cases.py)
         switch (RT_DETECT_ABLATE == 2 ? 0 : (bitmap ? n2 + 1 : packed ? n2 : -n2)) {
             case 0: for (int i = lane; i < n; i += 64) { keys[i] = src[i].x; vals[i] = __uint_as_float(src[i].y); } break;
             case 129: sort_bucket_bitmap<2>(src, n, lane, keys, vals, a.tbits, bkt); break;
@@ -3010,8 +3008,7 @@ __global__ __launch_bounds__(256) void detect_bucket(const DetectArgs a) {
 // 3.76 against 3.16 ms of detection per step; profiles/r06_k_*.)
 // LDS of a wave, inside the small-bucket wave's 8 KiB: keys[kGroupCells] | vals[kGroupCells] | row means of up to 256 bins.
 // ---------------------------------------------------------------------------
-constexpr int kGroupCells = 896;
-constexpr int kGroupBins = 256;  // (kSmallBucket - kGroupCells) * 8 / 4
+// (kGroupCells, kGroupBins: rt_core.h)
 
 // gather + sort: cell i of the group (i = m*64 + lane) is cell i - start(b) of bucket b, b = the number of buckets whose inclusive
 // prefix `ends[.]` is <= i; one word per cell ((bin, t) above the cell's position, as in sort_bucket_packed), the powers parked in LDS
@@ -3106,6 +3103,7 @@ __global__ __launch_bounds__(256) void detect_group(const DetectArgs a) {
     const uint2 *hot_s = a.hot + (int64_t)s * kBuckets * a.hot_cap;
     int n2 = 64;
     while (n2 < n) n2 <<= 1;
+    // (every instantiation at its size edges: tests/detect_order_cases.py)
     switch (n2) {
         case 64: sort_group_packed<1>(hot_s, a.hot_cap, ends, n, lane, keys, vals); break;
         case 128: sort_group_packed<2>(hot_s, a.hot_cap, ends, n, lane, keys, vals); break;
