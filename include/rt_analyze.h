@@ -627,6 +627,44 @@ int rt_set_record_iq(rt_handle *h, int32_t margin_segments);   /* >= 0: on, with
 int rt_fetch_record_iq(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
                        void *iq, size_t cap_bytes, size_t *n_bytes, int32_t *bytes_per_sample);
 
+/*
+ * ---- record STFT: one complex STFT value per delivered segment (additive within ABI version 6) ----
+ * A frequency finer than fs / nperseg or a phase track over a pulse needs, per segment, one complex number: the STFT value of the
+ * record's bin.  Its |.|^2 is the cell rt_fetch_record_cells delivers; its phase is what the scans compute and drop.  That is
+ * nperseg times less data than the snippet rt_fetch_record_iq hands out (8 bytes a segment instead of nperseg * 8), computed on
+ * the device from the snippets the delivering rt_fetch gathered.
+ *   - the call and the records are those of rt_fetch_record_iq: the call the last rt_fetch / rt_fetch_f64 delivered in full; record
+ *     i is the i-th record that fetch wrote, shadowed ones included, over all lanes; it delivers the same whole segments
+ *     first_seg[i] ... min(end_i + m, T) - 1, margin included.  rt_set_record_iq must be on; there is no switch of its own.
+ *   - `offsets`: HOST memory, n_offsets == n_records + 1 entries (or NULL), in SEGMENTS: rt_fetch_record_iq's offsets divided by
+ *     nperseg.  `first_seg`: as there.  *n_cells == offsets[n_records].
+ *   - `values`: HOST memory, cap_cells interleaved (re, im) pairs -- 2 * cap_cells floats (doubles: the _f64 entry).  values == NULL
+ *     or cap_cells == 0: a size query.  cap_cells < *n_cells with a buffer: RT_E_CAPACITY, nothing written.
+ *   - a value, for record (s, fi) and a delivered segment whose N = nperseg samples are x[0 .. N), converted as the scans convert
+ *     the call's format (complex64 as is; uint8 b / 127.5 - 1 by the scan kernels' one float32 fma; int16 * 2^-15; int8 * 2^-7; a
+ *     float64 handle: complex128 as is and the float64 conversions):
+ *         value = sqrt(scale) * sum_n w[n] * (x[n] - mean(x)) * exp(-2 pi i fi n / N)
+ *     w = the handle's window, scale = rt_config.scale (rt_config_f64.scale), fi = rt_record.fi (fftfreq order).  This is
+ *     scipy.signal.spectrogram(..., noverlap=0, return_onesided=False, mode='complex') at that bin and segment; in exact
+ *     arithmetic |value|^2 is the spectrogram cell.  On a float32 handle sqrt(scale) is evaluated in float64 and rounded once.
+ *   - the value depends on the snippet and the bin alone: the same samples give the same bytes on every handle kind (mode, lanes,
+ *     chained, masked) and on every fetch of the same call.  A segment whose samples are all one finite value gives exactly 0 + 0i
+ *     (the mean is taken about the segment's first sample), at every nperseg.  A non-finite sample makes the values of its segment
+ *     non-finite (NaN for NaN) and of no other.
+ *   - lazy: rt_process* and rt_fetch do nothing for it.  The first call of the entry on a handle allocates an nperseg-entry
+ *     twiddle table (and a float32 handle's copy of the window); the first call for a delivered call builds that call's values in a
+ *     pool per call slot that grows on demand, by one kernel on the gather's stream, waited for.  A repeated call copies them again.
+ *     A handle that never calls the entry allocates and launches what it did before.
+ *   - validity: exactly as the record IQ (until the next rt_process*, rt_extract*, rt_reset or rt_set_record_iq).
+ *   - RT_E_INVALID, before anything is launched or copied: all that rt_fetch_record_iq refuses, with its messages under this
+ *     entry's name; a null `n_cells`; a wrong n_offsets / n_first; rt_fetch_record_stft on a float64 handle and
+ *     rt_fetch_record_stft_f64 on a float32 one.  RT_E_NOMEM: the table or the value pool could not be allocated.
+ */
+int rt_fetch_record_stft(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                         float *values, size_t cap_cells, size_t *n_cells);      /* float32 handle */
+int rt_fetch_record_stft_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                             double *values, size_t cap_cells, size_t *n_cells); /* float64 handle */
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

@@ -168,6 +168,8 @@ ABI_SYMBOLS = (
     "rt_set_chain",
     "rt_set_record_iq",
     "rt_fetch_record_iq",
+    "rt_fetch_record_stft",
+    "rt_fetch_record_stft_f64",
 )
 
 _lib = None
@@ -242,6 +244,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_set_chain.argtypes = [vp, C.c_int32]
     lib.rt_set_record_iq.argtypes = [vp, C.c_int32]
     lib.rt_fetch_record_iq.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    for fn in (lib.rt_fetch_record_stft, lib.rt_fetch_record_stft_f64):
+        fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -576,6 +580,7 @@ class NativeAnalyzer:
         if rc != RT_OK and not (allow_truncated and rc == RT_E_CAPACITY):
             self._check(rc)
         self._n_fetched = len(out)
+        self._last_fetched = out  # (fetch_record_fine reads the records' start and end)
         return out
 
     def fetch_record_cells(self):
@@ -612,6 +617,22 @@ class NativeAnalyzer:
             self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, payload.ctypes.data,
                            payload.size, C.byref(n), C.byref(bps)))
         return offsets, first, payload, int(bps.value)
+
+    def fetch_record_stft(self):
+        """``rt_fetch_record_stft`` (``rt_fetch_record_stft_f64`` on a float64 handle): ``(offsets, first_segment, values)`` of
+        the call ``fetch`` delivered last (in full) -- ``offsets`` int64 ``[n_records + 1]`` in segments, ``first_segment`` int32
+        ``[n_records]``, ``values`` complex64 (complex128): the STFT value of record ``i``'s bin in each of the whole segments
+        ``first_segment[i] ... `` that ``fetch_record_iq`` delivers for it."""
+        n_rec = getattr(self, "_n_fetched", 0)
+        offsets = np.zeros(n_rec + 1, dtype=np.int64)
+        first = np.zeros(n_rec, dtype=np.int32)
+        n = C.c_size_t(0)
+        fn = self._lib.rt_fetch_record_stft_f64 if self.f64 else self._lib.rt_fetch_record_stft
+        self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, None, 0, C.byref(n)))
+        values = np.empty(n.value, dtype=np.complex128 if self.f64 else np.complex64)
+        if n.value:
+            self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, values.ctypes.data, values.size, C.byref(n)))
+        return offsets, first, values
 
     def fetch_row_means(self) -> np.ndarray:
         """``rt_fetch_row_means`` (``rt_fetch_row_means_f64`` on a float64 handle): ``[S, nperseg]`` float32 (float64), the

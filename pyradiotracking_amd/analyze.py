@@ -235,6 +235,41 @@ def _same_signal(a, b) -> bool:
         return False
 
 
+FINE_DTYPE = np.dtype([("offset_hz", np.float64), ("coherence", np.float64), ("n_pairs", np.int32)])
+
+
+def record_fine(offsets, first_segment, values, start, end, sample_rate: float, nperseg: int) -> np.ndarray:
+    """The pulse-pair estimate of :meth:`BatchSignalAnalyzer.fetch_record_fine` from what ``fetch_record_stft`` returns and the
+    records' ``start`` / ``end``: one ``FINE_DTYPE`` row per record.  Over the record's own cells -- the segments ``[start, end)``
+    that were delivered -- ``R = sum c[t + 1] * conj(c[t])``, ``offset_hz = angle(R) / (2 pi) * sample_rate / nperseg`` and
+    ``coherence = |R| / sum |c[t + 1]| |c[t]|``.  The pair (segment -1, segment 0) is never used: the predecessor buffer's
+    ragged remainder lies between the two.  A record with no pair left has NaN and ``n_pairs == 0``.  float64 arithmetic."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    first_segment = np.asarray(first_segment, dtype=np.int64)
+    n = len(first_segment)
+    out = np.zeros(n, dtype=FINE_DTYPE)
+    out["offset_hz"] = out["coherence"] = np.nan
+    v = np.asarray(values).astype(np.complex128)
+    if n == 0 or v.size < 2:
+        return out
+    rec = np.repeat(np.arange(n), np.diff(offsets))  # the record of every delivered cell
+    seg = np.arange(v.size) - offsets[rec] + first_segment[rec]  # ... and its segment
+    own = (seg >= np.asarray(start, dtype=np.int64)[rec]) & (seg < np.asarray(end, dtype=np.int64)[rec])
+    pair = own[:-1] & own[1:] & (rec[:-1] == rec[1:]) & (seg[:-1] != -1)
+    at = rec[:-1][pair]
+    prod = (v[1:] * np.conj(v[:-1]))[pair]
+    mag = (np.abs(v[1:]) * np.abs(v[:-1]))[pair]
+    R = np.bincount(at, weights=prod.real, minlength=n) + 1j * np.bincount(at, weights=prod.imag, minlength=n)
+    M = np.bincount(at, weights=mag, minlength=n)
+    cnt = np.bincount(at, minlength=n)
+    has = cnt > 0
+    out["n_pairs"] = cnt
+    out["offset_hz"][has] = np.angle(R[has]) / (2.0 * np.pi) * float(sample_rate) / int(nperseg)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["coherence"][has] = np.abs(R[has]) / M[has]
+    return out
+
+
 def default_lanes(fft_nperseg: int, n_streams: int) -> int:
     """Stream groups per GPU (``rt_config.lanes``) that measured best: three up to nperseg 512 while the launches of a group are
     small enough to have ends worth filling by another group's kernels (fewer than 16 384 streams on the GPU) -- config 2 +14 % with
@@ -881,6 +916,31 @@ class BatchSignalAnalyzer:
         assert len(samples) == offsets[-1]
         return offsets, first, samples
 
+    def fetch_record_stft(self):
+        """``(offsets, first_segment, values)``: one complex STFT value per delivered segment of every record of the call
+        :meth:`fetch_records` (or :meth:`process_batch`) returned last -- the value of the RECORD'S bin, complex64 (complex128 with
+        ``precision="float64"``).  ``values[offsets[i]:offsets[i + 1]]`` belong to the whole segments ``first_segment[i] ...`` that
+        :meth:`fetch_record_iq` delivers for record ``i`` (margin included), so ``offsets`` is that method's divided by
+        ``fft_nperseg``.  A value is ``scipy.signal.spectrogram(..., noverlap=0, return_onesided=False, mode='complex')`` at that
+        bin and segment: ``sqrt(scale) * sum w[n] (x[n] - mean(x)) exp(-2 pi i fi n / N)``; ``abs(value) ** 2`` is the cell
+        :meth:`fetch_record_cells` returns, the phase is what the detection drops.  Computed on the device from the gathered
+        snippets, at the first call after a fetch; ``fft_nperseg`` times fewer bytes than the samples.
+        Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is."""
+        return self._native.fetch_record_stft()
+
+    def fetch_record_fine(self) -> np.ndarray:
+        """One row per record of the call returned last (``FINE_DTYPE``: ``offset_hz``, ``coherence``, ``n_pairs``): the
+        pulse-pair estimate of the tone's offset from its bin centre, from the values of the record's own cells (``[start, end)``
+        clipped to what was delivered; :func:`record_fine`).  ``frequency + offset_hz`` refines a signal's frequency;
+        ``coherence`` is 1 for a pure tone and falls with noise or modulation.  The estimate is unambiguous within half a bin
+        either side (``|offset_hz| <= sample_rate / (2 fft_nperseg)``): a tone further off shows in the neighbouring bin's record
+        too, so it is meaningful for the record the shadow filter keeps, the one whose bin the tone is nearest to.  The pair
+        across a buffer boundary (segments -1 and 0) is left out; a record with fewer than two usable cells has NaN.
+        Needs ``record_iq=True``."""
+        offsets, first, values = self._native.fetch_record_stft()
+        rec = self._native._last_fetched
+        return record_fine(offsets, first, values, rec["start"], rec["end"], self.sample_rate, self.fft_nperseg)
+
     def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
         """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
         reference's noise figure (analyze.py:373-375) -- over the buffer of the call :meth:`fetch_records` (or
@@ -1007,6 +1067,7 @@ class SignalAnalyzer:
         self.record_iq = bool(record_iq)
         self.record_iq_margin = int(record_iq_margin)
         self.signal_iq: Optional[List[np.ndarray]] = None
+        self.signal_stft: Optional[List[np.ndarray]] = None  # (beside signal_iq: the complex STFT values of each signal's bin)
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -1131,7 +1192,7 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = self.signal_iq = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
         self._batch.enqueue_bytes(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1155,7 +1216,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = self.signal_iq = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
         self._batch.enqueue_int16(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1179,7 +1240,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = self.signal_iq = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
         self._batch.enqueue_int8(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1194,7 +1255,7 @@ class SignalAnalyzer:
         buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = self.signal_iq = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
         if self.record_cells or self.record_iq:  # (process_batch, with the records kept for the cells' shadow flags)
             self._batch.enqueue(buf)
             rec = self._batch.fetch_records()
@@ -1210,7 +1271,8 @@ class SignalAnalyzer:
         )
         return out
 
-    def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False):
+    def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False,
+               record_stft: bool = False):
         """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
         instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
         (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
@@ -1219,7 +1281,11 @@ class SignalAnalyzer:
         shorter than a buffer is one more call if it holds at least two segments, else it is dropped with a log line (nothing
         could be detected in it).  Every replay starts without look-back; the analyzer's own callback state is left alone.
         ``record_iq=True``: returns ``(signals, signal_iq)`` -- beside every signal its samples, as the per-buffer callbacks of an
-        analyzer made with ``record_iq=True`` (and this analyzer's ``record_iq_margin``) leave them in ``signal_iq``."""
+        analyzer made with ``record_iq=True`` (and this analyzer's ``record_iq_margin``) leave them in ``signal_iq``.
+        ``record_stft=True`` (with ``record_iq=True``): returns ``(signals, signal_iq, signal_stft)``, the complex STFT values of
+        each signal's bin as well (:meth:`BatchSignalAnalyzer.fetch_record_stft`)."""
+        if record_stft and not record_iq:
+            raise ValueError("record_stft needs record_iq=True")
         per_sample = {"c64": 1, "u8": 2, "i16": 2, "i8": 2}[fmt]
         want = {"c64": np.complex64, "u8": np.uint8, "i16": np.int16, "i8": np.int8}[fmt]
         x = np.asarray(samples).reshape(-1)
@@ -1245,6 +1311,7 @@ class SignalAnalyzer:
         step = datetime.timedelta(seconds=B / self.sample_rate)  # analyze.py:205
         out: List[Signal] = []
         out_iq: List[np.ndarray] = []
+        out_stft: List[np.ndarray] = []
 
         def call(first: int, links: int, length: int):
             part = x[first * B * per_sample:(first * B + links * length) * per_sample]
@@ -1253,6 +1320,9 @@ class SignalAnalyzer:
             if record_iq:  # (records come by link, i.e. in time order: the kept ones line up with the signals below)
                 offsets, _, got = batch.fetch_record_iq()
                 out_iq.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
+            if record_stft:
+                offsets, _, got = batch.fetch_record_stft()
+                out_stft.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
             out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
 
         for first in range(0, n_full, L):
@@ -1262,6 +1332,8 @@ class SignalAnalyzer:
         elif rest:
             logger.info(f"SDR {self.device} replay: the last {rest} samples hold fewer than two segments and are dropped")
         [self.consume_signal(s) for s in out]
+        if record_stft:
+            return out, out_iq, out_stft
         return (out, out_iq) if record_iq else out
 
     def _keep_noise(self):
@@ -1276,6 +1348,8 @@ class SignalAnalyzer:
         if self.record_iq:
             offsets, _, samples = self._batch.fetch_record_iq()
             self.signal_iq = [samples[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
+            offsets, _, values = self._batch.fetch_record_stft()
+            self.signal_stft = [values[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
 
     def reset(self):
         self._batch.reset()
@@ -1297,7 +1371,7 @@ class SignalAnalyzer:
         dense detect kernel (``rt_extract``).  The time axis must be the one
         SciPy produces for ``fft_nperseg`` / ``sample_rate`` (hop = nperseg/fs);
         ``freqs`` is used as given."""
-        self.noise_dbw = self.signal_data = self.signal_iq = None  # (the caller holds this map: no row means, no cells of it)
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None  # (the caller holds this map: no row means, no cells of it)
         spec = np.asarray(spectrogram)
         n_bins, n_seg = spec.shape
         if n_seg == 0:

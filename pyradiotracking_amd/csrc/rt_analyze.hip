@@ -26,6 +26,7 @@
 #include <limits>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rt_kernels.h"
@@ -37,6 +38,8 @@
 #include "rt_present.h"
 #include "rt_chain.h"
 #include "rt_record_iq.h"
+#include "rt_record_stft.h"
+#include "rt_record_stft_book.h"
 #include "rt_ledger.h"
 #include "rt_tables.h"
 
@@ -245,6 +248,15 @@ struct IqSlot {
     int bps = 0;                                     // bytes per sample of the delivered call
     int state = RT_OK;                               // what the gather left: RT_OK, RT_E_NOMEM, RT_E_HIP
     std::string why;
+    // rt_fetch_record_stft (rt_record_stft.h): what the gather notes for it, and what the entry's first call for this delivered
+    // call leaves -- nothing below is allocated, uploaded or launched unless that entry is called
+    std::vector<int32_t> fi;                         // [records] the records' bins
+    int fmt = kFmtC64;                               // the delivered call's input format (bps does not tell uint8 from int8)
+    bool stft_done = false;                          // d_vals holds the delivered call's values
+    char *d_vals = nullptr;                          // [offsets.back() / N] cf, or cd on a float64 handle
+    size_t vals_bytes = 0;
+    char *d_work = nullptr;                          // StftWork: the prefix, then the bins
+    size_t work_bytes = 0;
 };
 struct RecordIq {
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
@@ -253,6 +265,8 @@ struct RecordIq {
     hipStream_t s_gather = nullptr;  // the gather's own stream: a fetch must not queue behind the next call's scan
     IqSlot slot[kSlots];
     int delivered = kIqNone;   // the slot whose snippets rt_fetch_record_iq hands out, or kIq*
+    void *d_stft_tw = nullptr;   // [N] cf / cd: record_stft's twiddles, made by the first rt_fetch_record_stft
+    float *d_stft_win = nullptr; // [N] float32 handle: the window as the caller gave it (a float64 handle's is F64State::d_window)
 };
 
 }  // namespace
@@ -349,6 +363,7 @@ struct rt_handle {
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
     RecordIq *riq = nullptr;  // rt_set_record_iq (float32 and float64 handles; a laned handle: its lanes hold theirs)
     int iq_margin = -1;       // ... the margin in force, -1: off (the one thing a laned handle keeps itself)
+    std::vector<float> h_window;  // float32 handle: rt_config.window as given (the scans' d_window is times sqrt(scale)): rt_fetch_record_stft uploads it at first need
 };
 
 namespace {
@@ -1390,6 +1405,10 @@ void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_
     qs.bps = bps;
     qs.offsets.assign(n + 1, 0);
     qs.first_seg.assign(n, 0);
+    qs.fmt = call.fmt;
+    qs.stft_done = false;
+    qs.fi.resize(n);
+    for (size_t i = 0; i < n; ++i) qs.fi[i] = reinterpret_cast<const int32_t *>(static_cast<const char *>(rec) + i * rec_stride)[1];
     std::vector<IqDesc> descs;
     const int64_t total = iq_build_descs(call, N, rec, rec_stride, n, qs.offsets.data(), qs.first_seg.data(), &descs);
     if (descs.empty()) return;
@@ -1459,11 +1478,211 @@ void iq_free(rt_handle *h) {
         (void)hipFree(qs.d_pool);
         (void)hipHostFree(qs.h_descs);
         (void)hipFree(qs.d_descs);
+        (void)hipFree(qs.d_vals);
+        (void)hipFree(qs.d_work);
     }
+    (void)hipFree(q->d_stft_tw);
+    (void)hipFree(q->d_stft_win);
     (void)hipFree(q->d_tails);
     if (q->s_gather) (void)hipStreamDestroy(q->s_gather);
     delete q;
     h->riq = nullptr;
+}
+
+// rt_fetch_record_iq and rt_fetch_record_stft hand out the same delivered call: the lanes that hold it, and what each refuses --
+// `entry` names the caller in the message.  *records, *samples: over all lanes; *bps: of the delivered call.
+int iq_delivered_call(rt_handle *h, const char *entry, std::vector<rt_handle *> *lanes, size_t *records, size_t *samples, int *bps) {
+    const auto refuse = [&](const char *why) {
+        h->err = std::string(entry) + ": " + why;
+        return RT_E_INVALID;
+    };
+    if (h->iq_margin < 0) return refuse("rt_set_record_iq has not turned the feature on");
+    if (h->kids.empty()) lanes->assign(1, h);
+    else *lanes = h->kids;
+    // every lane holds the samples of its streams' records: all of them are checked and counted before anything is written
+    *records = *samples = 0;
+    *bps = 0;
+    for (rt_handle *l : *lanes) {
+        const int d = l->riq ? l->riq->delivered : kIqNone;
+        if (d == kIqExtract) return refuse("the call fetched last was an rt_extract: it has no samples");
+        if (d == kIqTruncated) return refuse("the call fetched last was delivered truncated");
+        if (d == kIqOff) return refuse("the call fetched last was enqueued before the feature was turned on");
+        if (d < 0) return refuse("no samples: no call delivered by rt_fetch since the last rt_process*, rt_extract, rt_reset or rt_set_record_iq");
+        const IqSlot &qs = l->riq->slot[d];
+        if (qs.state != RT_OK) {
+            h->err = std::string(entry) + ": " + qs.why;
+            return qs.state;
+        }
+        *records += qs.first_seg.size();
+        *samples += (size_t)qs.offsets.back();
+        *bps = qs.bps;
+    }
+    return RT_OK;
+}
+
+// ---- rt_fetch_record_stft: one complex STFT value per delivered segment (rt_record_stft.h; the work list: rt_record_stft_book.h) ----
+template <class P, int FMT>
+void launch_record_stft(const StftArgs<P> &a, hipStream_t st) {
+    const int64_t blocks = (a.n_segs + kStftWaves - 1) / kStftWaves;
+    hipLaunchKernelGGL((record_stft<P, FMT>), dim3((unsigned)blocks), dim3(kStftBlock), 0, st, a);
+}
+
+// The values of lane-less handle `l`'s delivered call into its slot's value pool, once per delivered call: the twiddle table and
+// (float32) the window go to the device with the first call of the entry on the handle, the value pool grows on demand like the
+// byte pool, the kernel runs on the gather's stream and is waited for.  The error text goes to `h` (the handle the caller holds).
+template <class P>
+int record_stft_run(rt_handle *h, rt_handle *l, const char *entry) {
+    using C = typename stft_types<P>::C;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    if (qs.stft_done) return RT_OK;
+    const int N = iq_nperseg(l);
+    const size_t n = qs.first_seg.size();
+    StftWork work;
+    const int64_t cells = stft_build_work(qs.offsets.data(), qs.fi.data(), n, N, &work);
+    if (cells < 0 || (uint64_t)cells * (uint64_t)N * (uint64_t)qs.bps > qs.pool_bytes || (cells > 0 && !qs.d_pool) ||
+        (cells + kStftWaves - 1) / kStftWaves > 0x7fffffffll) {
+        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+        return RT_E_HIP;
+    }
+    if (cells == 0) {
+        qs.stft_done = true;
+        return RT_OK;
+    }
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    const auto nomem = [&](const char *what, size_t bytes) {
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
+        return RT_E_NOMEM;
+    };
+    if (!q.d_stft_tw) {
+        const std::vector<C> tw = record_stft_twiddles<C, typename std::conditional<sizeof(P) == 4, double, long double>::type>(N);
+        void *d = nullptr;
+        if (hipMalloc(&d, tw.size() * sizeof(C)) != hipSuccess) return nomem("the twiddle table", tw.size() * sizeof(C));
+        if (hipMemcpy(d, tw.data(), tw.size() * sizeof(C), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            h->err = std::string(entry) + ": uploading the twiddle table failed";
+            return RT_E_HIP;
+        }
+        q.d_stft_tw = d;
+    }
+    if (!l->f64 && !q.d_stft_win) {
+        float *d = nullptr;
+        if (hipMalloc(&d, (size_t)N * sizeof(float)) != hipSuccess) return nomem("the window", (size_t)N * sizeof(float));
+        if (hipMemcpy(d, l->h_window.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            h->err = std::string(entry) + ": uploading the window failed";
+            return RT_E_HIP;
+        }
+        q.d_stft_win = d;
+    }
+    const size_t val_bytes = (size_t)cells * sizeof(C);
+    if (qs.vals_bytes < val_bytes) {
+        (void)hipFree(qs.d_vals);
+        qs.d_vals = nullptr;
+        const size_t want = std::max(val_bytes, std::max(qs.vals_bytes * 2, (size_t)1 << 16));
+        qs.vals_bytes = 0;
+        if (hipMalloc(&qs.d_vals, want) != hipSuccess) {
+            (void)hipGetLastError();
+            if (want == val_bytes || hipMalloc(&qs.d_vals, val_bytes) != hipSuccess) return nomem("the call's values", val_bytes);
+            qs.vals_bytes = val_bytes;
+        } else {
+            qs.vals_bytes = want;
+        }
+    }
+    const size_t prefix_bytes = (n + 1) * sizeof(int64_t), work_bytes = prefix_bytes + n * sizeof(int32_t);
+    if (qs.work_bytes < work_bytes) {
+        (void)hipFree(qs.d_work);
+        qs.d_work = nullptr;
+        qs.work_bytes = 0;
+        const size_t want = std::max(work_bytes, (size_t)1 << 16);
+        if (hipMalloc(&qs.d_work, want) != hipSuccess) return nomem("the work list", want);
+        qs.work_bytes = want;
+    }
+    StftArgs<P> a{};
+    a.pool = qs.d_pool;
+    a.seg_first = reinterpret_cast<const int64_t *>(qs.d_work);
+    a.fi = reinterpret_cast<const int32_t *>(qs.d_work + prefix_bytes);
+    a.n_records = (int32_t)n;
+    a.nperseg = N;
+    a.n_segs = cells;
+    a.tw = static_cast<const C *>(q.d_stft_tw);
+    a.values = reinterpret_cast<C *>(qs.d_vals);
+    if constexpr (sizeof(P) == 4) {
+        a.window = q.d_stft_win;
+        a.root = stft_root_f32(l->cfg.scale);
+    } else {
+        a.window = l->f64->d_window;
+        a.root = stft_root_f64(l->f64->c.scale);
+    }
+    // (pageable sources: `work` lives until the stream has been waited for below)
+    hipError_t e = hipMemcpyAsync(qs.d_work, work.seg_first.data(), prefix_bytes, hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) e = hipMemcpyAsync(qs.d_work + prefix_bytes, work.fi.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        if (qs.fmt == kFmtU8) launch_record_stft<P, kFmtU8>(a, q.s_gather);
+        else if (qs.fmt == kFmtI16) launch_record_stft<P, kFmtI16>(a, q.s_gather);
+        else if (qs.fmt == kFmtI8) launch_record_stft<P, kFmtI8>(a, q.s_gather);
+        else launch_record_stft<P, kFmtC64>(a, q.s_gather);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s_gather);  // (`work` must outlive whatever copy did start)
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": record_stft: " + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    qs.stft_done = true;
+    return RT_OK;
+}
+
+template <class P>
+int fetch_record_stft_impl(rt_handle *h, const char *entry, const char *twin, int64_t *offsets, size_t n_offsets, int32_t *first_seg,
+                                  size_t n_first, P *values, size_t cap_cells, size_t *n_cells) {
+    using C = typename stft_types<P>::C;
+    if (!h || !n_cells) return RT_E_INVALID;
+    *n_cells = 0;
+    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
+        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
+        return RT_E_INVALID;
+    }
+    std::vector<rt_handle *> lanes;
+    size_t records = 0, samples = 0;
+    int bps = 0;
+    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
+        h->err = std::string(entry) + ": n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
+        return RT_E_INVALID;
+    }
+    const size_t N = (size_t)iq_nperseg(h);
+    *n_cells = samples / N;
+    const bool query = !values || cap_cells == 0;
+    if (!query && cap_cells < *n_cells) {
+        h->err = std::string(entry) + ": output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    if (!query)
+        for (rt_handle *l : lanes) {
+            const int rs = record_stft_run<P>(h, l, entry);
+            if (rs != RT_OK) return rs;
+        }
+    size_t r0 = 0, c0 = 0;
+    if (offsets) offsets[0] = 0;
+    for (rt_handle *l : lanes) {
+        const IqSlot &qs = l->riq->slot[l->riq->delivered];
+        const size_t n = qs.first_seg.size(), mine = (size_t)qs.offsets.back() / N;
+        if (offsets)
+            for (size_t i = 0; i < n; ++i) offsets[r0 + i + 1] = (int64_t)c0 + qs.offsets[i + 1] / (int64_t)N;
+        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
+        if (!query && mine) {
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(values + 2 * c0, qs.d_vals, mine * sizeof(C), hipMemcpyDeviceToHost));
+        }
+        r0 += n;
+        c0 += mine;
+    }
+    return RT_OK;
 }
 
 int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
@@ -1896,6 +2115,7 @@ int rt_create(const rt_config *cfg, rt_handle **out) {
     if (!h) return fail_create(RT_E_NOMEM, "out of host memory");
     h->cfg = *cfg;
     h->cfg.window = nullptr;
+    h->h_window.assign(cfg->window, cfg->window + cfg->nperseg);
     h->R3 = R3;
     h->big = big;
     h->QS = QS;
@@ -3284,33 +3504,15 @@ int rt_fetch_record_iq(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t
     if (!h || !n_bytes || !bytes_per_sample) return RT_E_INVALID;
     *n_bytes = 0;
     *bytes_per_sample = 0;
-    const auto refuse = [&](const char *why) {
-        h->err = std::string("rt_fetch_record_iq: ") + why;
-        return RT_E_INVALID;
-    };
-    if (h->iq_margin < 0) return refuse("rt_set_record_iq has not turned the feature on");
-    std::vector<rt_handle *> one{h};
-    const std::vector<rt_handle *> &lanes = h->kids.empty() ? one : h->kids;
-    // every lane holds the samples of its streams' records: all of them are checked and counted before anything is written
+    std::vector<rt_handle *> lanes;
     size_t records = 0, samples = 0;
     int bps = 0;
-    for (rt_handle *l : lanes) {
-        const int d = l->riq ? l->riq->delivered : kIqNone;
-        if (d == kIqExtract) return refuse("the call fetched last was an rt_extract: it has no samples");
-        if (d == kIqTruncated) return refuse("the call fetched last was delivered truncated");
-        if (d == kIqOff) return refuse("the call fetched last was enqueued before the feature was turned on");
-        if (d < 0) return refuse("no samples: no call delivered by rt_fetch since the last rt_process*, rt_extract, rt_reset or rt_set_record_iq");
-        const IqSlot &qs = l->riq->slot[d];
-        if (qs.state != RT_OK) {
-            h->err = "rt_fetch_record_iq: " + qs.why;
-            return qs.state;
-        }
-        records += qs.first_seg.size();
-        samples += (size_t)qs.offsets.back();
-        bps = qs.bps;
+    const int rc = iq_delivered_call(h, "rt_fetch_record_iq", &lanes, &records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
+        h->err = "rt_fetch_record_iq: n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
+        return RT_E_INVALID;
     }
-    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records))
-        return refuse("n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number");
     *n_bytes = samples * (size_t)bps;
     *bytes_per_sample = bps;
     const bool query = !iq || cap_bytes == 0;
@@ -3335,6 +3537,16 @@ int rt_fetch_record_iq(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t
         s0 += mine;
     }
     return RT_OK;
+}
+
+int rt_fetch_record_stft(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, float *values, size_t cap_cells,
+                         size_t *n_cells) {
+    return fetch_record_stft_impl<float>(h, "rt_fetch_record_stft", "rt_fetch_record_stft_f64", offsets, n_offsets, first_seg, n_first, values, cap_cells, n_cells);
+}
+
+int rt_fetch_record_stft_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, double *values,
+                             size_t cap_cells, size_t *n_cells) {
+    return fetch_record_stft_impl<double>(h, "rt_fetch_record_stft_f64", "rt_fetch_record_stft", offsets, n_offsets, first_seg, n_first, values, cap_cells, n_cells);
 }
 
 int rt_get_call_info(rt_handle *h, rt_call_info *info) {

@@ -16,6 +16,7 @@
 #include "../../include/rt_analyze.h"
 #include "rt_core.h"
 #include "rt_ledger.h"
+#include "rt_record_stft_book.h"
 #include "rt_tables.h"
 
 using namespace rt;
@@ -735,6 +736,33 @@ int hc_extract_rescue_f64(const double *spec, const double *row_sums, int n_seg,
     }
     for (int i = 0; i < m && i < cap; ++i) out[i] = ordered[(size_t)i];
     return m;
+}
+
+}  // extern "C"
+
+// ---- rt_fetch_record_stft: the work list, the twiddle table and sqrt(scale) (rt_record_stft_book.h, rt_tables.h) ----
+extern "C" {
+
+// offsets [n + 1] (samples) and fi [n] -> seg_first [n + 1], fi_out [n]; returns the delivered segments, -1: refused
+long long hc_stft_work(const int64_t *offsets, const int32_t *fi, long long n, int nperseg, int64_t *seg_first, int32_t *fi_out) {
+    StftWork w;
+    const int64_t cells = stft_build_work(offsets, fi, (size_t)n, nperseg, &w);
+    if (cells < 0) return -1;
+    std::copy(w.seg_first.begin(), w.seg_first.end(), seg_first);
+    std::copy(w.fi.begin(), w.fi.end(), fi_out);
+    return (long long)cells;
+}
+int hc_stft_record_of(const int64_t *seg_first, int n, long long g) { return stft_record_of(seg_first, n, (int64_t)g); }
+float hc_stft_root_f32(float scale) { return stft_root_f32(scale); }
+double hc_stft_root_f64(double scale) { return stft_root_f64(scale); }
+// out: [nperseg] interleaved (re, im)
+void hc_stft_twiddles_f32(int nperseg, float *out) {
+    const std::vector<cf> tw = record_stft_twiddles<cf, double>(nperseg);
+    std::memcpy(out, tw.data(), tw.size() * sizeof(cf));
+}
+void hc_stft_twiddles_f64(int nperseg, double *out) {
+    const std::vector<cd> tw = record_stft_twiddles<cd, long double>(nperseg);
+    std::memcpy(out, tw.data(), tw.size() * sizeof(cd));
 }
 
 }  // extern "C"

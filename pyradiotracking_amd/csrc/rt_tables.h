@@ -165,6 +165,19 @@ std::vector<Out> transform_twiddles(int M) {
     return tw;
 }
 
+// W_N^j = exp(-2 pi i j / N) for every j < N (StftArgs::tw, rt_record_stft.h: record_stft reads entry (fi * n) mod N, reduced in
+// integers, for bin fi and sample n -- any N, a power of two or not)
+template <class Out, class Wide>
+std::vector<Out> record_stft_twiddles(int N) {
+    using S = decltype(Out{}.x);
+    std::vector<Out> tw((size_t)N);
+    for (int j = 0; j < N; ++j) {
+        const Wide ang = (Wide)-2 * pi_of<Wide>() * (Wide)j / (Wide)N;
+        tw[(size_t)j] = Out{(S)std::cos(ang), (S)std::sin(ang)};
+    }
+    return tw;
+}
+
 // FFT_M in place (iterative radix-2: bit reversal, then log2 M stages)
 template <class Wide>
 void host_fft(std::vector<Wide> &re, std::vector<Wide> &im) {
