@@ -665,6 +665,45 @@ int rt_fetch_record_stft(rt_handle *h, int64_t *offsets, size_t n_offsets, int32
 int rt_fetch_record_stft_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
                              double *values, size_t cap_cells, size_t *n_cells); /* float64 handle */
 
+/*
+ * ---- record STFT at a sub-segment hop: one complex value per FRAME (additive within ABI version 6) ----
+ * rt_fetch_record_stft's values lie a whole segment apart, so a phase advance between them gives a frequency only within half a
+ * bin, and an edge only to a segment.  This entry delivers the same single-bin transform for frames every h = N / k samples
+ * (N = nperseg, k = hop_div): the advance between frames is 2 pi delta / k for a tone delta bins off the centre, and the
+ * amplitude is sampled k times a segment.  A frame is a segment that starts elsewhere.
+ *   - `hop_div`: 1 <= k <= 16 and N % k == 0; anything else is RT_E_INVALID, the message names k and N, and it is refused before
+ *     anything is launched or copied.
+ *   - the call, the records and `first_seg` are exactly those of rt_fetch_record_stft: record i has the delivered segments
+ *     first_seg[i] ... last_i.  Its PREDECESSOR PART are the Lp segments below 0 (Lp = clamp(-first_seg[i], 0, L) of its L
+ *     delivered segments), its OWN PART the Lc = L - Lp from 0 on.
+ *   - frames: a part of L >= 1 segments has (L - 1) * k + 1 frames, frame j the N samples from sample j * h of the part; a part
+ *     of no segment has none.  A record delivers its predecessor part's frames, then its own part's.  No frame straddles the two
+ *     parts, on any handle kind, also where the predecessor buffer left no ragged remainder: one rule.
+ *   - `offsets`: HOST memory, n_offsets == n_records + 1 entries (or NULL), counting FRAMES.  *n_frames == offsets[n_records].
+ *   - `values`: HOST memory, cap_frames interleaved (re, im) pairs.  values == NULL or cap_frames == 0: a size query.
+ *     cap_frames < *n_frames with a buffer: RT_E_CAPACITY, nothing written.
+ *   - a value is rt_fetch_record_stft's formula on the frame's N samples x[0 .. N): the same conversions, window, sqrt(scale),
+ *     bin fi and mean (over the frame), the phase reference frame-local:
+ *         value = sqrt(scale) * sum_n w[n] * (x[n] - mean(x)) * exp(-2 pi i fi n / N)        n from the frame's start
+ *     i.e. scipy.signal.spectrogram(part, nperseg=N, noverlap=N - h, detrend='constant', return_onesided=False,
+ *     mode='complex')[fi, j].  (The bin's own rotation over a hop, exp(2 pi i fi / k), is left in between consecutive frames.)
+ *   - bit identity: frame j with j % k == 0 is a delivered segment, and its value is the bytes rt_fetch_record_stft gives for
+ *     that segment; with k == 1 the whole output is that entry's.  A value depends on the frame's samples and the bin alone: the
+ *     same samples give the same bytes on every handle kind, on every fetch and in every order of calls.  A frame whose samples
+ *     are all one finite value is exactly 0 + 0i; a non-finite sample makes exactly the frames that cover it non-finite.
+ *   - lazy: rt_process*, rt_fetch and rt_fetch_record_stft allocate, copy and launch what they do without this entry.  The
+ *     entry's first call for a delivered call builds the values for that k in a pool of its own per call slot (it grows on
+ *     demand, is separate from rt_fetch_record_stft's and remembers the k it holds), by one kernel on the gather's stream, waited
+ *     for.  A repeated call with the same k copies; another k builds again.  The twiddle table and the float32 window copy are
+ *     the ones rt_fetch_record_stft uses, made by whichever of the two entries is called first.
+ *   - size query, RT_E_CAPACITY, validity, RT_E_NOMEM and every refusal: rt_fetch_record_stft's, under this entry's name; the
+ *     wrong twin is refused too.
+ */
+int rt_fetch_record_stft_hop(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                             float *values, size_t cap_frames, size_t *n_frames);      /* float32 handle */
+int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                                 double *values, size_t cap_frames, size_t *n_frames); /* float64 handle */
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

@@ -170,6 +170,8 @@ ABI_SYMBOLS = (
     "rt_fetch_record_iq",
     "rt_fetch_record_stft",
     "rt_fetch_record_stft_f64",
+    "rt_fetch_record_stft_hop",
+    "rt_fetch_record_stft_hop_f64",
 )
 
 _lib = None
@@ -246,6 +248,8 @@ def load_library(path: Optional[str] = None):
     lib.rt_fetch_record_iq.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     for fn in (lib.rt_fetch_record_stft, lib.rt_fetch_record_stft_f64):
         fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    for fn in (lib.rt_fetch_record_stft_hop, lib.rt_fetch_record_stft_hop_f64):
+        fn.argtypes = [vp, C.c_int32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -618,16 +622,23 @@ class NativeAnalyzer:
                            payload.size, C.byref(n), C.byref(bps)))
         return offsets, first, payload, int(bps.value)
 
-    def fetch_record_stft(self):
+    def fetch_record_stft(self, hop_div: int = 1):
         """``rt_fetch_record_stft`` (``rt_fetch_record_stft_f64`` on a float64 handle): ``(offsets, first_segment, values)`` of
         the call ``fetch`` delivered last (in full) -- ``offsets`` int64 ``[n_records + 1]`` in segments, ``first_segment`` int32
         ``[n_records]``, ``values`` complex64 (complex128): the STFT value of record ``i``'s bin in each of the whole segments
-        ``first_segment[i] ... `` that ``fetch_record_iq`` delivers for it."""
+        ``first_segment[i] ... `` that ``fetch_record_iq`` delivers for it.  ``hop_div`` k > 1: ``rt_fetch_record_stft_hop``
+        (``_f64``), the values of the frames every ``nperseg / k`` samples, ``offsets`` in frames."""
         n_rec = getattr(self, "_n_fetched", 0)
         offsets = np.zeros(n_rec + 1, dtype=np.int64)
         first = np.zeros(n_rec, dtype=np.int32)
         n = C.c_size_t(0)
-        fn = self._lib.rt_fetch_record_stft_f64 if self.f64 else self._lib.rt_fetch_record_stft
+        if int(hop_div) != 1:
+            hop = self._lib.rt_fetch_record_stft_hop_f64 if self.f64 else self._lib.rt_fetch_record_stft_hop
+
+            def fn(*args):
+                return hop(args[0], int(hop_div), *args[1:])
+        else:
+            fn = self._lib.rt_fetch_record_stft_f64 if self.f64 else self._lib.rt_fetch_record_stft
         self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, None, 0, C.byref(n)))
         values = np.empty(n.value, dtype=np.complex128 if self.f64 else np.complex64)
         if n.value:

@@ -238,24 +238,64 @@ def _same_signal(a, b) -> bool:
 FINE_DTYPE = np.dtype([("offset_hz", np.float64), ("coherence", np.float64), ("n_pairs", np.int32)])
 
 
-def record_fine(offsets, first_segment, values, start, end, sample_rate: float, nperseg: int) -> np.ndarray:
+def _stft_frames(offsets, first_segment, nperseg: int, hop_div: int):
+    """``(record, in_predecessor_part, position)`` of every frame ``fetch_record_stft(hop_div)`` delivers.  A record with
+    ``first_segment < 0`` delivers its predecessor part first: all ``(-first_segment - 1) k + 1`` frames of it, or fewer where
+    the record ends inside it."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    first = np.asarray(first_segment, dtype=np.int64)
+    N, k = int(nperseg), int(hop_div)
+    if k < 1 or N % k:
+        raise ValueError(f"hop_div {k} must be >= 1 and divide nperseg {N}")
+    h = N // k
+    n = len(first)
+    rec = np.repeat(np.arange(n), np.diff(offsets))
+    j = np.arange(int(offsets[-1]) if len(offsets) else 0, dtype=np.int64) - offsets[rec]
+    lead = np.where(first < 0, np.minimum((-first - 1) * k + 1, np.diff(offsets)), 0)  # frames of the predecessor part
+    pred = j < lead[rec]
+    pos = np.where(pred, first[rec] * N + j * h, np.maximum(first[rec], 0) * N + (j - lead[rec]) * h)
+    return rec, pred, pos
+
+
+def stft_frame_positions(offsets, first_segment, nperseg: int, hop_div: int) -> np.ndarray:
+    """int64, one entry per frame of ``fetch_record_stft(hop_div)``: the frame's first sample relative to sample 0 of the call's
+    buffer.  Frames of a record's predecessor part are negative, counted back from the end of the predecessor buffer's last whole
+    segment as ``first_segment`` counts: segment ``-1`` starts at ``-nperseg``."""
+    return _stft_frames(offsets, first_segment, nperseg, hop_div)[2]
+
+
+def record_fine(offsets, first_segment, values, start, end, sample_rate: float, nperseg: int, hop_div: int = 1, fi=None) -> np.ndarray:
     """The pulse-pair estimate of :meth:`BatchSignalAnalyzer.fetch_record_fine` from what ``fetch_record_stft`` returns and the
     records' ``start`` / ``end``: one ``FINE_DTYPE`` row per record.  Over the record's own cells -- the segments ``[start, end)``
     that were delivered -- ``R = sum c[t + 1] * conj(c[t])``, ``offset_hz = angle(R) / (2 pi) * sample_rate / nperseg`` and
     ``coherence = |R| / sum |c[t + 1]| |c[t]|``.  The pair (segment -1, segment 0) is never used: the predecessor buffer's
-    ragged remainder lies between the two.  A record with no pair left has NaN and ``n_pairs == 0``.  float64 arithmetic."""
+    ragged remainder lies between the two.  A record with no pair left has NaN and ``n_pairs == 0``.  float64 arithmetic.
+
+    ``hop_div`` k > 1: ``values`` are the frames of ``fetch_record_stft(hop_div=k)`` and ``fi`` (required) the records' bins.
+    The pairs are consecutive frames of the same part that both lie wholly inside the record's own cells (``start * nperseg <=
+    position`` and ``position + nperseg <= end * nperseg``); ``R`` is turned back by the bin's own rotation over one hop,
+    ``exp(-2 pi i (fi mod k) / k)``, which the frame-local phase reference leaves in, and ``offset_hz = angle(R) / (2 pi) * k *
+    sample_rate / nperseg``: unambiguous within ``k / 2`` bins either side."""
     offsets = np.asarray(offsets, dtype=np.int64)
     first_segment = np.asarray(first_segment, dtype=np.int64)
     n = len(first_segment)
+    k = int(hop_div)
     out = np.zeros(n, dtype=FINE_DTYPE)
     out["offset_hz"] = out["coherence"] = np.nan
     v = np.asarray(values).astype(np.complex128)
+    if k != 1 and fi is None:
+        raise ValueError("record_fine with hop_div > 1 needs the records' bins (fi)")
     if n == 0 or v.size < 2:
         return out
-    rec = np.repeat(np.arange(n), np.diff(offsets))  # the record of every delivered cell
-    seg = np.arange(v.size) - offsets[rec] + first_segment[rec]  # ... and its segment
-    own = (seg >= np.asarray(start, dtype=np.int64)[rec]) & (seg < np.asarray(end, dtype=np.int64)[rec])
-    pair = own[:-1] & own[1:] & (rec[:-1] == rec[1:]) & (seg[:-1] != -1)
+    if k == 1:
+        rec = np.repeat(np.arange(n), np.diff(offsets))  # the record of every delivered cell
+        seg = np.arange(v.size) - offsets[rec] + first_segment[rec]  # ... and its segment
+        own = (seg >= np.asarray(start, dtype=np.int64)[rec]) & (seg < np.asarray(end, dtype=np.int64)[rec])
+        pair = own[:-1] & own[1:] & (rec[:-1] == rec[1:]) & (seg[:-1] != -1)
+    else:
+        rec, pred, pos = _stft_frames(offsets, first_segment, nperseg, k)
+        own = (pos >= np.asarray(start, dtype=np.int64)[rec] * int(nperseg)) & (pos + int(nperseg) <= np.asarray(end, dtype=np.int64)[rec] * int(nperseg))
+        pair = own[:-1] & own[1:] & (rec[:-1] == rec[1:]) & (pred[:-1] == pred[1:])
     at = rec[:-1][pair]
     prod = (v[1:] * np.conj(v[:-1]))[pair]
     mag = (np.abs(v[1:]) * np.abs(v[:-1]))[pair]
@@ -264,9 +304,51 @@ def record_fine(offsets, first_segment, values, start, end, sample_rate: float, 
     cnt = np.bincount(at, minlength=n)
     has = cnt > 0
     out["n_pairs"] = cnt
-    out["offset_hz"][has] = np.angle(R[has]) / (2.0 * np.pi) * float(sample_rate) / int(nperseg)
+    if k != 1:
+        R = R * np.exp(-2j * np.pi * (np.asarray(fi, dtype=np.int64) % k) / k)
+    out["offset_hz"][has] = np.angle(R[has]) / (2.0 * np.pi) * k * float(sample_rate) / int(nperseg)
     with np.errstate(divide="ignore", invalid="ignore"):
         out["coherence"][has] = np.abs(R[has]) / M[has]
+    return out
+
+
+def record_edges(offsets, first_segment, values, start, end, nperseg: int, hop_div: int) -> np.ndarray:
+    """float64 ``[n_records, 2]``: ``(rise, fall)`` of every record's pulse in samples relative to sample 0 of the call's buffer,
+    from the frames of ``fetch_record_stft(hop_div)``.  ``level`` is the median of ``|c|`` over the frames that lie wholly inside
+    the record's own cells (``start * nperseg <= position``, ``position + nperseg <= end * nperseg``).  ``rise``: from the first
+    such frame that reaches ``level / 2`` (the first of them, but for a pulse that is still rising there) back, within its part,
+    to the first frame with ``|c| < level / 2``; ``|c|`` is interpolated linearly between that frame and its successor, and half
+    a window, ``nperseg / 2``, is added: a frame's value weighs the samples about its centre.  ``fall``: the mirror image forward
+    from the last such frame.  NaN where the part ends before ``|c|`` falls below ``level / 2`` (margin 0, a pulse cut by the
+    buffer's end) and for a record without a frame inside its own cells."""
+    N, k = int(nperseg), int(hop_div)
+    rec, pred, pos = _stft_frames(offsets, first_segment, N, k)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    a = np.abs(np.asarray(values).astype(np.complex128))
+    start = np.asarray(start, dtype=np.int64)
+    end = np.asarray(end, dtype=np.int64)
+    out = np.full((n, 2), np.nan)
+    for i in range(n):
+        lo, hi = int(offsets[i]), int(offsets[i + 1])
+        ai, pi, parti = a[lo:hi], pos[lo:hi], pred[lo:hi]
+        inside = np.flatnonzero((pi >= start[i] * N) & (pi + N <= end[i] * N))
+        if not len(inside):
+            continue
+        half = 0.5 * float(np.median(ai[inside]))
+        if not half > 0:
+            continue
+        up = inside[ai[inside] >= half]
+        for col, q, step in ((0, int(up[0]), -1), (1, int(up[-1]), 1)):
+            part = parti[q]
+            q += step
+            while 0 <= q < len(ai) and parti[q] == part and not ai[q] < half:
+                q += step
+            if not (0 <= q < len(ai)) or parti[q] != part:
+                continue  # the part ends first
+            p = q - step  # the frame next to q on the pulse's side: |c| >= level / 2 there
+            t = (half - ai[q]) / (ai[p] - ai[q])
+            out[i, col] = pi[q] + t * (pi[p] - pi[q]) + 0.5 * N
     return out
 
 
@@ -916,7 +998,7 @@ class BatchSignalAnalyzer:
         assert len(samples) == offsets[-1]
         return offsets, first, samples
 
-    def fetch_record_stft(self):
+    def fetch_record_stft(self, hop_div: int = 1):
         """``(offsets, first_segment, values)``: one complex STFT value per delivered segment of every record of the call
         :meth:`fetch_records` (or :meth:`process_batch`) returned last -- the value of the RECORD'S bin, complex64 (complex128 with
         ``precision="float64"``).  ``values[offsets[i]:offsets[i + 1]]`` belong to the whole segments ``first_segment[i] ...`` that
@@ -925,10 +1007,24 @@ class BatchSignalAnalyzer:
         bin and segment: ``sqrt(scale) * sum w[n] (x[n] - mean(x)) exp(-2 pi i fi n / N)``; ``abs(value) ** 2`` is the cell
         :meth:`fetch_record_cells` returns, the phase is what the detection drops.  Computed on the device from the gathered
         snippets, at the first call after a fetch; ``fft_nperseg`` times fewer bytes than the samples.
-        Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is."""
-        return self._native.fetch_record_stft()
+        Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is.
 
-    def fetch_record_fine(self) -> np.ndarray:
+        ``hop_div`` k > 1 (``rt_fetch_record_stft_hop``; 2 ... 16, a divisor of ``fft_nperseg``): the same value for FRAMES every
+        ``fft_nperseg / k`` samples, ``offsets`` counting frames.  The delivered segments below 0 (the predecessor part) and those
+        from 0 on (the record's own part) are framed separately -- a part of ``L`` segments has ``(L - 1) k + 1`` frames, none
+        straddles the two -- and :func:`stft_frame_positions` gives every frame's first sample.  Every k-th frame of a part is a
+        delivered segment, with the bytes the default returns for it; the phase reference is the frame's own start."""
+        return self._native.fetch_record_stft(hop_div)
+
+    def fetch_record_edges(self, hop_div: int = 4) -> np.ndarray:
+        """float64 ``[n_records, 2]``: ``(rise, fall)`` of every record's pulse in samples relative to sample 0 of the buffer of
+        the call returned last, to a fraction of ``fft_nperseg / hop_div`` where the pulse is switched and the delivered margin
+        holds the edge (``record_iq_margin >= 1``); NaN otherwise (:func:`record_edges`).  Needs ``record_iq=True``."""
+        offsets, first, values = self._native.fetch_record_stft(hop_div)
+        rec = self._native._last_fetched
+        return record_edges(offsets, first, values, rec["start"], rec["end"], self.fft_nperseg, hop_div)
+
+    def fetch_record_fine(self, hop_div: int = 1) -> np.ndarray:
         """One row per record of the call returned last (``FINE_DTYPE``: ``offset_hz``, ``coherence``, ``n_pairs``): the
         pulse-pair estimate of the tone's offset from its bin centre, from the values of the record's own cells (``[start, end)``
         clipped to what was delivered; :func:`record_fine`).  ``frequency + offset_hz`` refines a signal's frequency;
@@ -936,10 +1032,11 @@ class BatchSignalAnalyzer:
         either side (``|offset_hz| <= sample_rate / (2 fft_nperseg)``): a tone further off shows in the neighbouring bin's record
         too, so it is meaningful for the record the shadow filter keeps, the one whose bin the tone is nearest to.  The pair
         across a buffer boundary (segments -1 and 0) is left out; a record with fewer than two usable cells has NaN.
+        ``hop_div`` k > 1: from the frames of ``fetch_record_stft(hop_div=k)``, unambiguous within ``k / 2`` bins either side.
         Needs ``record_iq=True``."""
-        offsets, first, values = self._native.fetch_record_stft()
+        offsets, first, values = self._native.fetch_record_stft(hop_div)
         rec = self._native._last_fetched
-        return record_fine(offsets, first, values, rec["start"], rec["end"], self.sample_rate, self.fft_nperseg)
+        return record_fine(offsets, first, values, rec["start"], rec["end"], self.sample_rate, self.fft_nperseg, hop_div, rec["fi"])
 
     def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
         """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
@@ -1044,11 +1141,14 @@ class SignalAnalyzer:
         f64_rescue: bool = False,
         record_iq: bool = False,
         record_iq_margin: int = 0,
+        stft_hop_div: int = 1,
         **kwargs,
     ):
         """``record_iq=True``: after every buffer ``signal_iq`` is the list of the sample arrays of the signals put on the queue
         (unshadowed, queue order, like ``signal_data``) -- the IQ of each pulse in the format the buffer came in, with
-        ``record_iq_margin`` whole segments on either side (:meth:`BatchSignalAnalyzer.fetch_record_iq`).
+        ``record_iq_margin`` whole segments on either side (:meth:`BatchSignalAnalyzer.fetch_record_iq`), and ``signal_stft`` the
+        list of their complex STFT values: one per delivered segment, or with ``stft_hop_div=k`` one per frame every
+        ``fft_nperseg / k`` samples (:meth:`BatchSignalAnalyzer.fetch_record_stft`).
 
         ``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
@@ -1068,6 +1168,7 @@ class SignalAnalyzer:
         self.record_iq_margin = int(record_iq_margin)
         self.signal_iq: Optional[List[np.ndarray]] = None
         self.signal_stft: Optional[List[np.ndarray]] = None  # (beside signal_iq: the complex STFT values of each signal's bin)
+        self.stft_hop_div = int(stft_hop_div)
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -1272,7 +1373,7 @@ class SignalAnalyzer:
         return out
 
     def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False,
-               record_stft: bool = False):
+               record_stft: bool = False, stft_hop_div: int = 1):
         """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
         instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
         (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
@@ -1283,7 +1384,8 @@ class SignalAnalyzer:
         ``record_iq=True``: returns ``(signals, signal_iq)`` -- beside every signal its samples, as the per-buffer callbacks of an
         analyzer made with ``record_iq=True`` (and this analyzer's ``record_iq_margin``) leave them in ``signal_iq``.
         ``record_stft=True`` (with ``record_iq=True``): returns ``(signals, signal_iq, signal_stft)``, the complex STFT values of
-        each signal's bin as well (:meth:`BatchSignalAnalyzer.fetch_record_stft`)."""
+        each signal's bin as well (:meth:`BatchSignalAnalyzer.fetch_record_stft`), with ``stft_hop_div=k`` at frames every
+        ``fft_nperseg / k`` samples."""
         if record_stft and not record_iq:
             raise ValueError("record_stft needs record_iq=True")
         per_sample = {"c64": 1, "u8": 2, "i16": 2, "i8": 2}[fmt]
@@ -1321,7 +1423,7 @@ class SignalAnalyzer:
                 offsets, _, got = batch.fetch_record_iq()
                 out_iq.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
             if record_stft:
-                offsets, _, got = batch.fetch_record_stft()
+                offsets, _, got = batch.fetch_record_stft(stft_hop_div)
                 out_stft.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
             out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
 
@@ -1348,7 +1450,7 @@ class SignalAnalyzer:
         if self.record_iq:
             offsets, _, samples = self._batch.fetch_record_iq()
             self.signal_iq = [samples[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
-            offsets, _, values = self._batch.fetch_record_stft()
+            offsets, _, values = self._batch.fetch_record_stft(self.stft_hop_div)
             self.signal_stft = [values[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
 
     def reset(self):

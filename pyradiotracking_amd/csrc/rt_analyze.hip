@@ -39,6 +39,7 @@
 #include "rt_chain.h"
 #include "rt_record_iq.h"
 #include "rt_record_stft.h"
+#include "rt_record_stft_hop.h"
 #include "rt_record_stft_book.h"
 #include "rt_ledger.h"
 #include "rt_tables.h"
@@ -257,6 +258,12 @@ struct IqSlot {
     size_t vals_bytes = 0;
     char *d_work = nullptr;                          // StftWork: the prefix, then the bins
     size_t work_bytes = 0;
+    // rt_fetch_record_stft_hop (rt_record_stft_hop.h): a value pool and a work list of its own, and the hop they were built for
+    int hop_k = 0;                                   // d_hop_vals holds the delivered call's frames at nperseg / hop_k; 0: none
+    char *d_hop_vals = nullptr;                      // [frames] cf, or cd on a float64 handle
+    size_t hop_vals_bytes = 0;
+    char *d_hop_work = nullptr;                      // StftHopWork: frame_first, pool_seg, lp, fi
+    size_t hop_work_bytes = 0;
 };
 struct RecordIq {
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
@@ -1407,6 +1414,7 @@ void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_
     qs.first_seg.assign(n, 0);
     qs.fmt = call.fmt;
     qs.stft_done = false;
+    qs.hop_k = 0;
     qs.fi.resize(n);
     for (size_t i = 0; i < n; ++i) qs.fi[i] = reinterpret_cast<const int32_t *>(static_cast<const char *>(rec) + i * rec_stride)[1];
     std::vector<IqDesc> descs;
@@ -1480,6 +1488,8 @@ void iq_free(rt_handle *h) {
         (void)hipFree(qs.d_descs);
         (void)hipFree(qs.d_vals);
         (void)hipFree(qs.d_work);
+        (void)hipFree(qs.d_hop_vals);
+        (void)hipFree(qs.d_hop_work);
     }
     (void)hipFree(q->d_stft_tw);
     (void)hipFree(q->d_stft_win);
@@ -1678,6 +1688,206 @@ int fetch_record_stft_impl(rt_handle *h, const char *entry, const char *twin, in
         if (!query && mine) {
             RT_HIP(h, hipSetDevice(l->cfg.device));
             RT_HIP(h, hipMemcpy(values + 2 * c0, qs.d_vals, mine * sizeof(C), hipMemcpyDeviceToHost));
+        }
+        r0 += n;
+        c0 += mine;
+    }
+    return RT_OK;
+}
+
+// ---- rt_fetch_record_stft_hop: the same values for frames every nperseg / k samples (rt_record_stft_hop.h) ----
+template <class P, int FMT>
+void launch_record_stft_hop(const StftHopArgs<P> &a, int group, hipStream_t st) {
+    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
+    const dim3 grid((unsigned)((a.n_frames + per_block - 1) / per_block)), block(kStftBlock);
+    if (group == 8) hipLaunchKernelGGL((record_stft_hop<P, FMT, 8>), grid, block, 0, st, a);
+    else if (group == 16) hipLaunchKernelGGL((record_stft_hop<P, FMT, 16>), grid, block, 0, st, a);
+    else if (group == 32) hipLaunchKernelGGL((record_stft_hop<P, FMT, 32>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((record_stft_hop<P, FMT, 64>), grid, block, 0, st, a);
+}
+
+// a device pool that grows on demand, like the byte pool: at least `need` bytes in *p, doubling
+inline bool stft_hop_grow(char **p, size_t *have, size_t need) {
+    if (*have >= need) return true;
+    (void)hipFree(*p);
+    *p = nullptr;
+    const size_t want = std::max(need, std::max(*have * 2, (size_t)1 << 16));
+    *have = 0;
+    if (hipMalloc(p, want) == hipSuccess) {
+        *have = want;
+        return true;
+    }
+    (void)hipGetLastError();
+    if (want == need || hipMalloc(p, need) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return false;
+    }
+    *have = need;
+    return true;
+}
+
+// The frames of lane-less handle `l`'s delivered call at hop nperseg / k into its slot's hop pool: once per delivered call and k
+// (record_stft_run's twin; it shares that entry's twiddle table and window, made by whichever entry is called first, and nothing
+// else -- the value pool, the work list and the k they hold are this entry's own).
+template <class P>
+int record_stft_hop_run(rt_handle *h, rt_handle *l, const char *entry, int k, const StftHopWork &work, int64_t frames) {
+    using C = typename stft_types<P>::C;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    if (qs.hop_k == k) return RT_OK;
+    const int N = iq_nperseg(l);
+    const size_t n = qs.first_seg.size();
+    const int group = stft_hop_group(N, qs.bps);
+    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
+    if ((uint64_t)qs.offsets.back() * (uint64_t)qs.bps > qs.pool_bytes || (frames > 0 && !qs.d_pool) || (frames + per_block - 1) / per_block > 0x7fffffffll) {
+        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+        return RT_E_HIP;
+    }
+    if (frames == 0) {
+        qs.hop_k = k;
+        return RT_OK;
+    }
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    const auto nomem = [&](const char *what, size_t bytes) {
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
+        return RT_E_NOMEM;
+    };
+    if (!q.d_stft_tw) {
+        const std::vector<C> tw = record_stft_twiddles<C, typename std::conditional<sizeof(P) == 4, double, long double>::type>(N);
+        void *d = nullptr;
+        if (hipMalloc(&d, tw.size() * sizeof(C)) != hipSuccess) return nomem("the twiddle table", tw.size() * sizeof(C));
+        if (hipMemcpy(d, tw.data(), tw.size() * sizeof(C), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            h->err = std::string(entry) + ": uploading the twiddle table failed";
+            return RT_E_HIP;
+        }
+        q.d_stft_tw = d;
+    }
+    if (!l->f64 && !q.d_stft_win) {
+        float *d = nullptr;
+        if (hipMalloc(&d, (size_t)N * sizeof(float)) != hipSuccess) return nomem("the window", (size_t)N * sizeof(float));
+        if (hipMemcpy(d, l->h_window.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            h->err = std::string(entry) + ": uploading the window failed";
+            return RT_E_HIP;
+        }
+        q.d_stft_win = d;
+    }
+    qs.hop_k = 0;  // (whatever the pool held is gone from here on)
+    const size_t val_bytes = (size_t)frames * sizeof(C);
+    if (!stft_hop_grow(&qs.d_hop_vals, &qs.hop_vals_bytes, val_bytes)) return nomem("the call's frames", val_bytes);
+    // the work list in one piece: frame_first [n + 1], pool_seg [n], lp [n], fi [n]
+    const size_t b_first = (n + 1) * sizeof(int64_t), b_seg = n * sizeof(int64_t), b_i32 = n * sizeof(int32_t);
+    const size_t work_bytes = b_first + b_seg + 2 * b_i32;
+    if (!stft_hop_grow(&qs.d_hop_work, &qs.hop_work_bytes, work_bytes)) return nomem("the work list", work_bytes);
+    std::vector<char> packed(work_bytes);
+    std::memcpy(packed.data(), work.frame_first.data(), b_first);
+    std::memcpy(packed.data() + b_first, work.pool_seg.data(), b_seg);
+    std::memcpy(packed.data() + b_first + b_seg, work.lp.data(), b_i32);
+    std::memcpy(packed.data() + b_first + b_seg + b_i32, work.fi.data(), b_i32);
+    StftHopArgs<P> a{};
+    a.pool = qs.d_pool;
+    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_hop_work);
+    a.pool_seg = reinterpret_cast<const int64_t *>(qs.d_hop_work + b_first);
+    a.lp = reinterpret_cast<const int32_t *>(qs.d_hop_work + b_first + b_seg);
+    a.fi = reinterpret_cast<const int32_t *>(qs.d_hop_work + b_first + b_seg + b_i32);
+    a.n_records = (int32_t)n;
+    a.nperseg = N;
+    a.hop_div = k;
+    a.n_frames = frames;
+    a.pool_samples = qs.offsets.back();
+    a.tw = static_cast<const C *>(q.d_stft_tw);
+    a.values = reinterpret_cast<C *>(qs.d_hop_vals);
+    if constexpr (sizeof(P) == 4) {
+        a.window = q.d_stft_win;
+        a.root = stft_root_f32(l->cfg.scale);
+    } else {
+        a.window = l->f64->d_window;
+        a.root = stft_root_f64(l->f64->c.scale);
+    }
+    // (a pageable source: `packed` lives until the stream has been waited for below)
+    hipError_t e = hipMemcpyAsync(qs.d_hop_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        if (qs.fmt == kFmtU8) launch_record_stft_hop<P, kFmtU8>(a, group, q.s_gather);
+        else if (qs.fmt == kFmtI16) launch_record_stft_hop<P, kFmtI16>(a, group, q.s_gather);
+        else if (qs.fmt == kFmtI8) launch_record_stft_hop<P, kFmtI8>(a, group, q.s_gather);
+        else launch_record_stft_hop<P, kFmtC64>(a, group, q.s_gather);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": record_stft_hop: " + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    qs.hop_k = k;
+    return RT_OK;
+}
+
+template <class P>
+int fetch_record_stft_hop_impl(rt_handle *h, const char *entry, const char *twin, int32_t hop_div, int64_t *offsets, size_t n_offsets,
+                               int32_t *first_seg, size_t n_first, P *values, size_t cap_frames, size_t *n_frames) {
+    using C = typename stft_types<P>::C;
+    if (!h || !n_frames) return RT_E_INVALID;
+    *n_frames = 0;
+    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
+        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
+        return RT_E_INVALID;
+    }
+    const int N = iq_nperseg(h);
+    if (!stft_hop_div_ok(N, hop_div)) {
+        h->err = std::string(entry) + ": hop_div k = " + std::to_string(hop_div) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) +
+                 " and divide nperseg N = " + std::to_string(N);
+        return RT_E_INVALID;
+    }
+    std::vector<rt_handle *> lanes;
+    size_t records = 0, samples = 0;
+    int bps = 0;
+    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
+        h->err = std::string(entry) + ": n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
+        return RT_E_INVALID;
+    }
+    // every lane's frame plan, before anything is launched or written
+    std::vector<StftHopWork> works(lanes.size());
+    std::vector<int64_t> frames(lanes.size());
+    size_t total = 0;
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
+        frames[i] = stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.first_seg.size(), N, hop_div, &works[i]);
+        if (frames[i] < 0) {
+            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+            return RT_E_HIP;
+        }
+        total += (size_t)frames[i];
+    }
+    *n_frames = total;
+    const bool query = !values || cap_frames == 0;
+    if (!query && cap_frames < total) {
+        h->err = std::string(entry) + ": output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    if (!query)
+        for (size_t i = 0; i < lanes.size(); ++i) {
+            const int rs = record_stft_hop_run<P>(h, lanes[i], entry, hop_div, works[i], frames[i]);
+            if (rs != RT_OK) return rs;
+        }
+    size_t r0 = 0, c0 = 0;
+    if (offsets) offsets[0] = 0;
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        rt_handle *l = lanes[i];
+        const IqSlot &qs = l->riq->slot[l->riq->delivered];
+        const size_t n = qs.first_seg.size(), mine = (size_t)frames[i];
+        if (offsets)
+            for (size_t r = 0; r < n; ++r) offsets[r0 + r + 1] = (int64_t)c0 + works[i].frame_first[r + 1];
+        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
+        if (!query && mine) {
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(values + 2 * c0, qs.d_hop_vals, mine * sizeof(C), hipMemcpyDeviceToHost));
         }
         r0 += n;
         c0 += mine;
@@ -3547,6 +3757,18 @@ int rt_fetch_record_stft(rt_handle *h, int64_t *offsets, size_t n_offsets, int32
 int rt_fetch_record_stft_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, double *values,
                              size_t cap_cells, size_t *n_cells) {
     return fetch_record_stft_impl<double>(h, "rt_fetch_record_stft_f64", "rt_fetch_record_stft", offsets, n_offsets, first_seg, n_first, values, cap_cells, n_cells);
+}
+
+int rt_fetch_record_stft_hop(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, float *values,
+                             size_t cap_frames, size_t *n_frames) {
+    return fetch_record_stft_hop_impl<float>(h, "rt_fetch_record_stft_hop", "rt_fetch_record_stft_hop_f64", hop_div, offsets, n_offsets, first_seg, n_first,
+                                             values, cap_frames, n_frames);
+}
+
+int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, double *values,
+                                 size_t cap_frames, size_t *n_frames) {
+    return fetch_record_stft_hop_impl<double>(h, "rt_fetch_record_stft_hop_f64", "rt_fetch_record_stft_hop", hop_div, offsets, n_offsets, first_seg, n_first,
+                                              values, cap_frames, n_frames);
 }
 
 int rt_get_call_info(rt_handle *h, rt_call_info *info) {

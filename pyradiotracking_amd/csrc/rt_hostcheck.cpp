@@ -753,6 +753,25 @@ long long hc_stft_work(const int64_t *offsets, const int32_t *fi, long long n, i
     return (long long)cells;
 }
 int hc_stft_record_of(const int64_t *seg_first, int n, long long g) { return stft_record_of(seg_first, n, (int64_t)g); }
+// rt_fetch_record_stft_hop's frame plan: -> frame_first [n + 1], pool_seg [n], lp [n], fi_out [n]; returns the frames, -1: refused
+long long hc_stft_hop_work(const int64_t *offsets, const int32_t *first_seg, const int32_t *fi, long long n, int nperseg, int k, int64_t *frame_first,
+                           int64_t *pool_seg, int32_t *lp, int32_t *fi_out) {
+    StftHopWork w;
+    const int64_t frames = stft_hop_build_work(offsets, first_seg, fi, (size_t)n, nperseg, k, &w);
+    if (frames < 0) return -1;
+    std::copy(w.frame_first.begin(), w.frame_first.end(), frame_first);
+    std::copy(w.pool_seg.begin(), w.pool_seg.end(), pool_seg);
+    std::copy(w.lp.begin(), w.lp.end(), lp);
+    std::copy(w.fi.begin(), w.fi.end(), fi_out);
+    return (long long)frames;
+}
+// out: record, part, pool sample of frame g
+void hc_stft_hop_frame_at(const int64_t *frame_first, const int64_t *pool_seg, const int32_t *lp, int n, int nperseg, int k, long long g, int64_t *out) {
+    const StftHopFrame f = stft_hop_frame_at(frame_first, pool_seg, lp, n, nperseg, k, (int64_t)g);
+    out[0] = f.record;
+    out[1] = f.part;
+    out[2] = f.sample;
+}
 float hc_stft_root_f32(float scale) { return stft_root_f32(scale); }
 double hc_stft_root_f64(double scale) { return stft_root_f64(scale); }
 // out: [nperseg] interleaved (re, im)

@@ -11,6 +11,7 @@
 
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -49,6 +50,77 @@ inline int stft_record_of(const int64_t *seg_first, int n, int64_t g) {
         if (seg_first[mid] <= g) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// ---- rt_fetch_record_stft_hop: frames every h = N / k samples (record_stft_hop, rt_record_stft_hop.h) ----
+// A record's delivered segments fall into two PARTS that lie one behind the other in the pool: the Lp segments below 0 (the
+// predecessor buffer's) and the Lc from 0 on (the call's own).  A part of L >= 1 segments has (L - 1) k + 1 frames, frame j the N
+// samples from sample j h of the part; a part without a segment has none, and no frame straddles the two parts -- the predecessor's
+// ragged remainder lies between them.  The list is per record again; a lane group finds its record by binary search over the frame
+// prefix and its part by one comparison.
+struct StftHopWork {
+    int N = 0, k = 0;
+    std::vector<int64_t> frame_first;  // [n + 1] frames in front of each record; frame_first[n]: all of them
+    std::vector<int64_t> pool_seg;     // [n] the pool segment of each record's first delivered segment
+    std::vector<int32_t> lp;           // [n] segments of the predecessor part: clamp(-first_seg, 0, L)
+    std::vector<int32_t> fi;           // [n] each record's bin, fftfreq order
+};
+
+constexpr int kStftHopMaxDiv = 16;
+
+inline bool stft_hop_div_ok(int N, int k) { return N >= 1 && k >= 1 && k <= kStftHopMaxDiv && N % k == 0; }
+inline int64_t stft_hop_part_frames(int64_t L, int k) { return L > 0 ? (L - 1) * k + 1 : 0; }
+
+// `offsets`, `fi` as stft_build_work takes them, `first_seg` [n]: IqSlot::first_seg.  Returns the call's frames, or -1 where the
+// lists are not what iq_build_descs writes or k is no divisor of N in 1 .. 16: nothing is launched from such a list.
+inline int64_t stft_hop_build_work(const int64_t *offsets, const int32_t *first_seg, const int32_t *fi, size_t n, int N, int k, StftHopWork *w) {
+    if (!stft_hop_div_ok(N, k) || (n && !first_seg)) return -1;
+    if (stft_build_work(offsets, fi, n, N, nullptr) < 0) return -1;
+    if (w) {
+        w->N = N;
+        w->k = k;
+        w->frame_first.assign(n + 1, 0);
+        w->pool_seg.assign(n, 0);
+        w->lp.assign(n, 0);
+        w->fi.assign(n, 0);
+    }
+    int64_t frames = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t L = (offsets[i + 1] - offsets[i]) / N;
+        const int64_t Lp = std::min<int64_t>(std::max<int64_t>(-(int64_t)first_seg[i], 0), L);
+        if (L > INT32_MAX) return -1;
+        frames += stft_hop_part_frames(Lp, k) + stft_hop_part_frames(L - Lp, k);
+        if (w) {
+            w->frame_first[i + 1] = frames;
+            w->pool_seg[i] = offsets[i] / N;
+            w->lp[i] = (int32_t)Lp;
+            w->fi[i] = fi[i];
+        }
+    }
+    return frames;
+}
+
+struct StftHopFrame {
+    int record;      // the record frame g belongs to
+    int part;        // 0: the predecessor part, 1: the record's own
+    int64_t sample;  // the frame's first sample in the pool
+};
+
+// frame g (0 <= g < frame_first[n]) -> its record (the last one that starts at or before it), its part and where its N samples
+// start.  The kernel's search, word for word.
+inline StftHopFrame stft_hop_frame_at(const int64_t *frame_first, const int64_t *pool_seg, const int32_t *lp, int n, int N, int k, int64_t g) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_first[mid] <= g) lo = mid; else hi = mid - 1;
+    }
+    const int64_t j = g - frame_first[lo], h = N / k;
+    const int64_t Lp = lp[lo], Fp = Lp > 0 ? (Lp - 1) * k + 1 : 0;
+    if (j < Fp) return StftHopFrame{lo, 0, pool_seg[lo] * N + j * h};
+    return StftHopFrame{lo, 1, (pool_seg[lo] + Lp) * N + (j - Fp) * h};
+}
+inline StftHopFrame stft_hop_frame_at(const StftHopWork &w, int64_t g) {
+    return stft_hop_frame_at(w.frame_first.data(), w.pool_seg.data(), w.lp.data(), (int)w.lp.size(), w.N, w.k, g);
 }
 
 // sqrt(scale), the factor between the windowed transform and a value: evaluated in float64, and on a float32 handle rounded once
