@@ -704,6 +704,51 @@ int rt_fetch_record_stft_hop(rt_handle *h, int32_t hop_div, int64_t *offsets, si
 int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
                                  double *values, size_t cap_frames, size_t *n_frames); /* float64 handle */
 
+/*
+ * ---- per-record estimates from the frames, reduced on the device (additive within ABI version 6) ----
+ * What a caller makes of rt_fetch_record_stft_hop's frames is one row per record: the tone's offset from its bin (pulse pair),
+ * its coherence, the pulse's level and its rise and fall.  This entry reduces the frames where they lie; they are not copied to the
+ * host.  One entry serves float32 and float64 handles: the rows are float64 either way, only the frames read differ.
+ *   - `hop_div`: k as for rt_fetch_record_stft_hop (1 ... 16, a divisor of N = nperseg; k == 1: the frames are the segments);
+ *     anything else is RT_E_INVALID, refused before anything is launched or copied.  h = N / k.
+ *   - the call, the records and their order are rt_fetch_record_stft_hop's; rt_set_record_iq must be on.
+ *   - `out`: HOST memory, `cap` rows.  out == NULL or cap == 0: a size query, *n_out = the records.  cap < *n_out with a buffer:
+ *     RT_E_CAPACITY, nothing written.  Validity, RT_E_NOMEM and every refusal: rt_fetch_record_stft_hop's, under this entry's name.
+ *   - a frame's position is its first sample relative to sample 0 of the call's buffer (frames of the predecessor part are
+ *     negative: segment -1 starts at -N).  The INSIDE frames of record (start, end) are those with start * N <= position and
+ *     position + N <= end * N.  |c| = sqrt(re * re + im * im) in float64, +inf where a component is infinite.
+ *   - pairs are consecutive inside frames of the same part; no pair spans the predecessor part and the record's own, at any k.
+ *       R = sum c[t + 1] conj(c[t]), multiplied by exp(-2 pi i (fi mod k) / k) where k > 1 (the bin's own turn over one hop)
+ *       M = sum |c[t + 1]| |c[t]|
+ *       offset_bins = atan2(r_im, r_re) / (2 pi) * k  (bins; times sample_rate / N for Hz), coherence = |R| / M
+ *     R is formed as record_fine forms it, re + 1j * im: r_re is NaN where r_im is infinite or NaN.
+ *     both NaN when n_pairs == 0; M == 0 gives coherence 0 / 0 = NaN; where R is exactly zero the sign of offset_bins is atan2's
+ *     and no part of the contract.
+ *   - level: the exact median of |c| over the inside frames (the mean of the two middle values of an even count); NaN when there
+ *     is none, and when any of them is NaN.
+ *   - rise, fall: half = level / 2; unless half > 0, both are NaN.  up0 is the first inside frame with |c| >= half, q the nearest
+ *     earlier frame of the same part -- among all delivered frames, not only the inside ones -- with |c[q]| < half (a NaN |c| is
+ *     passed over).  rise = position[q] + (half - |c[q]|) / (|c[q + 1]| - |c[q]|) * h + N / 2; NaN where the part ends before such
+ *     a q.  fall mirrors it forward from the last inside frame with |c| >= half.
+ *   - the same frames give the same row bytes: on every handle kind, on every fetch and in every order of calls.
+ *   - lazy: rt_process*, rt_fetch and the other fetch entries allocate, copy and launch what they do without this entry (the gather
+ *     notes the records' start and end on the host).  The entry's first call for a delivered call and k makes sure the hop pool
+ *     holds the frames for k (as rt_fetch_record_stft_hop would, without the copy), uploads a plan of 48 bytes a record, runs one
+ *     kernel on the gather's stream, waits, and copies the rows down.  A repeated call with the same k copies the rows again; a
+ *     later rt_fetch_record_stft_hop with the same k copies without rebuilding.
+ */
+typedef struct rt_record_estimate {
+    double r_re, r_im;     /* R, turned back                                                  */
+    double pair_mag;       /* M                                                               */
+    double offset_bins;    /* NaN when n_pairs == 0                                           */
+    double coherence;      /* NaN when n_pairs == 0                                           */
+    double level;          /* NaN when n_inside == 0                                          */
+    double rise, fall;     /* samples relative to sample 0 of the call's buffer, or NaN       */
+    int32_t n_pairs, n_inside;
+} rt_record_estimate;      /* 72 bytes */
+
+int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out);
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

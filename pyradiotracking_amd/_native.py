@@ -95,6 +95,24 @@ RECORD_DTYPE = np.dtype(
     ]
 )
 
+#: numpy view of ``rt_record_estimate`` (72 bytes): a row of ``rt_fetch_record_estimates``
+ESTIMATE_DTYPE = np.dtype(
+    [
+        ("r_re", "<f8"),
+        ("r_im", "<f8"),
+        ("pair_mag", "<f8"),
+        ("offset_bins", "<f8"),
+        ("coherence", "<f8"),
+        ("level", "<f8"),
+        ("rise", "<f8"),
+        ("fall", "<f8"),
+        ("n_pairs", "<i4"),
+        ("n_inside", "<i4"),
+    ]
+)
+assert ESTIMATE_DTYPE.itemsize == 72
+
+
 class RtConfigF64(C.Structure):
     """``rt_config_f64``: the float64 window / scale / thresholds / calibration of a float64 handle (``rt_create_f64``)."""
 
@@ -172,6 +190,7 @@ ABI_SYMBOLS = (
     "rt_fetch_record_stft_f64",
     "rt_fetch_record_stft_hop",
     "rt_fetch_record_stft_hop_f64",
+    "rt_fetch_record_estimates",
 )
 
 _lib = None
@@ -250,6 +269,7 @@ def load_library(path: Optional[str] = None):
         fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for fn in (lib.rt_fetch_record_stft_hop, lib.rt_fetch_record_stft_hop_f64):
         fn.argtypes = [vp, C.c_int32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.rt_fetch_record_estimates.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -644,6 +664,16 @@ class NativeAnalyzer:
         if n.value:
             self._check(fn(self._handle, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, values.ctypes.data, values.size, C.byref(n)))
         return offsets, first, values
+
+    def fetch_record_estimates(self, hop_div: int = 4) -> np.ndarray:
+        """``rt_fetch_record_estimates``: one ``ESTIMATE_DTYPE`` row per record of the call ``fetch`` delivered last (in full),
+        reduced on the device from the frames every ``nperseg / hop_div`` samples; the frames are not copied."""
+        n = C.c_size_t(0)
+        self._check(self._lib.rt_fetch_record_estimates(self._handle, int(hop_div), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=ESTIMATE_DTYPE)
+        if n.value:
+            self._check(self._lib.rt_fetch_record_estimates(self._handle, int(hop_div), out.ctypes.data, out.size, C.byref(n)))
+        return out
 
     def fetch_row_means(self) -> np.ndarray:
         """``rt_fetch_row_means`` (``rt_fetch_row_means_f64`` on a float64 handle): ``[S, nperseg]`` float32 (float64), the

@@ -236,6 +236,9 @@ def _same_signal(a, b) -> bool:
 
 
 FINE_DTYPE = np.dtype([("offset_hz", np.float64), ("coherence", np.float64), ("n_pairs", np.int32)])
+#: a row of :meth:`BatchSignalAnalyzer.fetch_record_estimates`: what ``record_fine`` and ``record_edges`` give, reduced on the device
+ESTIMATES_DTYPE = np.dtype([("offset_hz", np.float64), ("coherence", np.float64), ("n_pairs", np.int32), ("level", np.float64), ("rise", np.float64),
+                            ("fall", np.float64), ("n_inside", np.int32), ("r", np.complex128), ("pair_mag", np.float64)])
 
 
 def _stft_frames(offsets, first_segment, nperseg: int, hop_div: int):
@@ -1024,6 +1027,24 @@ class BatchSignalAnalyzer:
         rec = self._native._last_fetched
         return record_edges(offsets, first, values, rec["start"], rec["end"], self.fft_nperseg, hop_div)
 
+    def fetch_record_estimates(self, hop_div: int = 4) -> np.ndarray:
+        """One ``ESTIMATES_DTYPE`` row per record of the call returned last, reduced on the device from the frames of
+        ``fetch_record_stft(hop_div)`` (``rt_fetch_record_estimates``) -- the frames themselves are not copied to the host:
+        ``offset_hz``, ``coherence``, ``n_pairs`` as :func:`record_fine` gives them for ``hop_div``, ``rise`` and ``fall`` as
+        :func:`record_edges` does, ``level`` (the median of ``|c|`` over the ``n_inside`` frames wholly inside the record's own
+        cells, whose half the edges are read at), and the raw sums ``r`` (turned back by the bin's own rotation) and ``pair_mag``
+        (``coherence = |r| / pair_mag``).  The two host functions define the result; the rows are float64 on every handle kind and
+        the same frames give the same bytes.  ``hop_div`` 1 ... 16, a divisor of ``fft_nperseg``; 1: the frames are the segments.
+        Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is."""
+        rows = self._native.fetch_record_estimates(hop_div)
+        out = np.zeros(len(rows), dtype=ESTIMATES_DTYPE)
+        out["offset_hz"] = rows["offset_bins"] * float(self.sample_rate) / int(self.fft_nperseg)
+        for name in ("coherence", "n_pairs", "level", "rise", "fall", "n_inside", "pair_mag"):
+            out[name] = rows[name]
+        out["r"].real = rows["r_re"]  # (the parts as they are: 1j * r_im would turn an infinite r_im into a NaN real part)
+        out["r"].imag = rows["r_im"]
+        return out
+
     def fetch_record_fine(self, hop_div: int = 1) -> np.ndarray:
         """One row per record of the call returned last (``FINE_DTYPE``: ``offset_hz``, ``coherence``, ``n_pairs``): the
         pulse-pair estimate of the tone's offset from its bin centre, from the values of the record's own cells (``[start, end)``
@@ -1142,13 +1163,15 @@ class SignalAnalyzer:
         record_iq: bool = False,
         record_iq_margin: int = 0,
         stft_hop_div: int = 1,
+        record_estimates: bool = False,
         **kwargs,
     ):
         """``record_iq=True``: after every buffer ``signal_iq`` is the list of the sample arrays of the signals put on the queue
         (unshadowed, queue order, like ``signal_data``) -- the IQ of each pulse in the format the buffer came in, with
         ``record_iq_margin`` whole segments on either side (:meth:`BatchSignalAnalyzer.fetch_record_iq`), and ``signal_stft`` the
         list of their complex STFT values: one per delivered segment, or with ``stft_hop_div=k`` one per frame every
-        ``fft_nperseg / k`` samples (:meth:`BatchSignalAnalyzer.fetch_record_stft`).
+        ``fft_nperseg / k`` samples (:meth:`BatchSignalAnalyzer.fetch_record_stft`).  ``record_estimates=True`` with it:
+        ``signal_estimates`` holds one row per such signal (:meth:`BatchSignalAnalyzer.fetch_record_estimates` at ``stft_hop_div``).
 
         ``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
@@ -1169,6 +1192,10 @@ class SignalAnalyzer:
         self.signal_iq: Optional[List[np.ndarray]] = None
         self.signal_stft: Optional[List[np.ndarray]] = None  # (beside signal_iq: the complex STFT values of each signal's bin)
         self.stft_hop_div = int(stft_hop_div)
+        if record_estimates and not record_iq:
+            raise ValueError("record_estimates needs record_iq=True")
+        self.record_estimates = bool(record_estimates)
+        self.signal_estimates: Optional[np.ndarray] = None  # (beside signal_stft: one ESTIMATES_DTYPE row per signal)
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -1293,7 +1320,7 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
         self._batch.enqueue_bytes(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1317,7 +1344,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
         self._batch.enqueue_int16(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1341,7 +1368,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
         self._batch.enqueue_int8(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1356,7 +1383,7 @@ class SignalAnalyzer:
         buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
         if self.record_cells or self.record_iq:  # (process_batch, with the records kept for the cells' shadow flags)
             self._batch.enqueue(buf)
             rec = self._batch.fetch_records()
@@ -1373,7 +1400,7 @@ class SignalAnalyzer:
         return out
 
     def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False,
-               record_stft: bool = False, stft_hop_div: int = 1):
+               record_stft: bool = False, stft_hop_div: int = 1, record_estimates: bool = False):
         """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
         instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
         (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
@@ -1385,9 +1412,12 @@ class SignalAnalyzer:
         analyzer made with ``record_iq=True`` (and this analyzer's ``record_iq_margin``) leave them in ``signal_iq``.
         ``record_stft=True`` (with ``record_iq=True``): returns ``(signals, signal_iq, signal_stft)``, the complex STFT values of
         each signal's bin as well (:meth:`BatchSignalAnalyzer.fetch_record_stft`), with ``stft_hop_div=k`` at frames every
-        ``fft_nperseg / k`` samples."""
+        ``fft_nperseg / k`` samples.  ``record_estimates=True`` (with ``record_iq=True``): one more list at the end of the tuple,
+        a row of :meth:`BatchSignalAnalyzer.fetch_record_estimates` (at ``stft_hop_div``) per signal."""
         if record_stft and not record_iq:
             raise ValueError("record_stft needs record_iq=True")
+        if record_estimates and not record_iq:
+            raise ValueError("record_estimates needs record_iq=True")
         per_sample = {"c64": 1, "u8": 2, "i16": 2, "i8": 2}[fmt]
         want = {"c64": np.complex64, "u8": np.uint8, "i16": np.int16, "i8": np.int8}[fmt]
         x = np.asarray(samples).reshape(-1)
@@ -1414,6 +1444,7 @@ class SignalAnalyzer:
         out: List[Signal] = []
         out_iq: List[np.ndarray] = []
         out_stft: List[np.ndarray] = []
+        out_est: List[np.void] = []
 
         def call(first: int, links: int, length: int):
             part = x[first * B * per_sample:(first * B + links * length) * per_sample]
@@ -1425,6 +1456,8 @@ class SignalAnalyzer:
             if record_stft:
                 offsets, _, got = batch.fetch_record_stft(stft_hop_div)
                 out_stft.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
+            if record_estimates:
+                out_est.extend(batch.fetch_record_estimates(stft_hop_div)[rec["shadowed"] == 0])
             out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
 
         for first in range(0, n_full, L):
@@ -1434,9 +1467,8 @@ class SignalAnalyzer:
         elif rest:
             logger.info(f"SDR {self.device} replay: the last {rest} samples hold fewer than two segments and are dropped")
         [self.consume_signal(s) for s in out]
-        if record_stft:
-            return out, out_iq, out_stft
-        return (out, out_iq) if record_iq else out
+        got = (out, out_iq) + ((out_stft,) if record_stft else ()) + ((out_est,) if record_estimates else ())
+        return got if record_iq else out
 
     def _keep_noise(self):
         if self.row_means:
@@ -1452,6 +1484,8 @@ class SignalAnalyzer:
             self.signal_iq = [samples[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
             offsets, _, values = self._batch.fetch_record_stft(self.stft_hop_div)
             self.signal_stft = [values[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
+            if self.record_estimates:
+                self.signal_estimates = self._batch.fetch_record_estimates(self.stft_hop_div)[np.flatnonzero(keep)]
 
     def reset(self):
         self._batch.reset()
@@ -1473,7 +1507,7 @@ class SignalAnalyzer:
         dense detect kernel (``rt_extract``).  The time axis must be the one
         SciPy produces for ``fft_nperseg`` / ``sample_rate`` (hop = nperseg/fs);
         ``freqs`` is used as given."""
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = None  # (the caller holds this map: no row means, no cells of it)
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None  # (the caller holds this map: no row means, no cells of it)
         spec = np.asarray(spectrogram)
         n_bins, n_seg = spec.shape
         if n_seg == 0:

@@ -40,6 +40,7 @@
 #include "rt_record_iq.h"
 #include "rt_record_stft.h"
 #include "rt_record_stft_hop.h"
+#include "rt_record_estimates.h"
 #include "rt_record_stft_book.h"
 #include "rt_ledger.h"
 #include "rt_tables.h"
@@ -264,6 +265,13 @@ struct IqSlot {
     size_t hop_vals_bytes = 0;
     char *d_hop_work = nullptr;                      // StftHopWork: frame_first, pool_seg, lp, fi
     size_t hop_work_bytes = 0;
+    // rt_fetch_record_estimates (rt_record_estimates.h): the records' cells as the gather notes them, the rows and their plan
+    std::vector<int32_t> start, end;                 // [records]
+    int est_k = 0;                                   // d_est holds the delivered call's rows for this hop_div; 0: none
+    char *d_est = nullptr;                           // [records] rt_record_estimate
+    size_t est_bytes = 0;
+    char *d_est_work = nullptr;                      // the turn-back table, then EstimatesWork
+    size_t est_work_bytes = 0;
 };
 struct RecordIq {
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
@@ -1415,8 +1423,16 @@ void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_
     qs.fmt = call.fmt;
     qs.stft_done = false;
     qs.hop_k = 0;
+    qs.est_k = 0;
     qs.fi.resize(n);
-    for (size_t i = 0; i < n; ++i) qs.fi[i] = reinterpret_cast<const int32_t *>(static_cast<const char *>(rec) + i * rec_stride)[1];
+    qs.start.resize(n);
+    qs.end.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t *const r = reinterpret_cast<const int32_t *>(static_cast<const char *>(rec) + i * rec_stride);
+        qs.fi[i] = r[1];
+        qs.start[i] = r[2];
+        qs.end[i] = r[3];
+    }
     std::vector<IqDesc> descs;
     const int64_t total = iq_build_descs(call, N, rec, rec_stride, n, qs.offsets.data(), qs.first_seg.data(), &descs);
     if (descs.empty()) return;
@@ -1490,6 +1506,8 @@ void iq_free(rt_handle *h) {
         (void)hipFree(qs.d_work);
         (void)hipFree(qs.d_hop_vals);
         (void)hipFree(qs.d_hop_work);
+        (void)hipFree(qs.d_est);
+        (void)hipFree(qs.d_est_work);
     }
     (void)hipFree(q->d_stft_tw);
     (void)hipFree(q->d_stft_win);
@@ -1891,6 +1909,132 @@ int fetch_record_stft_hop_impl(rt_handle *h, const char *entry, const char *twin
         }
         r0 += n;
         c0 += mine;
+    }
+    return RT_OK;
+}
+
+// ---- rt_fetch_record_estimates: one row per record, reduced from the hop pool's frames (rt_record_estimates.h) ----
+// The rows of lane-less handle `l`'s delivered call for hop_div k into its slot's row pool: once per delivered call and k.  The hop
+// pool is made to hold k first (record_stft_hop_run: a no-op where it does); the frames stay on the device.
+template <class P>
+int record_estimates_run(rt_handle *h, rt_handle *l, const char *entry, int k, const StftHopWork &hop, const EstimatesWork &work, int64_t frames) {
+    using C = typename stft_types<P>::C;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    if (qs.est_k == k) return RT_OK;
+    const size_t n = qs.first_seg.size();
+    if (n == 0) {
+        qs.est_k = k;
+        return RT_OK;
+    }
+    if (n > (size_t)INT32_MAX) {  // (the kernel counts records in int32; the grid is a quarter of that)
+        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+        return RT_E_HIP;
+    }
+    const int rs = record_stft_hop_run<P>(h, l, entry, k, hop, frames);
+    if (rs != RT_OK) return rs;
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    const auto nomem = [&](const char *what, size_t bytes) {
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
+        return RT_E_NOMEM;
+    };
+    qs.est_k = 0;  // (whatever the row pool held is gone from here on)
+    const size_t row_bytes = n * sizeof(rt_record_estimate);
+    if (!stft_hop_grow(&qs.d_est, &qs.est_bytes, row_bytes)) return nomem("the call's estimates", row_bytes);
+    // the plan in one piece: the turn-back table, frame_first [n + 1], base [n][2], range [n][4], lp [n], fmod [n]
+    const size_t b_first = (n + 1) * sizeof(int64_t), b_base = 2 * n * sizeof(int64_t), b_range = 4 * n * sizeof(int32_t), b_i32 = n * sizeof(int32_t);
+    const size_t o_first = kEstTurnBytes, o_base = o_first + b_first, o_range = o_base + b_base, o_lp = o_range + b_range, o_fmod = o_lp + b_i32;
+    const size_t work_bytes = o_fmod + b_i32;
+    if (!stft_hop_grow(&qs.d_est_work, &qs.est_work_bytes, work_bytes)) return nomem("the estimates' plan", work_bytes);
+    std::vector<char> packed(work_bytes);
+    static_assert(kEstTurnBytes >= 2 * kStftHopMaxDiv * (int)sizeof(double), "the turn-back table holds every hop_div");
+    estimates_turn_table(k, reinterpret_cast<double *>(packed.data()));
+    std::memcpy(packed.data() + o_first, work.frame_first.data(), b_first);
+    std::memcpy(packed.data() + o_base, work.base.data(), b_base);
+    std::memcpy(packed.data() + o_range, work.range.data(), b_range);
+    std::memcpy(packed.data() + o_lp, work.lp.data(), b_i32);
+    std::memcpy(packed.data() + o_fmod, work.fmod.data(), b_i32);
+    EstimatesArgs<P> a{};
+    a.values = reinterpret_cast<const C *>(qs.d_hop_vals);
+    a.turn = reinterpret_cast<const double *>(qs.d_est_work);
+    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_est_work + o_first);
+    a.base = reinterpret_cast<const int64_t *>(qs.d_est_work + o_base);
+    a.range = reinterpret_cast<const int32_t *>(qs.d_est_work + o_range);
+    a.lp = reinterpret_cast<const int32_t *>(qs.d_est_work + o_lp);
+    a.fmod = reinterpret_cast<const int32_t *>(qs.d_est_work + o_fmod);
+    a.n_records = (int32_t)n;
+    a.nperseg = iq_nperseg(l);
+    a.hop_div = k;
+    a.n_frames = frames;
+    a.out = reinterpret_cast<rt_record_estimate *>(qs.d_est);
+    // (a pageable source: `packed` lives until the stream has been waited for below)
+    hipError_t e = hipMemcpyAsync(qs.d_est_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((record_estimates<P>), dim3((unsigned)((n + kStftWaves - 1) / kStftWaves)), dim3(kStftBlock), 0, q.s_gather, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": record_estimates: " + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    qs.est_k = k;
+    return RT_OK;
+}
+
+int fetch_record_estimates_impl(rt_handle *h, const char *entry, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out) {
+    if (!h || !n_out) return RT_E_INVALID;
+    *n_out = 0;
+    const int N = iq_nperseg(h);
+    if (!stft_hop_div_ok(N, hop_div)) {
+        h->err = std::string(entry) + ": hop_div k = " + std::to_string(hop_div) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) +
+                 " and divide nperseg N = " + std::to_string(N);
+        return RT_E_INVALID;
+    }
+    std::vector<rt_handle *> lanes;
+    size_t records = 0, samples = 0;
+    int bps = 0;
+    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    // every lane's plans, before anything is launched or written
+    std::vector<StftHopWork> hops(lanes.size());
+    std::vector<EstimatesWork> works(lanes.size());
+    std::vector<int64_t> frames(lanes.size());
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
+        const size_t n = qs.first_seg.size();
+        frames[i] = qs.start.size() == n && qs.end.size() == n && qs.fi.size() == n
+                        ? estimates_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.start.data(), qs.end.data(), n, N, hop_div, &works[i])
+                        : -1;
+        if (frames[i] < 0 || stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), n, N, hop_div, &hops[i]) != frames[i]) {
+            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+            return RT_E_HIP;
+        }
+    }
+    *n_out = records;
+    const bool query = !out || cap == 0;
+    if (query) return RT_OK;
+    if (cap < records) {
+        h->err = std::string(entry) + ": output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const int rs = lanes[i]->f64 ? record_estimates_run<double>(h, lanes[i], entry, hop_div, hops[i], works[i], frames[i])
+                                     : record_estimates_run<float>(h, lanes[i], entry, hop_div, hops[i], works[i], frames[i]);
+        if (rs != RT_OK) return rs;
+    }
+    size_t r0 = 0;
+    for (rt_handle *l : lanes) {
+        const IqSlot &qs = l->riq->slot[l->riq->delivered];
+        const size_t n = qs.first_seg.size();
+        if (n) {
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(out + r0, qs.d_est, n * sizeof(rt_record_estimate), hipMemcpyDeviceToHost));
+        }
+        r0 += n;
     }
     return RT_OK;
 }
@@ -3769,6 +3913,10 @@ int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets
                                  size_t cap_frames, size_t *n_frames) {
     return fetch_record_stft_hop_impl<double>(h, "rt_fetch_record_stft_hop_f64", "rt_fetch_record_stft_hop", hop_div, offsets, n_offsets, first_seg, n_first,
                                               values, cap_frames, n_frames);
+}
+
+int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out) {
+    return fetch_record_estimates_impl(h, "rt_fetch_record_estimates", hop_div, out, cap, n_out);
 }
 
 int rt_get_call_info(rt_handle *h, rt_call_info *info) {

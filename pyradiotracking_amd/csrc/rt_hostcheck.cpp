@@ -772,6 +772,21 @@ void hc_stft_hop_frame_at(const int64_t *frame_first, const int64_t *pool_seg, c
     out[1] = f.part;
     out[2] = f.sample;
 }
+// rt_fetch_record_estimates' plan: -> frame_first [n + 1], lp [n], range [n][4], base [n][2], fmod [n], turn [k][2]; returns the
+// frames, -1: refused (nothing is written then)
+long long hc_estimates_work(const int64_t *offsets, const int32_t *first_seg, const int32_t *fi, const int32_t *start, const int32_t *end, long long n,
+                            int nperseg, int k, int64_t *frame_first, int32_t *lp, int32_t *range, int64_t *base, int32_t *fmod, double *turn) {
+    EstimatesWork w;
+    const int64_t frames = estimates_build_work(offsets, first_seg, fi, start, end, (size_t)n, nperseg, k, &w);
+    if (frames < 0) return -1;
+    std::copy(w.frame_first.begin(), w.frame_first.end(), frame_first);
+    std::copy(w.lp.begin(), w.lp.end(), lp);
+    std::copy(w.range.begin(), w.range.end(), range);
+    std::copy(w.base.begin(), w.base.end(), base);
+    std::copy(w.fmod.begin(), w.fmod.end(), fmod);
+    if (turn) estimates_turn_table(k, turn);
+    return (long long)frames;
+}
 float hc_stft_root_f32(float scale) { return stft_root_f32(scale); }
 double hc_stft_root_f64(double scale) { return stft_root_f64(scale); }
 // out: [nperseg] interleaved (re, im)

@@ -123,6 +123,78 @@ inline StftHopFrame stft_hop_frame_at(const StftHopWork &w, int64_t g) {
     return stft_hop_frame_at(w.frame_first.data(), w.pool_seg.data(), w.lp.data(), (int)w.lp.size(), w.N, w.k, g);
 }
 
+// ---- rt_fetch_record_estimates: one row per record from the frames (record_estimates, rt_record_estimates.h) ----
+// The frames are the hop entry's, so the prefix and lp are StftHopWork's.  On top of them a record has, per part, the frames that
+// lie wholly INSIDE its own cells -- start * N <= position and position + N <= end * N.  A part's positions rise by h, so its
+// inside frames are one run [lo, hi) of the record's frame indices (part 0: 0 .. Fp, part 1: Fp .. F), an empty run being lo == hi;
+// `base` is the position of each part's first frame (first_seg * N, max(first_seg, 0) * N) and `fmod` the turn-back index fi mod k.
+struct EstimatesWork {
+    int N = 0, k = 0;
+    std::vector<int64_t> frame_first;  // [n + 1] StftHopWork::frame_first
+    std::vector<int32_t> lp;           // [n] StftHopWork::lp
+    std::vector<int32_t> range;        // [n][4] lo0, hi0, lo1, hi1: frame indices inside the record
+    std::vector<int64_t> base;         // [n][2] position of frame 0 of part 0 and of part 1, relative to sample 0 of the call's buffer
+    std::vector<int32_t> fmod;         // [n] fi mod k
+};
+
+// The run [lo, hi) of j in 0 .. F with start * N <= (seg0 * N + j h) and (seg0 * N + j h) + N <= end * N, h = N / k: positions are
+// whole hops, so the bounds are (start - seg0) k and (end - 1 - seg0) k + 1, clamped.
+inline void estimates_inside(int64_t seg0, int64_t F, int64_t start, int64_t end, int k, int64_t *lo, int64_t *hi) {
+    *lo = std::min(std::max((start - seg0) * k, (int64_t)0), F);
+    *hi = std::min(std::max((end - 1 - seg0) * k + 1, (int64_t)0), F);
+    if (*hi < *lo) *hi = *lo;
+}
+
+// `offsets`, `first_seg`, `fi` as stft_hop_build_work takes them; `start`, `end` [n]: the records' cells.  Returns the call's
+// frames, or -1 for what stft_hop_build_work refuses, for start > end, for a record of more than INT32_MAX frames and for a run
+// that leaves its part: nothing is launched from such a list.
+inline int64_t estimates_build_work(const int64_t *offsets, const int32_t *first_seg, const int32_t *fi, const int32_t *start, const int32_t *end,
+                                    size_t n, int N, int k, EstimatesWork *w) {
+    StftHopWork hop;
+    const int64_t frames = stft_hop_build_work(offsets, first_seg, fi, n, N, k, &hop);
+    if (frames < 0 || (n && (!start || !end))) return -1;
+    if (w) {
+        w->N = N;
+        w->k = k;
+        w->frame_first = hop.frame_first;
+        w->lp = hop.lp;
+        w->range.assign(4 * n, 0);
+        w->base.assign(2 * n, 0);
+        w->fmod.assign(n, 0);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (start[i] > end[i]) return -1;
+        const int64_t F = hop.frame_first[i + 1] - hop.frame_first[i], Fp = stft_hop_part_frames(hop.lp[i], k);
+        if (F > INT32_MAX) return -1;
+        const int64_t seg0[2] = {(int64_t)first_seg[i], std::max<int64_t>(first_seg[i], 0)};
+        int64_t lo[2], hi[2];
+        estimates_inside(seg0[0], Fp, start[i], end[i], k, &lo[0], &hi[0]);
+        estimates_inside(seg0[1], F - Fp, start[i], end[i], k, &lo[1], &hi[1]);
+        lo[1] += Fp;
+        hi[1] += Fp;
+        if (lo[0] < 0 || hi[0] > Fp || lo[1] < Fp || hi[1] > F || lo[0] > hi[0] || lo[1] > hi[1]) return -1;
+        if (w) {
+            for (int p = 0; p < 2; ++p) {
+                w->range[4 * i + 2 * p] = (int32_t)lo[p];
+                w->range[4 * i + 2 * p + 1] = (int32_t)hi[p];
+                w->base[2 * i + p] = seg0[p] * N;
+            }
+            w->fmod[i] = fi[i] % k;
+        }
+    }
+    return frames;
+}
+
+// the turn-back table: (cos, sin) of 2 pi m / k for m = 0 .. k - 1; R is multiplied by cos - i sin.  The angle is formed as
+// NumPy forms -2j * pi * m / k, so the factors are record_fine's (cos is even, sin odd in every libm).
+inline void estimates_turn_table(int k, double *cs /* [2 k] */) {
+    for (int m = 0; m < k; ++m) {
+        const double x = 2.0 * 3.141592653589793 * (double)m / (double)k;
+        cs[2 * m] = std::cos(x);
+        cs[2 * m + 1] = std::sin(x);
+    }
+}
+
 // sqrt(scale), the factor between the windowed transform and a value: evaluated in float64, and on a float32 handle rounded once
 inline float stft_root_f32(float scale) { return (float)std::sqrt((double)scale); }
 inline double stft_root_f64(double scale) { return std::sqrt(scale); }
