@@ -1827,7 +1827,7 @@ __global__ __launch_bounds__(256) void plan_pass_b(const uint16_t *full, uint16_
 // Writes need[t] = C[t] | C[t+1] for the tile's rows and appends the rows with any bit set to the stream's segment list
 // (order irrelevant: the detection sorts its cells).
 // The 16-bit words of four neighbouring lanes are handled as one 64-bit word (the operations are bitwise, lg is a multiple of
-// 16): a row is w = lg / 4 words.
+// 4: 4 and 8 at nperseg 64 and 128, 16 ... 256 from nperseg 256 on): a row is w = lg / 4 words, 1 ... 64.
 //
 // Streaming form, no LDS passes: a lane owns one word column of one tile of rows and walks it upwards in time with two
 // bit-sliced counters (K bit planes of 64 independent counters each):
@@ -1852,7 +1852,7 @@ __global__ __launch_bounds__(64) void plan_runs(const uint16_t *hot, uint16_t *n
     using u64 = unsigned long long;
     const int s = blockIdx.x, lane = threadIdx.x;  // (streams along x: a grid's y extent ends at 65 535)
     if (absent && absent[s] != 0) return;  // (the whole wave: the bit scan left this stream alone, its segment count stays zero)
-    const int w = lg / 4;                     // 64-bit words per row (4 .. 64)
+    const int w = lg / 4;                     // 64-bit words per row (1 .. 64)
     const int tpw = 64 / w;                   // tiles per wave
     const int c = lane % w, tj = lane / w;
     const int B = tile_rows;
