@@ -749,6 +749,52 @@ typedef struct rt_record_estimate {
 
 int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out);
 
+/*
+ * ---- input statistics: level, DC and clipping of every stream's raw input (additive within ABI version 6) ----
+ * Everything above describes a buffer's spectrum; this describes the buffer.  A radio at fixed gain clips, a dead one delivers
+ * constant bytes instead of no callbacks, and a record only exists where the detection worked -- so the caller wants, per stream
+ * and call: how many components sat at full scale, the level, the DC, whether the samples still move.  With the feature on every
+ * rt_process* reads its input once more on the device (one streaming kernel and a fold, on the scan's stream, in front of the
+ * scan) and leaves one 64-byte row per stream in pinned host memory; rt_fetch_input_stats copies the rows.
+ *   - a RAW COMPONENT is, per input format: uint8 2 b - 255 (an odd integer; (2 b - 255) / 255 is exactly b / 127.5 - 1); int8 and
+ *     int16 the integer itself; complex64 / complex128 the value.  value = raw / unit.
+ *   - integer formats: the three sums are exact integers of 64 bits, converted to double once, so every field is
+ *     (double)(the exact sum) at any buffer length; peak is exact.
+ *   - float formats: every sum is formed in float64 over the FINITE components alone, in an order that depends on the sample index
+ *     and nothing else -- not on the pointer's alignment, the stride, the lanes, the _host entries -- so the same samples give
+ *     the same bytes in all of them, and from run to run.  A NaN or an infinite component is counted in n_nonfinite and takes part
+ *     in nothing else.
+ *   - rt_set_input_stats(h, on): on != 0 turns the feature on, 0 off.  RT_E_INVALID ("pending") while unfetched calls are pending,
+ *     as rt_set_record_iq.  Every handle kind: float32 in every mode, nperseg and lane count, chained (every link is a stream),
+ *     float64 dense and with RT_FLAG_F64_SPARSE / RT_FLAG_F64_RESCUE.  The first call that turns it on allocates the partial rows
+ *     and the pinned rows of the two call slots (RT_E_NOMEM); a handle on which it was never on allocates, copies and launches
+ *     exactly what it did without this entry.
+ *   - rt_fetch_input_stats(h, out, n): `out` HOST memory, n == n_streams rows, of the call the last rt_fetch / rt_fetch_f64
+ *     delivered (RT_OK or RT_E_CAPACITY).  Valid until the next rt_process*, rt_extract*, rt_reset or rt_set_input_stats on the
+ *     handle; with two calls in flight: process k, process k + 1, fetch k, stats k.  RT_E_INVALID: a null handle or `out`, a wrong
+ *     n, the feature off, no delivered call, a delivered call enqueued before the feature was on, a delivered rt_extract*.  A
+ *     laned handle gathers its lanes' rows in stream order.
+ *   - a stream absent from the call (rt_set_present) has n_samples 0, zero counts and sums, peak 0; format and unit are set.
+ *   - the rows are computed once, at enqueue, from ALL n_samples (the remainder past the last whole segment included; a call of
+ *     fewer than nperseg samples has rows too).  What rt_fetch analyses again -- AUTO's level-ups, the partial dense re-run, pool
+ *     and capacity growth, the detrend guard, the float64 rescue -- does not recompute them; a failed rt_process* leaves none.
+ *     The analysis itself is the same bytes with the feature on or off.
+ */
+typedef struct rt_input_stats {
+    int64_t n_samples;     /* samples of this stream the call covered; 0 for a stream absent from the call                       */
+    int64_t n_rail;        /* components (I and Q counted separately) at full scale: uint8 0 or 255; int8 -128 or 127; int16
+                              -32768 or 32767; complex64 / complex128: finite with |c| >= 1.0                                     */
+    int64_t n_nonfinite;   /* NaN or +-Inf components (0 for the integer formats)                                                */
+    double sum_i, sum_q;   /* sums of the raw components                                                                          */
+    double sum_sq;         /* sum of I * I + Q * Q, raw                                                                           */
+    double peak;           /* max |raw component|, 0 if there is none                                                             */
+    int32_t format;        /* the call's input format: 0 complex, 1 uint8, 2 int16, 3 int8                                        */
+    int32_t unit;          /* raw full scale: uint8 255, int8 128, int16 32768, complex 1                                         */
+} rt_input_stats;          /* 64 bytes */
+
+int rt_set_input_stats(rt_handle *h, int32_t on);
+int rt_fetch_input_stats(rt_handle *h, rt_input_stats *out, size_t n);
+
 /* Plain device-memory helpers so that a host without its own HIP binding
  * (ctypes-only integration) can stage IQ: thin hipMalloc/hipFree/hipMemcpy. */
 int rt_dev_alloc(int32_t device, size_t bytes, void **out);

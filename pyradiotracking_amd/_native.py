@@ -112,6 +112,22 @@ ESTIMATE_DTYPE = np.dtype(
 )
 assert ESTIMATE_DTYPE.itemsize == 72
 
+#: numpy view of ``rt_input_stats`` (64 bytes): a row of ``rt_fetch_input_stats``
+INPUT_STATS_DTYPE = np.dtype(
+    [
+        ("n_samples", "<i8"),
+        ("n_rail", "<i8"),
+        ("n_nonfinite", "<i8"),
+        ("sum_i", "<f8"),
+        ("sum_q", "<f8"),
+        ("sum_sq", "<f8"),
+        ("peak", "<f8"),
+        ("format", "<i4"),
+        ("unit", "<i4"),
+    ]
+)
+assert INPUT_STATS_DTYPE.itemsize == 64
+
 
 class RtConfigF64(C.Structure):
     """``rt_config_f64``: the float64 window / scale / thresholds / calibration of a float64 handle (``rt_create_f64``)."""
@@ -191,6 +207,8 @@ ABI_SYMBOLS = (
     "rt_fetch_record_stft_hop",
     "rt_fetch_record_stft_hop_f64",
     "rt_fetch_record_estimates",
+    "rt_set_input_stats",
+    "rt_fetch_input_stats",
 )
 
 _lib = None
@@ -270,6 +288,8 @@ def load_library(path: Optional[str] = None):
     for fn in (lib.rt_fetch_record_stft_hop, lib.rt_fetch_record_stft_hop_f64):
         fn.argtypes = [vp, C.c_int32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.rt_fetch_record_estimates.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.rt_set_input_stats.argtypes = [vp, C.c_int32]
+    lib.rt_fetch_input_stats.argtypes = [vp, vp, C.c_size_t]
     for name in ABI_SYMBOLS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     if path is None:
@@ -673,6 +693,17 @@ class NativeAnalyzer:
         out = np.zeros(n.value, dtype=ESTIMATE_DTYPE)
         if n.value:
             self._check(self._lib.rt_fetch_record_estimates(self._handle, int(hop_div), out.ctypes.data, out.size, C.byref(n)))
+        return out
+
+    def set_input_stats(self, on: bool):
+        """``rt_set_input_stats``: every later ``rt_process*`` also leaves one ``INPUT_STATS_DTYPE`` row per stream, computed
+        on the device from the raw input (``fetch_input_stats``); refused while calls are pending."""
+        self._check(self._lib.rt_set_input_stats(self._handle, 1 if on else 0))
+
+    def fetch_input_stats(self) -> np.ndarray:
+        """``rt_fetch_input_stats``: ``[n_streams]`` ``INPUT_STATS_DTYPE`` rows of the call ``fetch`` delivered last."""
+        out = np.zeros(self.n_streams, dtype=INPUT_STATS_DTYPE)
+        self._check(self._lib.rt_fetch_input_stats(self._handle, out.ctypes.data, out.size))
         return out
 
     def fetch_row_means(self) -> np.ndarray:

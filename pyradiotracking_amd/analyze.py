@@ -239,6 +239,32 @@ FINE_DTYPE = np.dtype([("offset_hz", np.float64), ("coherence", np.float64), ("n
 #: a row of :meth:`BatchSignalAnalyzer.fetch_record_estimates`: what ``record_fine`` and ``record_edges`` give, reduced on the device
 ESTIMATES_DTYPE = np.dtype([("offset_hz", np.float64), ("coherence", np.float64), ("n_pairs", np.int32), ("level", np.float64), ("rise", np.float64),
                             ("fall", np.float64), ("n_inside", np.int32), ("r", np.complex128), ("pair_mag", np.float64)])
+#: a row of :func:`input_levels`: what an operator reads off :meth:`BatchSignalAnalyzer.fetch_input_stats`
+LEVELS_DTYPE = np.dtype([("dc_i", np.float64), ("dc_q", np.float64), ("power_dbfs", np.float64), ("rail_fraction", np.float64), ("peak", np.float64),
+                         ("nonfinite", np.int64)])
+
+
+def input_levels(stats) -> np.ndarray:
+    """One ``LEVELS_DTYPE`` row per row of ``stats`` (``_native.INPUT_STATS_DTYPE``, :meth:`BatchSignalAnalyzer.fetch_input_stats`),
+    in VALUE units (raw / ``unit``: full scale is 1): ``dc_i``, ``dc_q`` the mean of each component, ``power_dbfs`` =
+    ``10 log10(sum_sq / (n unit^2))`` (0 dBFS: a complex tone of amplitude 1; both components square from rail to rail: +3 dB; -inf for silence), ``rail_fraction`` =
+    ``n_rail / (2 n)`` the share of components at full scale, ``peak`` the largest ``|component|``, ``nonfinite`` the NaN and
+    infinite components.  The means are over all ``2 n`` components' slots, the non-finite ones counting as absent values; a
+    stream without samples (``n_samples == 0``: absent from the call, or an empty buffer) has NaN in every float field."""
+    st = np.atleast_1d(np.asarray(stats))
+    out = np.zeros(st.shape, dtype=LEVELS_DTYPE)
+    n = st["n_samples"].astype(np.float64)
+    unit = st["unit"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["dc_i"] = st["sum_i"] / (n * unit)
+        out["dc_q"] = st["sum_q"] / (n * unit)
+        out["power_dbfs"] = 10.0 * np.log10(st["sum_sq"] / (n * unit * unit))
+        out["rail_fraction"] = st["n_rail"] / (2.0 * n)
+        out["peak"] = st["peak"] / unit
+    out["nonfinite"] = st["n_nonfinite"]
+    for name in ("dc_i", "dc_q", "power_dbfs", "rail_fraction", "peak"):
+        out[name][st["n_samples"] == 0] = np.nan
+    return out
 
 
 def _stft_frames(offsets, first_segment, nperseg: int, hop_div: int):
@@ -420,9 +446,14 @@ class BatchSignalAnalyzer:
         chain: int = 0,
         record_iq: bool = False,
         record_iq_margin: int = 0,
+        input_stats: bool = False,
         **kwargs,
     ):
-        """``record_iq`` (``rt_set_record_iq``): keep the sample tail of every stream's previous buffer, so that
+        """``input_stats`` (``rt_set_input_stats``): every enqueued buffer is also read once by a streaming kernel of its own that
+        leaves, per stream, the level, DC, clipping and non-finite counts of the RAW input (:meth:`fetch_input_stats`,
+        :func:`input_levels`).  On every kind of analyzer; the analysis itself is unchanged.
+
+        ``record_iq`` (``rt_set_record_iq``): keep the sample tail of every stream's previous buffer, so that
         :meth:`fetch_record_iq` can hand out the IQ samples behind every record of a call, ``record_iq_margin`` whole segments
         on either side included.  On every kind of analyzer (any ``mode``, ``lanes``, ``chain``, ``precision``).
 
@@ -621,6 +652,9 @@ class BatchSignalAnalyzer:
             if not 0 <= self.record_iq_margin <= 1024:
                 raise ValueError("record_iq_margin must be 0 ... 1024 segments")
             self._native.set_record_iq(self.record_iq_margin)
+        self.input_stats = bool(input_stats)
+        if self.input_stats:
+            self._native.set_input_stats(True)
         self._decoder = _RecordDecoder(fft_nperseg, sample_rate, self.center_freq, self.calibration_db, f64=f64)
         self.decoder = self._decoder  # record -> field conversion, shared with pyradiotracking_amd.match
         self.gpu = gpu
@@ -1059,6 +1093,22 @@ class BatchSignalAnalyzer:
         rec = self._native._last_fetched
         return record_fine(offsets, first, values, rec["start"], rec["end"], self.sample_rate, self.fft_nperseg, hop_div, rec["fi"])
 
+    def set_input_stats(self, on: bool) -> None:
+        """Turn the per-stream input statistics on or off (``rt_set_input_stats``) between calls: ``NativeError``
+        (``RT_E_INVALID``) while enqueued buffers are unfetched.  A buffer enqueued while they were off has none."""
+        self._native.set_input_stats(bool(on))
+        self.input_stats = bool(on)
+
+    def fetch_input_stats(self) -> np.ndarray:
+        """``[S]`` rows of ``_native.INPUT_STATS_DTYPE`` for the buffer of the call :meth:`fetch_records` (or
+        :meth:`process_batch`) returned last, computed on the device from ALL its samples when it was enqueued: ``n_samples``,
+        ``n_rail`` (components at full scale), ``n_nonfinite``, the sums ``sum_i``, ``sum_q``, ``sum_sq`` of the raw components
+        and their squares, ``peak``, and the ``format`` / ``unit`` that turn raw into values (:func:`input_levels` does).  Exact
+        for the integer formats; for complex input the same samples give the same bytes however they are laid out or split into
+        lanes.  A stream that sat the call out (:meth:`set_present`) has ``n_samples == 0``.  Needs ``input_stats=True``; raises
+        ``NativeError`` (``RT_E_INVALID``) once another buffer was enqueued or the analyzer reset, and after ``extract_signals``."""
+        return self._native.fetch_input_stats()
+
     def fetch_row_means(self, dbw: bool = False) -> np.ndarray:
         """``[S, fft_nperseg]`` (float32, float64 with ``precision="float64"``): every bin's row mean -- ``freq_avg``, the
         reference's noise figure (analyze.py:373-375) -- over the buffer of the call :meth:`fetch_records` (or
@@ -1164,9 +1214,13 @@ class SignalAnalyzer:
         record_iq_margin: int = 0,
         stft_hop_div: int = 1,
         record_estimates: bool = False,
+        input_stats: bool = False,
         **kwargs,
     ):
-        """``record_iq=True``: after every buffer ``signal_iq`` is the list of the sample arrays of the signals put on the queue
+        """``input_stats=True``: after every buffer ``input_stats`` holds the row of
+        :meth:`BatchSignalAnalyzer.fetch_input_stats` for the buffer just analysed (:func:`input_levels` turns it into levels).
+
+        ``record_iq=True``: after every buffer ``signal_iq`` is the list of the sample arrays of the signals put on the queue
         (unshadowed, queue order, like ``signal_data``) -- the IQ of each pulse in the format the buffer came in, with
         ``record_iq_margin`` whole segments on either side (:meth:`BatchSignalAnalyzer.fetch_record_iq`), and ``signal_stft`` the
         list of their complex STFT values: one per delivered segment, or with ``stft_hop_div=k`` one per frame every
@@ -1196,6 +1250,8 @@ class SignalAnalyzer:
             raise ValueError("record_estimates needs record_iq=True")
         self.record_estimates = bool(record_estimates)
         self.signal_estimates: Optional[np.ndarray] = None  # (beside signal_stft: one ESTIMATES_DTYPE row per signal)
+        self._input_stats_on = bool(input_stats)
+        self.input_stats: Optional[np.void] = None  # (the buffer's own level, DC and clipping: one INPUT_STATS_DTYPE row)
         self.calibration_db = calibration_db
         try:
             self.device_index = int(device)  # analyze.py:89-91
@@ -1255,6 +1311,7 @@ class SignalAnalyzer:
             record_cells=self.record_cells,
             record_iq=self.record_iq,
             record_iq_margin=self.record_iq_margin,
+            input_stats=self._input_stats_on,
             f64_sparse=bool(f64_sparse),
             f64_rescue=bool(f64_rescue),
             # capacities of the native handle (no counterpart in the reference, whose lists are unbounded)
@@ -1320,7 +1377,7 @@ class SignalAnalyzer:
         ts_start = self._clock(n)
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = self.input_stats = None
         self._batch.enqueue_bytes(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1344,7 +1401,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = self.input_stats = None
         self._batch.enqueue_int16(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1368,7 +1425,7 @@ class SignalAnalyzer:
         if n > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
         ts_start = self._clock(n)
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = self.input_stats = None
         self._batch.enqueue_int8(raw.reshape(1, -1))
         rec = self._batch.fetch_records()
         self._keep_noise()
@@ -1383,7 +1440,7 @@ class SignalAnalyzer:
         buf = np.ascontiguousarray(buffer, dtype=np.complex128 if self.precision == "float64" else np.complex64).reshape(1, -1)
         if buf.shape[1] > self._batch.sdr_callback_length:
             raise ValueError("buffer longer than sdr_callback_length")
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = self.input_stats = None
         if self.record_cells or self.record_iq:  # (process_batch, with the records kept for the cells' shadow flags)
             self._batch.enqueue(buf)
             rec = self._batch.fetch_records()
@@ -1473,6 +1530,8 @@ class SignalAnalyzer:
     def _keep_noise(self):
         if self.row_means:
             self.noise_dbw = self._batch.fetch_row_means(dbw=True)[0]
+        if self._input_stats_on:
+            self.input_stats = self._batch.fetch_input_stats()[0]
 
     def _keep_cells(self, keep):
         """``signal_data``: the cells of the records ``keep`` selects (those whose signals go to the queue), in their order."""
@@ -1507,7 +1566,7 @@ class SignalAnalyzer:
         dense detect kernel (``rt_extract``).  The time axis must be the one
         SciPy produces for ``fft_nperseg`` / ``sample_rate`` (hop = nperseg/fs);
         ``freqs`` is used as given."""
-        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = None  # (the caller holds this map: no row means, no cells of it)
+        self.noise_dbw = self.signal_data = self.signal_iq = self.signal_stft = self.signal_estimates = self.input_stats = None  # (the caller holds this map: no row means, no cells of it)
         spec = np.asarray(spectrogram)
         n_bins, n_seg = spec.shape
         if n_seg == 0:

@@ -41,6 +41,7 @@
 #include "rt_record_stft.h"
 #include "rt_record_stft_hop.h"
 #include "rt_record_estimates.h"
+#include "rt_input_stats.h"
 #include "rt_record_stft_book.h"
 #include "rt_ledger.h"
 #include "rt_tables.h"
@@ -284,6 +285,20 @@ struct RecordIq {
     float *d_stft_win = nullptr; // [N] float32 handle: the window as the caller gave it (a float64 handle's is F64State::d_window)
 };
 
+// rt_set_input_stats (rt_input_stats.h): nothing of it exists until the entry turns the feature on.  One per lane-less handle,
+// float32 or float64; a laned handle's lanes each own theirs.  A call slot's partial rows, its pinned rows, and the number of the
+// call whose rows they are (0: none -- the slot's call was enqueued with the feature off, or failed to enqueue).
+struct InputStatsSlot {
+    void *d_parts = nullptr;            // [S][max_chunks] InputStatsPart
+    rt_input_stats *h_rows = nullptr;   // [S] pinned, device-visible: input_stats_fold writes them
+    uint64_t seq = 0;
+};
+struct InputStatsState {
+    bool on = false;
+    int max_chunks = 0;  // chunks of rt_config.max_samples
+    InputStatsSlot slot[kSlots];
+};
+
 }  // namespace
 
 struct rt_handle {
@@ -378,6 +393,7 @@ struct rt_handle {
     F64State *f64 = nullptr;  // a float64 handle (rt_create_f64): nothing above but cfg, N, s_scan, err and info is used
     RecordIq *riq = nullptr;  // rt_set_record_iq (float32 and float64 handles; a laned handle: its lanes hold theirs)
     int iq_margin = -1;       // ... the margin in force, -1: off (the one thing a laned handle keeps itself)
+    InputStatsState *ist = nullptr;  // rt_set_input_stats (float32 and float64 handles; a laned handle: its lanes hold theirs)
     std::vector<float> h_window;  // float32 handle: rt_config.window as given (the scans' d_window is times sqrt(scale)): rt_fetch_record_stft uploads it at first need
 };
 
@@ -2039,6 +2055,62 @@ int fetch_record_estimates_impl(rt_handle *h, const char *entry, int32_t hop_div
     return RT_OK;
 }
 
+// ---- rt_set_input_stats: the call's rows, at enqueue (rt_input_stats.h) ----
+// On the scan's stream, in front of the scan, where the call's IQ is in place (the staged copy of the _host entries included) and
+// the call's presence rows are on the device.  `d_absent`: row kMaskAbsent of the call's mask, or null.  The slot's rows are no
+// call's from here on; the caller marks them the new call's once the whole call is enqueued.
+template <int FMT>
+void launch_input_stats(const InputStatsArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL((input_stats<FMT>), dim3((unsigned)a.n_streams * (unsigned)a.n_chunks), dim3(kInputStatsBlock), 0, st, a);
+}
+int enqueue_input_stats(rt_handle *h, int idx, const void *iq, int64_t n_samples, int64_t stream_stride, int fmt, const int32_t *d_absent) {
+    InputStatsState &q = *h->ist;
+    InputStatsSlot &qs = q.slot[idx];
+    qs.seq = 0;
+    const int kfmt = (h->f64 && fmt == kFmtC64) ? kStatsC128 : fmt;
+    static_assert(kStatsC64 == kFmtC64 && kStatsU8 == kFmtU8 && kStatsI16 == kFmtI16 && kStatsI8 == kFmtI8, "one numbering of the input formats");
+    InputStatsArgs a{};
+    a.iq = static_cast<const char *>(iq);
+    a.stream_stride = stream_stride;
+    a.n_samples = n_samples;
+    a.n_streams = h->cfg.n_streams;
+    a.n_chunks = (int32_t)((n_samples + kInputStatsChunk - 1) / kInputStatsChunk);
+    a.absent = d_absent;
+    a.parts = qs.d_parts;
+    a.rows = qs.h_rows;
+    if (a.n_chunks > q.max_chunks || (int64_t)a.n_streams * a.n_chunks > 0x7FFFFFFFll) {
+        h->err = "input_stats: internal: more chunks than rt_config.max_samples holds";
+        return RT_E_HIP;
+    }
+    if (a.n_chunks > 0) {
+        switch (kfmt) {
+        case kStatsC64: launch_input_stats<kStatsC64>(a, h->s_scan); break;
+        case kStatsU8: launch_input_stats<kStatsU8>(a, h->s_scan); break;
+        case kStatsI16: launch_input_stats<kStatsI16>(a, h->s_scan); break;
+        case kStatsI8: launch_input_stats<kStatsI8>(a, h->s_scan); break;
+        default: launch_input_stats<kStatsC128>(a, h->s_scan); break;
+        }
+    }
+    const dim3 grid((unsigned)((a.n_streams + kInputStatsBlock - 1) / kInputStatsBlock));
+    if (stats_is_float(kfmt)) hipLaunchKernelGGL((input_stats_fold<double>), grid, dim3(kInputStatsBlock), 0, h->s_scan, a, kfmt);
+    else hipLaunchKernelGGL((input_stats_fold<int64_t>), grid, dim3(kInputStatsBlock), 0, h->s_scan, a, kfmt);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        h->err = std::string("input_stats: ") + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    return RT_OK;
+}
+void input_stats_free(rt_handle *h) {
+    if (!h->ist) return;
+    for (InputStatsSlot &qs : h->ist->slot) {
+        (void)hipFree(qs.d_parts);
+        (void)hipHostFree(qs.h_rows);
+    }
+    delete h->ist;
+    h->ist = nullptr;
+}
+
 int claim_slot(rt_handle *h, Slot **out, CallCtx *saved) {
     Slot &sl = h->slot[h->n_calls % kSlots];
     // the slot's previous call may still be in its detection (a stream of its own): what is enqueued from here on waits for it
@@ -2329,6 +2401,7 @@ void rt_destroy(rt_handle *h) {
     (void)hipSetDevice(h->cfg.device);
     (void)hipDeviceSynchronize();
     iq_free(h);
+    input_stats_free(h);
     (void)hipFree(h->d_work);
     (void)hipFree(h->d_twg);
     (void)hipFree(h->d_cwin);
@@ -3030,6 +3103,12 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
         } else if (!lc.took.empty()) {
             std::memcpy(sl.h_no_last, lc.took.data(), (size_t)S * sizeof(int32_t));  // (lock-step: the streams that take a reset)
         }
+        if (h->ist && h->ist->on) {
+            // rt_set_input_stats: the rows of the raw input, once per call (no re-analysis inside rt_fetch comes through here)
+            launched = true;  // (the slot's rows are rewritten from here on)
+            const int rci = enqueue_input_stats(h, idx, iq_dev, n_samples, stream_stride, fmt, lc.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr);
+            if (rci != RT_OK) return rci;
+        }
         c.mode_used = h->ap.begin_call(h->cfg.mode, (uint64_t)kBuckets * (uint64_t)h->hot_cap, (uint64_t)T * (uint64_t)h->N);
         if (T == 0) {
             // empty spectrogram: no signals; `_spectrogram_last` becomes an empty map
@@ -3062,6 +3141,7 @@ static int process_impl(rt_handle *h, const void *iq_dev, int64_t n_samples, int
     }
     c.pending = true;
     h->n_calls++;
+    if (h->ist && h->ist->on) h->ist->slot[&sl - h->slot].seq = c.seq;  // (the slot's rows are this call's)
     return RT_OK;
 }
 
@@ -3919,6 +3999,94 @@ int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate 
     return fetch_record_estimates_impl(h, "rt_fetch_record_estimates", hop_div, out, cap, n_out);
 }
 
+// ---- rt_set_input_stats / rt_fetch_input_stats (include/rt_analyze.h) ----
+static int set_input_stats_one(rt_handle *h, bool on) {
+    if (h->ist)
+        for (InputStatsSlot &qs : h->ist->slot) qs.seq = 0;  // (whatever rows the slots hold are no delivered call's any more)
+    if (!on) {
+        if (h->ist) h->ist->on = false;
+        return RT_OK;
+    }
+    if (!h->ist) {
+        RT_HIP(h, hipSetDevice(h->cfg.device));
+        InputStatsState *q = new (std::nothrow) InputStatsState();
+        const size_t S = (size_t)h->cfg.n_streams;
+        bool ok = q != nullptr;
+        if (ok) q->max_chunks = (int)std::max<int64_t>(1, (h->cfg.max_samples + kInputStatsChunk - 1) / kInputStatsChunk);
+        for (int i = 0; i < kSlots && ok; ++i)
+            ok = hipMalloc(&q->slot[i].d_parts, S * (size_t)q->max_chunks * sizeof(InputStatsPart<double>)) == hipSuccess &&
+                 hipHostMalloc(reinterpret_cast<void **>(&q->slot[i].h_rows), S * sizeof(rt_input_stats)) == hipSuccess;
+        h->ist = q;
+        if (!ok) {
+            (void)hipGetLastError();
+            input_stats_free(h);
+            h->err = "rt_set_input_stats: no memory for the partial rows and the pinned rows";
+            return RT_E_NOMEM;
+        }
+    }
+    h->ist->on = true;
+    return RT_OK;
+}
+
+int rt_set_input_stats(rt_handle *h, int32_t on) {
+    if (!h) return RT_E_INVALID;
+    bool pending = false;
+    if (h->f64) {
+        for (const F64Slot &sl : h->f64->slot) pending = pending || sl.pending;
+    } else {
+        pending = h->kids.empty() && oldest_pending(h);
+        for (rt_handle *k : h->kids) pending = pending || oldest_pending(k);
+    }
+    if (pending) {
+        h->err = "rt_set_input_stats with unfetched calls pending: fetch them first";
+        return RT_E_INVALID;
+    }
+    if (!h->kids.empty()) {
+        const int rc = for_each_lane(h, [&](rt_handle *k, int64_t) { return set_input_stats_one(k, on != 0); });
+        if (rc != RT_OK)
+            for (rt_handle *k : h->kids) (void)set_input_stats_one(k, false);  // (no lane keeps what another could not get)
+        return rc;
+    }
+    return set_input_stats_one(h, on != 0);
+}
+
+// why a lane-less handle (or a lane) has no rows to hand out, or null: *slot holds them
+static const char *input_stats_refused(const rt_handle *h, int *slot) {
+    const InputStatsState *q = h->ist;
+    if (!q || !q->on) return "the feature is off (rt_set_input_stats)";
+    const int rm = h->f64 ? h->f64->rm_slot : h->rm_slot;
+    if (rm == kRowMeansExtract) return "the call fetched last was an rt_extract: it has no input";
+    if (rm < 0) return "no call delivered by rt_fetch since the last rt_process*, rt_extract, rt_reset or rt_set_input_stats";
+    const uint64_t seq = h->f64 ? h->f64->slot[rm].seq : h->slot[rm].call.seq;
+    if (q->slot[rm].seq == 0 || q->slot[rm].seq != seq) return "the call fetched last was enqueued before the feature was on";
+    *slot = rm;
+    return nullptr;
+}
+
+int rt_fetch_input_stats(rt_handle *h, rt_input_stats *out, size_t n) {
+    if (!h) return RT_E_INVALID;
+    const char *why = nullptr;
+    if (!out) why = "null output";
+    else if (n != (size_t)h->cfg.n_streams) why = "n must be n_streams";
+    // every lane is checked before anything is written
+    std::vector<rt_handle *> lanes = h->kids;
+    if (lanes.empty()) lanes.push_back(h);
+    std::vector<int> slots(lanes.size(), 0);
+    for (size_t i = 0; i < lanes.size() && !why; ++i) why = input_stats_refused(lanes[i], &slots[i]);
+    if (why) {
+        h->err = std::string("rt_fetch_input_stats: ") + why;
+        return RT_E_INVALID;
+    }
+    // (the fold wrote the pinned rows in front of the call's scan, and the delivering rt_fetch waited for the call's end)
+    size_t s0 = 0;
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const size_t S = (size_t)lanes[i]->cfg.n_streams;
+        std::memcpy(out + s0, lanes[i]->ist->slot[slots[i]].h_rows, S * sizeof(rt_input_stats));
+        s0 += S;
+    }
+    return RT_OK;
+}
+
 int rt_get_call_info(rt_handle *h, rt_call_info *info) {
     if (!h || !info) return RT_E_INVALID;
     *info = h->info;
@@ -4325,6 +4493,7 @@ static void destroy_f64(rt_handle *h) {
     (void)hipSetDevice(h->cfg.device);
     (void)hipDeviceSynchronize();
     iq_free(h);
+    input_stats_free(h);
     for (F64Slot &sl : f->slot) {
         (void)hipFree(sl.d_raw);
         (void)hipFree(sl.d_raw_count);
@@ -4424,8 +4593,11 @@ static int process_f64(rt_handle *h, const void *iq, int64_t n_samples, int64_t 
         return RT_OK;
     };
     rc = upload();
+    const bool stats = h->ist && h->ist->on;
+    if (rc == RT_OK && stats) rc = enqueue_input_stats(h, idx, sl.iq, n_samples, stream_stride, fmt, lc.masked ? sl.d_mask + (size_t)kMaskAbsent * S : nullptr);
     if (rc == RT_OK) rc = f64_start(h, sl);
     if (rc != RT_OK) h->ledger.rollback(lc);
+    else if (stats) h->ist->slot[idx].seq = sl.seq;  // (the slot's rows are this call's)
     return rc;
 }
 

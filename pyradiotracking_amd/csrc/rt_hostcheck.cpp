@@ -15,6 +15,7 @@
 
 #include "../../include/rt_analyze.h"
 #include "rt_core.h"
+#include "rt_input_stats.h"
 #include "rt_ledger.h"
 #include "rt_record_stft_book.h"
 #include "rt_tables.h"
@@ -797,6 +798,39 @@ void hc_stft_twiddles_f32(int nperseg, float *out) {
 void hc_stft_twiddles_f64(int nperseg, double *out) {
     const std::vector<cd> tw = record_stft_twiddles<cd, long double>(nperseg);
     std::memcpy(out, tw.data(), tw.size() * sizeof(cd));
+}
+
+// rt_fetch_input_stats (rt_input_stats.h): the chunk length, one stream's row as the kernels form it -- fmt 0 complex64, 1 uint8,
+// 2 int16, 3 int8, 4 complex128; -1: no such format -- and the packed form of the 8-bit rule beside the rule itself on the same
+// words: n_rail, sum_i, sum_q, sum_sq, peak each
+int hc_input_stats_chunk() { return kInputStatsChunk; }
+int hc_input_stats(int fmt, const void *ptr, long long n, rt_input_stats *out) { return input_stats_host(fmt, ptr, (int64_t)n, out) ? 0 : -1; }
+}  // extern "C"
+template <int FMT>
+static void input_stats_words(const uint32_t *x, int n_words, long long *packed, long long *rule) {
+    InputStatsPart<int64_t> a, b;
+    stats_clear(a);
+    stats_clear(b);
+    StatsWords8 w;
+    for (int i = 0; i < n_words; ++i) stats_word8<FMT>(w, x[i]);
+    stats_words8_close<FMT>(a, w);
+    stats_samples_int<FMT>(b, reinterpret_cast<const char *>(x), (int64_t)n_words * 2);
+    const InputStatsPart<int64_t> *const both[2] = {&a, &b};
+    long long *const out[2] = {packed, rule};
+    for (int k = 0; k < 2; ++k) {
+        out[k][0] = both[k]->n_rail;
+        out[k][1] = both[k]->sum_i;
+        out[k][2] = both[k]->sum_q;
+        out[k][3] = both[k]->sum_sq;
+        out[k][4] = both[k]->peak;
+    }
+}
+extern "C" {
+int hc_input_stats_words8(int fmt, const uint32_t *x, int n_words, long long *packed, long long *rule) {
+    if (fmt == kStatsU8) input_stats_words<kStatsU8>(x, n_words, packed, rule);
+    else if (fmt == kStatsI8) input_stats_words<kStatsI8>(x, n_words, packed, rule);
+    else return -1;
+    return 0;
 }
 
 }  // extern "C"
