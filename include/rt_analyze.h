@@ -705,6 +705,43 @@ int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets
                                  double *values, size_t cap_frames, size_t *n_frames); /* float64 handle */
 
 /*
+ * ---- the bins beside each record's bin: 2 w + 1 complex values per FRAME (additive within ABI version 6) ----
+ * rt_fetch_record_stft_hop looks at one bin, rt_record.fi.  What the pulse looks like beside it -- a keyed carrier about
+ * 1 / duration wide or a broadband click, how much energy the neighbour bin holds, where the peak of a record with a single
+ * inside frame lies between bins -- takes the neighbouring bins of the same frames.  This entry delivers them.
+ *   - the call, the records, their order, `first_seg`, the two parts and the frames are exactly those of
+ *     rt_fetch_record_stft_hop at the same `hop_div` = k.  `offsets` counts FRAMES; *n_frames == offsets[n_records].
+ *   - `hop_div`: 1 <= k <= 16 and N % k == 0 (N = nperseg).  `half_width`: 0 <= w <= 8 with B = 2 w + 1 <= N.  Anything else is
+ *     RT_E_INVALID, the message names k, w and N, and it is refused before anything is launched or copied.
+ *   - `values`: HOST memory, cap_frames * B interleaved (re, im) pairs, frame-major.  Column order: column j of a frame belongs
+ *     to d = j - w, and its bin is (fi + d) mod N in the index space of rt_record.fi (fftfreq order).  The band is circular:
+ *     beside bin N - 1 lies bin 0, and beside N / 2 - 1 lies the most negative frequency.  values == NULL or cap_frames == 0: a
+ *     size query.  cap_frames < *n_frames with a buffer: RT_E_CAPACITY, nothing written.
+ *   - a value is rt_fetch_record_stft_hop's formula with the column's bin in place of fi: the same conversions, window,
+ *     sqrt(scale), mean about the frame's first sample, and the phase counted from the frame's start,
+ *         value[j] = sqrt(scale) * sum_n w[n] * (x[n] - mean(x)) * exp(-2 pi i ((fi + j - w) mod N) n / N)
+ *     Per bin the operations and their order are that entry's -- four fmas a sample against the table twiddle, then the group
+ *     butterfly -- so a value depends on the frame's samples and the bin alone.  (The centre bin's products are NOT rotated by
+ *     W^(d n) into the neighbours: cheaper, and it would round differently.)
+ *   - bit identity: (1) column w (d = 0) is the bytes of rt_fetch_record_stft_hop at that k; with half_width == 0 the whole
+ *     output is that entry's.  (2) For two records of one stream whose bins lie d apart, and frames of the same part at the same
+ *     position, column w + d of the one is the bytes of column w of the other.  (3) The same samples give the same bytes on every
+ *     handle kind, on every fetch and in every order of calls.  (4) A frame whose samples are all one finite value is exactly
+ *     0 + 0i in every column.  (5) A non-finite sample makes exactly the frames that cover it non-finite, in every column.
+ *   - lazy: rt_process*, rt_fetch and the other record entries allocate, copy and launch what they do without this one.  The
+ *     entry's first call for a delivered call builds the values for (k, w) in a pool of its own per call slot (it grows on
+ *     demand, its bytes computed in 64 bits, and remembers the (k, w) it holds), by one kernel on the gather's stream, waited
+ *     for.  The same (k, w) again copies; another pair builds again.  The twiddle table and the float32 window copy are the ones
+ *     the STFT entries share, made by whichever entry is called first.
+ *   - validity, RT_E_NOMEM (the handle is left as it was, the bytes are in the message) and every refusal:
+ *     rt_fetch_record_stft_hop's, under this entry's name; the wrong twin is refused too.
+ */
+int rt_fetch_record_band(rt_handle *h, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets, int32_t *first_seg,
+                         size_t n_first, float *values, size_t cap_frames, size_t *n_frames);      /* float32 handle */
+int rt_fetch_record_band_f64(rt_handle *h, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets, int32_t *first_seg,
+                             size_t n_first, double *values, size_t cap_frames, size_t *n_frames); /* float64 handle */
+
+/*
  * ---- per-record estimates from the frames, reduced on the device (additive within ABI version 6) ----
  * What a caller makes of rt_fetch_record_stft_hop's frames is one row per record: the tone's offset from its bin (pulse pair),
  * its coherence, the pulse's level and its rise and fall.  This entry reduces the frames where they lie; they are not copied to the

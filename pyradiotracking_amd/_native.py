@@ -207,6 +207,8 @@ ABI_SYMBOLS = (
     "rt_fetch_record_stft_hop",
     "rt_fetch_record_stft_hop_f64",
     "rt_fetch_record_estimates",
+    "rt_fetch_record_band",
+    "rt_fetch_record_band_f64",
     "rt_set_input_stats",
     "rt_fetch_input_stats",
 )
@@ -288,6 +290,8 @@ def load_library(path: Optional[str] = None):
     for fn in (lib.rt_fetch_record_stft_hop, lib.rt_fetch_record_stft_hop_f64):
         fn.argtypes = [vp, C.c_int32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.rt_fetch_record_estimates.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    for fn in (lib.rt_fetch_record_band, lib.rt_fetch_record_band_f64):
+        fn.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.rt_set_input_stats.argtypes = [vp, C.c_int32]
     lib.rt_fetch_input_stats.argtypes = [vp, vp, C.c_size_t]
     for name in ABI_SYMBOLS:
@@ -694,6 +698,22 @@ class NativeAnalyzer:
         if n.value:
             self._check(self._lib.rt_fetch_record_estimates(self._handle, int(hop_div), out.ctypes.data, out.size, C.byref(n)))
         return out
+
+    def fetch_record_band(self, hop_div: int = 1, half_width: int = 2):
+        """``rt_fetch_record_band`` (``_f64`` on a float64 handle): ``(offsets, first_segment, values)`` of the call ``fetch``
+        delivered last (in full) -- the frames of ``fetch_record_stft(hop_div)``, ``values`` complex64 (complex128)
+        ``[n_frames, 2 * half_width + 1]``: column ``j`` is the bin ``(fi + j - half_width) mod nperseg``."""
+        n_rec = getattr(self, "_n_fetched", 0)
+        k, w = int(hop_div), int(half_width)
+        offsets = np.zeros(n_rec + 1, dtype=np.int64)
+        first = np.zeros(n_rec, dtype=np.int32)
+        n = C.c_size_t(0)
+        fn = self._lib.rt_fetch_record_band_f64 if self.f64 else self._lib.rt_fetch_record_band
+        self._check(fn(self._handle, k, w, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, None, 0, C.byref(n)))
+        values = np.empty((n.value, 2 * w + 1), dtype=np.complex128 if self.f64 else np.complex64)
+        if n.value:
+            self._check(fn(self._handle, k, w, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, values.ctypes.data, n.value, C.byref(n)))
+        return offsets, first, values
 
     def set_input_stats(self, on: bool):
         """``rt_set_input_stats``: every later ``rt_process*`` also leaves one ``INPUT_STATS_DTYPE`` row per stream, computed

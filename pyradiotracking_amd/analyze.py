@@ -381,6 +381,38 @@ def record_edges(offsets, first_segment, values, start, end, nperseg: int, hop_d
     return out
 
 
+def band_bins(fi, half_width: int, nperseg: int) -> np.ndarray:
+    """int64 ``[n, 2 * half_width + 1]``: the bin of every column of :meth:`BatchSignalAnalyzer.fetch_record_band` for records at
+    the bins ``fi`` -- column ``j`` is ``(fi + j - half_width) mod nperseg`` in fftfreq order; the band is circular."""
+    w, N = int(half_width), int(nperseg)
+    if w < 0 or 2 * w + 1 > N:
+        raise ValueError(f"half_width {w} must be >= 0 with 2 * half_width + 1 <= nperseg {N}")
+    return (np.atleast_1d(np.asarray(fi, dtype=np.int64))[:, None] + np.arange(-w, w + 1, dtype=np.int64)[None, :]) % N
+
+
+def record_band_spectrum(offsets, first_segment, values, start, end, nperseg: int, hop_div: int = 1) -> np.ndarray:
+    """float64 ``[n_records, 2 w + 1]``: the pulse's spectrum around its bin -- per column of
+    :meth:`BatchSignalAnalyzer.fetch_record_band` the mean of ``|value| ** 2`` over the frames that lie wholly inside the record's
+    own cells (``start * nperseg <= position`` and ``position + nperseg <= end * nperseg``, the rule of
+    :meth:`BatchSignalAnalyzer.fetch_record_estimates`).  A record without such a frame has a NaN row."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    v = np.asarray(values)
+    if v.ndim != 2:
+        raise ValueError("values must be [n_frames, 2 * half_width + 1], as fetch_record_band returns them")
+    n, N = len(offsets) - 1, int(nperseg)
+    out = np.full((n, v.shape[1]), np.nan)
+    if n == 0 or not len(v):
+        return out
+    rec, _, pos = _stft_frames(offsets, first_segment, N, hop_div)
+    own = (pos >= np.asarray(start, dtype=np.int64)[rec] * N) & (pos + N <= np.asarray(end, dtype=np.int64)[rec] * N)
+    p = v.real.astype(np.float64) ** 2 + v.imag.astype(np.float64) ** 2
+    cnt = np.bincount(rec[own], minlength=n)
+    for j in range(v.shape[1]):
+        total = np.bincount(rec[own], weights=p[own, j], minlength=n)
+        out[cnt > 0, j] = total[cnt > 0] / cnt[cnt > 0]
+    return out
+
+
 def default_lanes(fft_nperseg: int, n_streams: int) -> int:
     """Stream groups per GPU (``rt_config.lanes``) that measured best: three up to nperseg 512 while the launches of a group are
     small enough to have ends worth filling by another group's kernels (fewer than 16 384 streams on the GPU) -- config 2 +14 % with
@@ -1053,6 +1085,17 @@ class BatchSignalAnalyzer:
         delivered segment, with the bytes the default returns for it; the phase reference is the frame's own start."""
         return self._native.fetch_record_stft(hop_div)
 
+    def fetch_record_band(self, hop_div: int = 1, half_width: int = 2):
+        """``(offsets, first_segment, values)``: for every frame of ``fetch_record_stft(hop_div)`` the complex STFT values of the
+        ``2 * half_width + 1`` bins around the record's bin (``rt_fetch_record_band``) -- ``values`` is ``[n_frames, 2 w + 1]``,
+        complex64 (complex128 with ``precision="float64"``), column ``j`` the bin ``(fi + j - w) mod fft_nperseg``
+        (:func:`band_bins`; circular, fftfreq order).  ``offsets`` and ``first_segment`` are that method's, column ``w`` its
+        bytes; every column is that method's value at the column's bin, operation for operation, so a record ``d`` bins away in
+        the same stream holds this record's column ``w + d`` in its own centre column.  ``half_width`` 0 ... 8, ``hop_div``
+        1 ... 16, a divisor of ``fft_nperseg``.  :func:`record_band_spectrum` reduces the frames to the pulse's spectrum.
+        Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is."""
+        return self._native.fetch_record_band(hop_div, half_width)
+
     def fetch_record_edges(self, hop_div: int = 4) -> np.ndarray:
         """float64 ``[n_records, 2]``: ``(rise, fall)`` of every record's pulse in samples relative to sample 0 of the buffer of
         the call returned last, to a fraction of ``fft_nperseg / hop_div`` where the pulse is switched and the delivered margin
@@ -1215,6 +1258,7 @@ class SignalAnalyzer:
         stft_hop_div: int = 1,
         record_estimates: bool = False,
         input_stats: bool = False,
+        record_band: Optional[int] = None,
         **kwargs,
     ):
         """``input_stats=True``: after every buffer ``input_stats`` holds the row of
@@ -1226,6 +1270,8 @@ class SignalAnalyzer:
         list of their complex STFT values: one per delivered segment, or with ``stft_hop_div=k`` one per frame every
         ``fft_nperseg / k`` samples (:meth:`BatchSignalAnalyzer.fetch_record_stft`).  ``record_estimates=True`` with it:
         ``signal_estimates`` holds one row per such signal (:meth:`BatchSignalAnalyzer.fetch_record_estimates` at ``stft_hop_div``).
+        ``record_band=w`` with it: ``signal_band`` is the list of their ``[n_frames, 2 w + 1]`` arrays, the bins beside each
+        signal's bin at ``stft_hop_div`` (:meth:`BatchSignalAnalyzer.fetch_record_band`).
 
         ``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
@@ -1250,6 +1296,10 @@ class SignalAnalyzer:
             raise ValueError("record_estimates needs record_iq=True")
         self.record_estimates = bool(record_estimates)
         self.signal_estimates: Optional[np.ndarray] = None  # (beside signal_stft: one ESTIMATES_DTYPE row per signal)
+        if record_band is not None and not record_iq:
+            raise ValueError("record_band needs record_iq=True")
+        self.record_band = None if record_band is None else int(record_band)
+        self.signal_band: Optional[List[np.ndarray]] = None  # (beside signal_stft: the bins around each signal's bin, frame by frame)
         self._input_stats_on = bool(input_stats)
         self.input_stats: Optional[np.void] = None  # (the buffer's own level, DC and clipping: one INPUT_STATS_DTYPE row)
         self.calibration_db = calibration_db
@@ -1457,7 +1507,7 @@ class SignalAnalyzer:
         return out
 
     def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False,
-               record_stft: bool = False, stft_hop_div: int = 1, record_estimates: bool = False):
+               record_stft: bool = False, stft_hop_div: int = 1, record_estimates: bool = False, record_band: Optional[int] = None):
         """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
         instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
         (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
@@ -1470,7 +1520,11 @@ class SignalAnalyzer:
         ``record_stft=True`` (with ``record_iq=True``): returns ``(signals, signal_iq, signal_stft)``, the complex STFT values of
         each signal's bin as well (:meth:`BatchSignalAnalyzer.fetch_record_stft`), with ``stft_hop_div=k`` at frames every
         ``fft_nperseg / k`` samples.  ``record_estimates=True`` (with ``record_iq=True``): one more list at the end of the tuple,
-        a row of :meth:`BatchSignalAnalyzer.fetch_record_estimates` (at ``stft_hop_div``) per signal."""
+        a row of :meth:`BatchSignalAnalyzer.fetch_record_estimates` (at ``stft_hop_div``) per signal.  ``record_band=w`` (with
+        ``record_iq=True``): one more list behind those, per signal the ``[n_frames, 2 w + 1]`` array of
+        :meth:`BatchSignalAnalyzer.fetch_record_band` (at ``stft_hop_div``)."""
+        if record_band is not None and not record_iq:
+            raise ValueError("record_band needs record_iq=True")
         if record_stft and not record_iq:
             raise ValueError("record_stft needs record_iq=True")
         if record_estimates and not record_iq:
@@ -1502,6 +1556,7 @@ class SignalAnalyzer:
         out_iq: List[np.ndarray] = []
         out_stft: List[np.ndarray] = []
         out_est: List[np.void] = []
+        out_band: List[np.ndarray] = []
 
         def call(first: int, links: int, length: int):
             part = x[first * B * per_sample:(first * B + links * length) * per_sample]
@@ -1515,6 +1570,9 @@ class SignalAnalyzer:
                 out_stft.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
             if record_estimates:
                 out_est.extend(batch.fetch_record_estimates(stft_hop_div)[rec["shadowed"] == 0])
+            if record_band is not None:
+                offsets, _, got = batch.fetch_record_band(stft_hop_div, record_band)
+                out_band.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
             out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
 
         for first in range(0, n_full, L):
@@ -1524,7 +1582,7 @@ class SignalAnalyzer:
         elif rest:
             logger.info(f"SDR {self.device} replay: the last {rest} samples hold fewer than two segments and are dropped")
         [self.consume_signal(s) for s in out]
-        got = (out, out_iq) + ((out_stft,) if record_stft else ()) + ((out_est,) if record_estimates else ())
+        got = (out, out_iq) + ((out_stft,) if record_stft else ()) + ((out_est,) if record_estimates else ()) + ((out_band,) if record_band is not None else ())
         return got if record_iq else out
 
     def _keep_noise(self):
@@ -1545,6 +1603,9 @@ class SignalAnalyzer:
             self.signal_stft = [values[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
             if self.record_estimates:
                 self.signal_estimates = self._batch.fetch_record_estimates(self.stft_hop_div)[np.flatnonzero(keep)]
+            if self.record_band is not None:
+                offsets, _, values = self._batch.fetch_record_band(self.stft_hop_div, self.record_band)
+                self.signal_band = [values[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
 
     def reset(self):
         self._batch.reset()

@@ -40,6 +40,7 @@
 #include "rt_record_iq.h"
 #include "rt_record_stft.h"
 #include "rt_record_stft_hop.h"
+#include "rt_record_band.h"
 #include "rt_record_estimates.h"
 #include "rt_input_stats.h"
 #include "rt_record_stft_book.h"
@@ -273,6 +274,12 @@ struct IqSlot {
     size_t est_bytes = 0;
     char *d_est_work = nullptr;                      // the turn-back table, then EstimatesWork
     size_t est_work_bytes = 0;
+    // rt_fetch_record_band (rt_record_band.h): a value pool and a work list of its own, and the (k, w) they were built for
+    int band_k = 0, band_w = 0;                      // d_band_vals holds the delivered call's frames for (band_k, band_w); k 0: none
+    char *d_band_vals = nullptr;                     // [frames][2 w + 1] cf, or cd on a float64 handle
+    size_t band_vals_bytes = 0;
+    char *d_band_work = nullptr;                     // StftHopWork: frame_first, pool_seg, lp, fi
+    size_t band_work_bytes = 0;
 };
 struct RecordIq {
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
@@ -1440,6 +1447,7 @@ void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_
     qs.stft_done = false;
     qs.hop_k = 0;
     qs.est_k = 0;
+    qs.band_k = 0;
     qs.fi.resize(n);
     qs.start.resize(n);
     qs.end.resize(n);
@@ -1524,6 +1532,8 @@ void iq_free(rt_handle *h) {
         (void)hipFree(qs.d_hop_work);
         (void)hipFree(qs.d_est);
         (void)hipFree(qs.d_est_work);
+        (void)hipFree(qs.d_band_vals);
+        (void)hipFree(qs.d_band_work);
     }
     (void)hipFree(q->d_stft_tw);
     (void)hipFree(q->d_stft_win);
@@ -1922,6 +1932,202 @@ int fetch_record_stft_hop_impl(rt_handle *h, const char *entry, const char *twin
         if (!query && mine) {
             RT_HIP(h, hipSetDevice(l->cfg.device));
             RT_HIP(h, hipMemcpy(values + 2 * c0, qs.d_hop_vals, mine * sizeof(C), hipMemcpyDeviceToHost));
+        }
+        r0 += n;
+        c0 += mine;
+    }
+    return RT_OK;
+}
+
+// ---- rt_fetch_record_band: the 2 w + 1 bins around each record's bin, frame by frame (rt_record_band.h) ----
+template <class P, int FMT, int HW>
+void launch_record_band_hw(const StftBandArgs<P> &a, int group, hipStream_t st) {
+    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
+    const dim3 grid((unsigned)((a.hop.n_frames + per_block - 1) / per_block)), block(kStftBlock);
+    const size_t lds = stft_band_lds_bytes(a.hop.nperseg, sizeof(typename stft_types<P>::C));
+    if (group == 8) hipLaunchKernelGGL((record_band<P, FMT, 8, HW>), grid, block, lds, st, a);
+    else if (group == 16) hipLaunchKernelGGL((record_band<P, FMT, 16, HW>), grid, block, lds, st, a);
+    else if (group == 32) hipLaunchKernelGGL((record_band<P, FMT, 32, HW>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((record_band<P, FMT, 64, HW>), grid, block, lds, st, a);
+}
+template <class P, int FMT>
+void launch_record_band(const StftBandArgs<P> &a, int group, hipStream_t st) {
+    const int hw = stft_band_bound(a.half_width);
+    if (hw == 0) launch_record_band_hw<P, FMT, 0>(a, group, st);
+    else if (hw == 2) launch_record_band_hw<P, FMT, 2>(a, group, st);
+    else launch_record_band_hw<P, FMT, 8>(a, group, st);
+}
+
+// The band of lane-less handle `l`'s delivered call for (k, w) into its slot's band pool: once per delivered call and pair
+// (record_stft_hop_run's twin: it shares the twiddle table and the window with the STFT entries, made by whichever is called
+// first, and nothing else -- the value pool, the work list and the pair they hold are this entry's own).
+template <class P>
+int record_band_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &work, int64_t frames) {
+    using C = typename stft_types<P>::C;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    if (qs.band_k == k && qs.band_w == w) return RT_OK;
+    const int N = iq_nperseg(l);
+    const size_t n = qs.first_seg.size();
+    const int group = stft_hop_group(N, qs.bps);
+    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
+    const int64_t elems = stft_band_elems(frames, w);
+    if ((uint64_t)qs.offsets.back() * (uint64_t)qs.bps > qs.pool_bytes || (frames > 0 && !qs.d_pool) || elems < 0 ||
+        (frames + per_block - 1) / per_block > 0x7fffffffll) {
+        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+        return RT_E_HIP;
+    }
+    if (frames == 0) {
+        qs.band_k = k;
+        qs.band_w = w;
+        return RT_OK;
+    }
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    const auto nomem = [&](const char *what, size_t bytes) {
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
+        return RT_E_NOMEM;
+    };
+    if (!q.d_stft_tw) {
+        const std::vector<C> tw = record_stft_twiddles<C, typename std::conditional<sizeof(P) == 4, double, long double>::type>(N);
+        void *d = nullptr;
+        if (hipMalloc(&d, tw.size() * sizeof(C)) != hipSuccess) return nomem("the twiddle table", tw.size() * sizeof(C));
+        if (hipMemcpy(d, tw.data(), tw.size() * sizeof(C), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            h->err = std::string(entry) + ": uploading the twiddle table failed";
+            return RT_E_HIP;
+        }
+        q.d_stft_tw = d;
+    }
+    if (!l->f64 && !q.d_stft_win) {
+        float *d = nullptr;
+        if (hipMalloc(&d, (size_t)N * sizeof(float)) != hipSuccess) return nomem("the window", (size_t)N * sizeof(float));
+        if (hipMemcpy(d, l->h_window.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            h->err = std::string(entry) + ": uploading the window failed";
+            return RT_E_HIP;
+        }
+        q.d_stft_win = d;
+    }
+    // both pools before either is touched: where the second cannot be had, the first still holds what it held
+    const size_t val_bytes = (size_t)((uint64_t)elems * sizeof(C));
+    const size_t b_first = (n + 1) * sizeof(int64_t), b_seg = n * sizeof(int64_t), b_i32 = n * sizeof(int32_t);
+    const size_t work_bytes = b_first + b_seg + 2 * b_i32;
+    if (qs.band_vals_bytes < val_bytes || qs.band_work_bytes < work_bytes) qs.band_k = 0;  // (a pool that grows loses what it held)
+    if (!stft_hop_grow(&qs.d_band_vals, &qs.band_vals_bytes, val_bytes)) return nomem("the call's band", val_bytes);
+    if (!stft_hop_grow(&qs.d_band_work, &qs.band_work_bytes, work_bytes)) return nomem("the work list", work_bytes);
+    qs.band_k = 0;  // (whatever the pool held is gone from here on)
+    std::vector<char> packed(work_bytes);
+    std::memcpy(packed.data(), work.frame_first.data(), b_first);
+    std::memcpy(packed.data() + b_first, work.pool_seg.data(), b_seg);
+    std::memcpy(packed.data() + b_first + b_seg, work.lp.data(), b_i32);
+    std::memcpy(packed.data() + b_first + b_seg + b_i32, work.fi.data(), b_i32);
+    StftBandArgs<P> b{};
+    StftHopArgs<P> &a = b.hop;
+    b.half_width = w;
+    a.pool = qs.d_pool;
+    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_band_work);
+    a.pool_seg = reinterpret_cast<const int64_t *>(qs.d_band_work + b_first);
+    a.lp = reinterpret_cast<const int32_t *>(qs.d_band_work + b_first + b_seg);
+    a.fi = reinterpret_cast<const int32_t *>(qs.d_band_work + b_first + b_seg + b_i32);
+    a.n_records = (int32_t)n;
+    a.nperseg = N;
+    a.hop_div = k;
+    a.n_frames = frames;
+    a.pool_samples = qs.offsets.back();
+    a.tw = static_cast<const C *>(q.d_stft_tw);
+    a.values = reinterpret_cast<C *>(qs.d_band_vals);
+    if constexpr (sizeof(P) == 4) {
+        a.window = q.d_stft_win;
+        a.root = stft_root_f32(l->cfg.scale);
+    } else {
+        a.window = l->f64->d_window;
+        a.root = stft_root_f64(l->f64->c.scale);
+    }
+    // (a pageable source: `packed` lives until the stream has been waited for below)
+    hipError_t e = hipMemcpyAsync(qs.d_band_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        if (qs.fmt == kFmtU8) launch_record_band<P, kFmtU8>(b, group, q.s_gather);
+        else if (qs.fmt == kFmtI16) launch_record_band<P, kFmtI16>(b, group, q.s_gather);
+        else if (qs.fmt == kFmtI8) launch_record_band<P, kFmtI8>(b, group, q.s_gather);
+        else launch_record_band<P, kFmtC64>(b, group, q.s_gather);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": record_band: " + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    qs.band_k = k;
+    qs.band_w = w;
+    return RT_OK;
+}
+
+template <class P>
+int fetch_record_band_impl(rt_handle *h, const char *entry, const char *twin, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets,
+                           int32_t *first_seg, size_t n_first, P *values, size_t cap_frames, size_t *n_frames) {
+    using C = typename stft_types<P>::C;
+    if (!h || !n_frames) return RT_E_INVALID;
+    *n_frames = 0;
+    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
+        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
+        return RT_E_INVALID;
+    }
+    const int N = iq_nperseg(h);
+    if (!stft_band_ok(N, hop_div, half_width)) {
+        h->err = std::string(entry) + ": hop_div k = " + std::to_string(hop_div) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) +
+                 " and divide nperseg N = " + std::to_string(N) + ", half_width w = " + std::to_string(half_width) + " must be 0 ... " +
+                 std::to_string(kStftBandMaxHalf) + " with 2 w + 1 <= N";
+        return RT_E_INVALID;
+    }
+    std::vector<rt_handle *> lanes;
+    size_t records = 0, samples = 0;
+    int bps = 0;
+    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
+        h->err = std::string(entry) + ": n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
+        return RT_E_INVALID;
+    }
+    // every lane's frame plan, before anything is launched or written
+    const size_t B = (size_t)stft_band_columns(half_width);
+    std::vector<StftHopWork> works(lanes.size());
+    std::vector<int64_t> frames(lanes.size());
+    size_t total = 0;
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
+        frames[i] = stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.first_seg.size(), N, hop_div, &works[i]);
+        if (frames[i] < 0 || stft_band_elems(frames[i], half_width) < 0) {
+            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+            return RT_E_HIP;
+        }
+        total += (size_t)frames[i];
+    }
+    *n_frames = total;
+    const bool query = !values || cap_frames == 0;
+    if (!query && cap_frames < total) {
+        h->err = std::string(entry) + ": output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    if (!query)
+        for (size_t i = 0; i < lanes.size(); ++i) {
+            const int rs = record_band_run<P>(h, lanes[i], entry, hop_div, half_width, works[i], frames[i]);
+            if (rs != RT_OK) return rs;
+        }
+    size_t r0 = 0, c0 = 0;
+    if (offsets) offsets[0] = 0;
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        rt_handle *l = lanes[i];
+        const IqSlot &qs = l->riq->slot[l->riq->delivered];
+        const size_t n = qs.first_seg.size(), mine = (size_t)frames[i];
+        if (offsets)
+            for (size_t r = 0; r < n; ++r) offsets[r0 + r + 1] = (int64_t)c0 + works[i].frame_first[r + 1];
+        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
+        if (!query && mine) {
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(values + 2 * c0 * B, qs.d_band_vals, mine * B * sizeof(C), hipMemcpyDeviceToHost));
         }
         r0 += n;
         c0 += mine;
@@ -3993,6 +4199,18 @@ int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets
                                  size_t cap_frames, size_t *n_frames) {
     return fetch_record_stft_hop_impl<double>(h, "rt_fetch_record_stft_hop_f64", "rt_fetch_record_stft_hop", hop_div, offsets, n_offsets, first_seg, n_first,
                                               values, cap_frames, n_frames);
+}
+
+int rt_fetch_record_band(rt_handle *h, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                         float *values, size_t cap_frames, size_t *n_frames) {
+    return fetch_record_band_impl<float>(h, "rt_fetch_record_band", "rt_fetch_record_band_f64", hop_div, half_width, offsets, n_offsets, first_seg, n_first,
+                                         values, cap_frames, n_frames);
+}
+
+int rt_fetch_record_band_f64(rt_handle *h, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
+                             double *values, size_t cap_frames, size_t *n_frames) {
+    return fetch_record_band_impl<double>(h, "rt_fetch_record_band_f64", "rt_fetch_record_band", hop_div, half_width, offsets, n_offsets, first_seg, n_first,
+                                          values, cap_frames, n_frames);
 }
 
 int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out) {

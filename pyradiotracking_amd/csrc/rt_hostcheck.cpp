@@ -773,6 +773,10 @@ void hc_stft_hop_frame_at(const int64_t *frame_first, const int64_t *pool_seg, c
     out[1] = f.part;
     out[2] = f.sample;
 }
+// rt_fetch_record_band: the argument rule, column j's bin, the pool's complex values (-1: the product leaves 64 bits)
+int hc_stft_band_ok(int nperseg, int k, int w) { return stft_band_ok(nperseg, k, w) ? 1 : 0; }
+int hc_stft_band_bin(int fi, int j, int w, int nperseg) { return stft_band_bin(fi, j, w, nperseg); }
+long long hc_stft_band_elems(long long frames, int w) { return (long long)stft_band_elems((int64_t)frames, w); }
 // rt_fetch_record_estimates' plan: -> frame_first [n + 1], lp [n], range [n][4], base [n][2], fmod [n], turn [k][2]; returns the
 // frames, -1: refused (nothing is written then)
 long long hc_estimates_work(const int64_t *offsets, const int32_t *first_seg, const int32_t *fi, const int32_t *start, const int32_t *end, long long n,

@@ -123,6 +123,28 @@ inline StftHopFrame stft_hop_frame_at(const StftHopWork &w, int64_t g) {
     return stft_hop_frame_at(w.frame_first.data(), w.pool_seg.data(), w.lp.data(), (int)w.lp.size(), w.N, w.k, g);
 }
 
+// ---- rt_fetch_record_band: the bins beside each record's bin (record_band, rt_record_band.h) ----
+// The frames and the work list are the hop entry's (StftHopWork, stft_hop_frame_at): nothing per record is added.  A frame has
+// B = 2 w + 1 columns, column j the bin (fi + j - w) mod N in fftfreq order -- the band is circular.
+constexpr int kStftBandMaxHalf = 8;
+
+inline bool stft_band_ok(int N, int k, int w) { return stft_hop_div_ok(N, k) && w >= 0 && w <= kStftBandMaxHalf && 2 * w + 1 <= N; }
+inline int stft_band_columns(int w) { return 2 * w + 1; }
+// column j (0 <= j < 2 w + 1) of a record at bin fi (0 <= fi < N) -> its bin in 0 .. N - 1
+inline int stft_band_bin(int fi, int j, int w, int N) {
+    int b = fi + (j - w);  // (|j - w| <= 8 < N: one correction either way)
+    if (b < 0) b += N;
+    if (b >= N) b -= N;
+    return b;
+}
+// complex values of the pool for `frames` frames: frames * (2 w + 1), or -1 where that (or its bytes at 16 a value) leaves int64
+inline int64_t stft_band_elems(int64_t frames, int w) {
+    if (frames < 0 || w < 0 || w > kStftBandMaxHalf) return -1;
+    const int64_t B = 2 * (int64_t)w + 1;
+    if (frames > (INT64_MAX / 16) / B) return -1;
+    return frames * B;
+}
+
 // ---- rt_fetch_record_estimates: one row per record from the frames (record_estimates, rt_record_estimates.h) ----
 // The frames are the hop entry's, so the prefix and lp are StftHopWork's.  On top of them a record has, per part, the frames that
 // lie wholly INSIDE its own cells -- start * N <= position and position + N <= end * N.  A part's positions rise by h, so its
