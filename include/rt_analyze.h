@@ -787,6 +787,58 @@ typedef struct rt_record_estimate {
 int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out);
 
 /*
+ * ---- per-record band spectrum, reduced on the device (additive within ABI version 6) ----
+ * What a caller makes of rt_fetch_record_band's frames is one short row per record: how wide the pulse is, where its peak lies
+ * between bins, how much of it sits in the centre bin.  This entry reduces the band where it lies; the frames are not copied to
+ * the host.  One entry serves float32 and float64 handles: rows, means and peaks are float64 either way, only the frames read
+ * differ (a float32 value is widened first).
+ *   - the call, the records, their order, the two parts and the frames are exactly rt_fetch_record_band's at the same
+ *     (hop_div, half_width) = (k, w); rt_set_record_iq must be on.  B = 2 w + 1, column j belongs to d_j = j - w as there.
+ *   - `hop_div`: 1 <= k <= 16 and N % k == 0 (N = nperseg).  `half_width`: 0 <= w <= 8 with 2 w + 1 <= N.  Anything else is
+ *     RT_E_INVALID, the message names k, w and N, and it is refused before anything is launched or copied.
+ *   - `rows`: HOST memory, `cap` rows.  `mean`, `peak`: HOST memory, cap * B doubles each, record-major; either may be NULL: not
+ *     wanted.  rows == NULL or cap == 0: a size query, *n_out = the records.  cap < *n_out with a buffer: RT_E_CAPACITY, nothing
+ *     written.  Validity, RT_E_NOMEM (the handle is left as it was) and every refusal: rt_fetch_record_band's, under this
+ *     entry's name.
+ *   - the INSIDE frames of record (start, end) are rt_fetch_record_estimates': start * N <= position and position + N <= end * N.
+ *     They are numbered i = 0, 1, ...: part 0's run first, then part 1's.  n_inside counts them.
+ *   - per column j and inside frame, p = re * re + im * im in float64, every product and sum rounded once (no contraction).
+ *     mean[j]: the project's canonical order, the one the record cells' statistics use -- 64 partials, inside frame i adds into
+ *     partial i mod 64 in increasing i, the partials are folded by halving (each takes its neighbour at distance 32, 16, ... 1),
+ *     and the sum is divided by n_inside.  peak[j]: the largest p over the inside frames; a NaN propagates (numpy.max).
+ *     n_inside == 0: every mean, peak and scalar of the row is NaN, peak_col is -1.
+ *   - the scalars are computed from the row's means m_0 ... m_2w in float64, left to right:
+ *       total        = ((m_0 + m_1) + ...)
+ *       centre_share = m_w / total
+ *       centroid     = (sum m_j d_j) / total                             bins off the record's bin
+ *       width        = sqrt((sum m_j ((d_j - centroid) (d_j - centroid))) / total)
+ *       peak_col     = the lowest j with m_j equal to the row's maximum
+ *       peak_bins    = d_p + 0.5 (a - c) / ((a - 2 b) + c),  a, b, c = log m_(p-1), log m_p, log m_(p+1),  p = peak_col,
+ *                      where 0 < p < 2 w and the three means are finite and > 0; NaN elsewhere (w == 0, a peak on the band's edge)
+ *     If any m_j is NaN, peak_col is -1 and every scalar is NaN.  A record of constant frames has total == 0, and the divisions
+ *     give NaN as IEEE gives them.  Times sample_rate / N, centroid, width and peak_bins are Hz.
+ *   - the same frames give the same bytes: on every handle kind (mode, lanes, chained, masked, float64 dense / map-free /
+ *     rescue), on every fetch and in any order of calls with the other record entries.  A NaN mean or peak is the one quiet NaN.
+ *   - lazy: rt_process*, rt_fetch and every other fetch entry allocate, copy and launch what they do without this entry.  The
+ *     entry's first call for a delivered call and (k, w) makes sure the band pool holds (k, w) (as rt_fetch_record_band would,
+ *     without the copy to the host), uploads a plan of 28 bytes a record, runs one kernel on the gather's stream, waits, and
+ *     copies rows, means and peaks down from a pool of its own per call slot.  The same (k, w) again copies only; another pair
+ *     builds again.  A later rt_fetch_record_band(k, w) copies without rebuilding.
+ */
+typedef struct rt_record_spectrum {
+    double total;          /* sum of the column means                                         */
+    double centre_share;   /* mean[w] / total                                                 */
+    double centroid;       /* bins off the record's bin                                       */
+    double width;          /* RMS width in bins about the centroid                            */
+    double peak_bins;      /* log-parabolic peak position, bins off the record's bin          */
+    int32_t peak_col;      /* lowest column whose mean is the largest; -1: a NaN mean         */
+    int32_t n_inside;      /* frames wholly inside the record's own cells                     */
+} rt_record_spectrum;      /* 48 bytes */
+
+int rt_fetch_record_spectrum(rt_handle *h, int32_t hop_div, int32_t half_width, rt_record_spectrum *rows, double *mean, double *peak,
+                             size_t cap, size_t *n_out);
+
+/*
  * ---- input statistics: level, DC and clipping of every stream's raw input (additive within ABI version 6) ----
  * Everything above describes a buffer's spectrum; this describes the buffer.  A radio at fixed gain clips, a dead one delivers
  * constant bytes instead of no callbacks, and a record only exists where the detection worked -- so the caller wants, per stream

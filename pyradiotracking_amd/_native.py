@@ -112,6 +112,20 @@ ESTIMATE_DTYPE = np.dtype(
 )
 assert ESTIMATE_DTYPE.itemsize == 72
 
+#: numpy view of ``rt_record_spectrum`` (48 bytes): a row of ``rt_fetch_record_spectrum``
+SPECTRUM_DTYPE = np.dtype(
+    [
+        ("total", "<f8"),
+        ("centre_share", "<f8"),
+        ("centroid", "<f8"),
+        ("width", "<f8"),
+        ("peak_bins", "<f8"),
+        ("peak_col", "<i4"),
+        ("n_inside", "<i4"),
+    ]
+)
+assert SPECTRUM_DTYPE.itemsize == 48
+
 #: numpy view of ``rt_input_stats`` (64 bytes): a row of ``rt_fetch_input_stats``
 INPUT_STATS_DTYPE = np.dtype(
     [
@@ -209,6 +223,7 @@ ABI_SYMBOLS = (
     "rt_fetch_record_estimates",
     "rt_fetch_record_band",
     "rt_fetch_record_band_f64",
+    "rt_fetch_record_spectrum",
     "rt_set_input_stats",
     "rt_fetch_input_stats",
 )
@@ -292,6 +307,7 @@ def load_library(path: Optional[str] = None):
     lib.rt_fetch_record_estimates.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for fn in (lib.rt_fetch_record_band, lib.rt_fetch_record_band_f64):
         fn.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.rt_fetch_record_spectrum.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.rt_set_input_stats.argtypes = [vp, C.c_int32]
     lib.rt_fetch_input_stats.argtypes = [vp, vp, C.c_size_t]
     for name in ABI_SYMBOLS:
@@ -714,6 +730,23 @@ class NativeAnalyzer:
         if n.value:
             self._check(fn(self._handle, k, w, offsets.ctypes.data, offsets.size, first.ctypes.data, first.size, values.ctypes.data, n.value, C.byref(n)))
         return offsets, first, values
+
+    def fetch_record_spectrum(self, hop_div: int = 4, half_width: int = 2):
+        """``rt_fetch_record_spectrum``: ``(rows, mean, peak)`` of the call ``fetch`` delivered last (in full) -- one
+        ``SPECTRUM_DTYPE`` row per record and float64 ``[n_records, 2 * half_width + 1]`` arrays of each column's mean and largest
+        ``|value| ** 2`` over the record's inside frames, reduced on the device from the frames of ``fetch_record_band``; the frames
+        are not copied."""
+        k, w = int(hop_div), int(half_width)
+        n = C.c_size_t(0)
+        fn = self._lib.rt_fetch_record_spectrum
+        self._check(fn(self._handle, k, w, None, None, None, 0, C.byref(n)))
+        cols = max(2 * w + 1, 0)
+        rows = np.zeros(n.value, dtype=SPECTRUM_DTYPE)
+        mean = np.zeros((n.value, cols), dtype=np.float64)
+        peak = np.zeros((n.value, cols), dtype=np.float64)
+        if n.value:
+            self._check(fn(self._handle, k, w, rows.ctypes.data, mean.ctypes.data, peak.ctypes.data, rows.size, C.byref(n)))
+        return rows, mean, peak
 
     def set_input_stats(self, on: bool):
         """``rt_set_input_stats``: every later ``rt_process*`` also leaves one ``INPUT_STATS_DTYPE`` row per stream, computed

@@ -413,6 +413,70 @@ def record_band_spectrum(offsets, first_segment, values, start, end, nperseg: in
     return out
 
 
+#: a row of :meth:`BatchSignalAnalyzer.fetch_record_spectrum` and of :func:`record_band_rows` (``_native.SPECTRUM_DTYPE``)
+SPECTRUM_DTYPE = _native.SPECTRUM_DTYPE
+
+
+def record_band_rows(offsets, first_segment, values, start, end, nperseg: int, hop_div: int = 1):
+    """``(rows, mean, peak)`` from what :meth:`BatchSignalAnalyzer.fetch_record_band` returns and the records' ``start`` /
+    ``end``: the definition :meth:`BatchSignalAnalyzer.fetch_record_spectrum` is held to within round-off, in plain NumPy.
+    Over the frames that lie wholly inside the record's own cells (the rule of :func:`record_band_spectrum`), per column ``j``
+    of ``p = re ** 2 + im ** 2`` in float64: ``mean[i, j]`` its mean and ``peak[i, j]`` its largest value (a NaN propagates).
+    ``rows`` is one ``SPECTRUM_DTYPE`` row per record from the means ``m`` with ``d = j - w``: ``total = sum m``,
+    ``centre_share = m[w] / total``, ``centroid = sum m d / total``, ``width = sqrt(sum m (d - centroid) ** 2 / total)`` (both
+    in bins), ``peak_col`` the lowest column of the largest mean, and ``peak_bins`` the vertex of the parabola through the
+    logarithms of the three means around it -- exact for a Gaussian main lobe -- where ``peak_col`` is no edge column and the
+    three are finite and positive, else NaN.  A record without an inside frame, or with a NaN mean, has NaN in every scalar and
+    ``peak_col == -1``."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    v = np.asarray(values)
+    if v.ndim != 2 or v.shape[1] % 2 != 1:
+        raise ValueError("values must be [n_frames, 2 * half_width + 1], as fetch_record_band returns them")
+    n, N, B = len(offsets) - 1, int(nperseg), v.shape[1]
+    w = B // 2
+    rows = np.zeros(n, dtype=SPECTRUM_DTYPE)
+    for name in ("total", "centre_share", "centroid", "width", "peak_bins"):
+        rows[name] = np.nan
+    rows["peak_col"] = -1
+    mean = np.full((n, B), np.nan)
+    peak = np.full((n, B), np.nan)
+    if n == 0:
+        return rows, mean, peak
+    rec, _, pos = _stft_frames(offsets, first_segment, N, hop_div)
+    own = (pos >= np.asarray(start, dtype=np.int64)[rec] * N) & (pos + N <= np.asarray(end, dtype=np.int64)[rec] * N)
+    with np.errstate(all="ignore"):
+        p = v.real.astype(np.float64) ** 2 + v.imag.astype(np.float64) ** 2
+        d = np.arange(-w, w + 1, dtype=np.float64)
+        for i in range(n):
+            mine = p[offsets[i]:offsets[i + 1]][own[offsets[i]:offsets[i + 1]]]
+            rows["n_inside"][i] = len(mine)
+            if not len(mine):
+                continue
+            m = mean[i] = mine.mean(axis=0)
+            peak[i] = mine.max(axis=0)
+            if np.isnan(m).any():
+                continue
+            total = m.sum()
+            centroid = (m * d).sum() / total
+            col = int(np.argmax(m))
+            rows["total"][i], rows["centre_share"][i], rows["centroid"][i] = total, m[w] / total, centroid
+            rows["width"][i] = np.sqrt((m * (d - centroid) ** 2).sum() / total)
+            rows["peak_col"][i] = col
+            if 0 < col < 2 * w and np.isfinite(m[col - 1:col + 2]).all() and (m[col - 1:col + 2] > 0).all():
+                a, b, c = np.log(m[col - 1:col + 2])
+                rows["peak_bins"][i] = d[col] + 0.5 * (a - c) / (a - 2.0 * b + c)
+    return rows, mean, peak
+
+
+def spectrum_hz(rows, sample_rate: float, nperseg: int) -> np.ndarray:
+    """A copy of the ``SPECTRUM_DTYPE`` rows with ``centroid``, ``width`` and ``peak_bins`` scaled from bins to Hz
+    (``sample_rate / nperseg`` a bin); the other fields are unchanged."""
+    out = np.array(rows, dtype=SPECTRUM_DTYPE, copy=True)
+    for name in ("centroid", "width", "peak_bins"):
+        out[name] = out[name] * (float(sample_rate) / int(nperseg))
+    return out
+
+
 def default_lanes(fft_nperseg: int, n_streams: int) -> int:
     """Stream groups per GPU (``rt_config.lanes``) that measured best: three up to nperseg 512 while the launches of a group are
     small enough to have ends worth filling by another group's kernels (fewer than 16 384 streams on the GPU) -- config 2 +14 % with
@@ -1096,6 +1160,16 @@ class BatchSignalAnalyzer:
         Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is."""
         return self._native.fetch_record_band(hop_div, half_width)
 
+    def fetch_record_spectrum(self, hop_div: int = 4, half_width: int = 2):
+        """``(rows, mean, peak)``: the band of ``fetch_record_band(hop_div, half_width)`` reduced on the device to one
+        ``SPECTRUM_DTYPE`` row per record of the call returned last (``rt_fetch_record_spectrum``) -- the frames themselves are
+        not copied to the host.  ``mean`` and ``peak`` are float64 ``[n_records, 2 w + 1]``: per column the mean and the largest
+        ``|value| ** 2`` over the ``n_inside`` frames wholly inside the record's own cells; ``rows`` holds ``total``,
+        ``centre_share``, ``centroid``, ``width``, ``peak_bins`` (bins off the record's bin; :func:`spectrum_hz` scales them to
+        Hz) and ``peak_col``.  :func:`record_band_rows` defines the result; the same frames give the same bytes on every handle
+        kind.  Needs ``record_iq=True``; valid exactly as long as :meth:`fetch_record_iq` is."""
+        return self._native.fetch_record_spectrum(hop_div, half_width)
+
     def fetch_record_edges(self, hop_div: int = 4) -> np.ndarray:
         """float64 ``[n_records, 2]``: ``(rise, fall)`` of every record's pulse in samples relative to sample 0 of the buffer of
         the call returned last, to a fraction of ``fft_nperseg / hop_div`` where the pulse is switched and the delivered margin
@@ -1259,6 +1333,7 @@ class SignalAnalyzer:
         record_estimates: bool = False,
         input_stats: bool = False,
         record_band: Optional[int] = None,
+        record_spectrum: bool = False,
         **kwargs,
     ):
         """``input_stats=True``: after every buffer ``input_stats`` holds the row of
@@ -1271,7 +1346,9 @@ class SignalAnalyzer:
         ``fft_nperseg / k`` samples (:meth:`BatchSignalAnalyzer.fetch_record_stft`).  ``record_estimates=True`` with it:
         ``signal_estimates`` holds one row per such signal (:meth:`BatchSignalAnalyzer.fetch_record_estimates` at ``stft_hop_div``).
         ``record_band=w`` with it: ``signal_band`` is the list of their ``[n_frames, 2 w + 1]`` arrays, the bins beside each
-        signal's bin at ``stft_hop_div`` (:meth:`BatchSignalAnalyzer.fetch_record_band`).
+        signal's bin at ``stft_hop_div`` (:meth:`BatchSignalAnalyzer.fetch_record_band`).  ``record_spectrum=True`` with
+        ``record_band=w``: ``signal_spectrum`` is ``(rows, mean, peak)`` of those signals, the band reduced on the device
+        (:meth:`BatchSignalAnalyzer.fetch_record_spectrum`).
 
         ``record_cells=True``: after every buffer ``signal_data`` is the list of the cell arrays of the signals put on the
         queue (unshadowed, queue order) -- the reference's ``data`` of each ``Signal`` (analyze.py:437-440): linear power.
@@ -1300,6 +1377,10 @@ class SignalAnalyzer:
             raise ValueError("record_band needs record_iq=True")
         self.record_band = None if record_band is None else int(record_band)
         self.signal_band: Optional[List[np.ndarray]] = None  # (beside signal_stft: the bins around each signal's bin, frame by frame)
+        if record_spectrum and record_band is None:
+            raise ValueError("record_spectrum needs record_iq=True and record_band=w")
+        self.record_spectrum = bool(record_spectrum)
+        self.signal_spectrum = None  # (beside signal_band: (rows, mean, peak), one row per signal)
         self._input_stats_on = bool(input_stats)
         self.input_stats: Optional[np.void] = None  # (the buffer's own level, DC and clipping: one INPUT_STATS_DTYPE row)
         self.calibration_db = calibration_db
@@ -1507,7 +1588,8 @@ class SignalAnalyzer:
         return out
 
     def replay(self, samples: np.ndarray, ts_start: datetime.datetime, *, chain: int = 16, fmt: str = "c64", record_iq: bool = False,
-               record_stft: bool = False, stft_hop_div: int = 1, record_estimates: bool = False, record_band: Optional[int] = None):
+               record_stft: bool = False, stft_hop_div: int = 1, record_estimates: bool = False, record_band: Optional[int] = None,
+               record_spectrum: bool = False):
         """Run one long RECORDING through the analysis, ``chain`` buffers of ``sdr_callback_length`` per call (``rt_set_chain``)
         instead of one: the signals -- returned, and put on ``signal_queue`` -- are those of calling the matching callback
         (``process_samples`` / ``process_bytes`` / ``process_int16`` / ``process_int8`` for ``fmt`` ``"c64"`` / ``"u8"`` /
@@ -1522,9 +1604,13 @@ class SignalAnalyzer:
         ``fft_nperseg / k`` samples.  ``record_estimates=True`` (with ``record_iq=True``): one more list at the end of the tuple,
         a row of :meth:`BatchSignalAnalyzer.fetch_record_estimates` (at ``stft_hop_div``) per signal.  ``record_band=w`` (with
         ``record_iq=True``): one more list behind those, per signal the ``[n_frames, 2 w + 1]`` array of
-        :meth:`BatchSignalAnalyzer.fetch_record_band` (at ``stft_hop_div``)."""
+        :meth:`BatchSignalAnalyzer.fetch_record_band` (at ``stft_hop_div``).  ``record_spectrum=True`` (with ``record_band=w``):
+        one more list at the very end, per signal the ``SPECTRUM_DTYPE`` row of
+        :meth:`BatchSignalAnalyzer.fetch_record_spectrum` (at ``stft_hop_div`` and ``w``)."""
         if record_band is not None and not record_iq:
             raise ValueError("record_band needs record_iq=True")
+        if record_spectrum and record_band is None:
+            raise ValueError("record_spectrum needs record_iq=True and record_band=w")
         if record_stft and not record_iq:
             raise ValueError("record_stft needs record_iq=True")
         if record_estimates and not record_iq:
@@ -1557,6 +1643,7 @@ class SignalAnalyzer:
         out_stft: List[np.ndarray] = []
         out_est: List[np.void] = []
         out_band: List[np.ndarray] = []
+        out_spec: List[np.void] = []
 
         def call(first: int, links: int, length: int):
             part = x[first * B * per_sample:(first * B + links * length) * per_sample]
@@ -1573,6 +1660,8 @@ class SignalAnalyzer:
             if record_band is not None:
                 offsets, _, got = batch.fetch_record_band(stft_hop_div, record_band)
                 out_band.extend(got[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(rec["shadowed"] == 0))
+                if record_spectrum:
+                    out_spec.extend(batch.fetch_record_spectrum(stft_hop_div, record_band)[0][rec["shadowed"] == 0])
             out.extend(batch._chained_signals(rec, [ts_start + first * step], True, False)[0])
 
         for first in range(0, n_full, L):
@@ -1583,6 +1672,7 @@ class SignalAnalyzer:
             logger.info(f"SDR {self.device} replay: the last {rest} samples hold fewer than two segments and are dropped")
         [self.consume_signal(s) for s in out]
         got = (out, out_iq) + ((out_stft,) if record_stft else ()) + ((out_est,) if record_estimates else ()) + ((out_band,) if record_band is not None else ())
+        got = got + ((out_spec,) if record_spectrum else ())
         return got if record_iq else out
 
     def _keep_noise(self):
@@ -1606,6 +1696,8 @@ class SignalAnalyzer:
             if self.record_band is not None:
                 offsets, _, values = self._batch.fetch_record_band(self.stft_hop_div, self.record_band)
                 self.signal_band = [values[offsets[i]:offsets[i + 1]] for i in np.flatnonzero(keep)]
+                if self.record_spectrum:
+                    self.signal_spectrum = tuple(a[np.flatnonzero(keep)] for a in self._batch.fetch_record_spectrum(self.stft_hop_div, self.record_band))
 
     def reset(self):
         self._batch.reset()

@@ -42,6 +42,7 @@
 #include "rt_record_stft_hop.h"
 #include "rt_record_band.h"
 #include "rt_record_estimates.h"
+#include "rt_record_spectrum.h"
 #include "rt_input_stats.h"
 #include "rt_record_stft_book.h"
 #include "rt_ledger.h"
@@ -280,6 +281,12 @@ struct IqSlot {
     size_t band_vals_bytes = 0;
     char *d_band_work = nullptr;                     // StftHopWork: frame_first, pool_seg, lp, fi
     size_t band_work_bytes = 0;
+    // rt_fetch_record_spectrum (rt_record_spectrum.h): the rows, means and peaks reduced from the band pool, and their plan
+    int spec_k = 0, spec_w = 0;                      // d_spec holds the delivered call's rows for (spec_k, spec_w); k 0: none
+    char *d_spec = nullptr;                          // [records] rt_record_spectrum, then mean and peak [records][2 w + 1] float64
+    size_t spec_bytes = 0;
+    char *d_spec_work = nullptr;                     // EstimatesWork: frame_first, range, lp
+    size_t spec_work_bytes = 0;
 };
 struct RecordIq {
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
@@ -1448,6 +1455,7 @@ void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_
     qs.hop_k = 0;
     qs.est_k = 0;
     qs.band_k = 0;
+    qs.spec_k = 0;
     qs.fi.resize(n);
     qs.start.resize(n);
     qs.end.resize(n);
@@ -1534,6 +1542,8 @@ void iq_free(rt_handle *h) {
         (void)hipFree(qs.d_est_work);
         (void)hipFree(qs.d_band_vals);
         (void)hipFree(qs.d_band_work);
+        (void)hipFree(qs.d_spec);
+        (void)hipFree(qs.d_spec_work);
     }
     (void)hipFree(q->d_stft_tw);
     (void)hipFree(q->d_stft_win);
@@ -2255,6 +2265,146 @@ int fetch_record_estimates_impl(rt_handle *h, const char *entry, int32_t hop_div
         if (n) {
             RT_HIP(h, hipSetDevice(l->cfg.device));
             RT_HIP(h, hipMemcpy(out + r0, qs.d_est, n * sizeof(rt_record_estimate), hipMemcpyDeviceToHost));
+        }
+        r0 += n;
+    }
+    return RT_OK;
+}
+
+// ---- rt_fetch_record_spectrum: one row per record and its column means and peaks, reduced from the band pool (rt_record_spectrum.h) ----
+template <class P>
+void launch_record_spectrum(const SpectrumArgs<P> &a, hipStream_t st) {
+    const dim3 grid((unsigned)(((size_t)a.n_records + kStftWaves - 1) / kStftWaves)), block(kStftBlock);
+    const int hw = stft_band_bound(a.half_width);
+    if (hw == 0) hipLaunchKernelGGL((record_spectrum<P, 0>), grid, block, 0, st, a);
+    else if (hw == 2) hipLaunchKernelGGL((record_spectrum<P, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((record_spectrum<P, 8>), grid, block, 0, st, a);
+}
+
+// The rows of lane-less handle `l`'s delivered call for (k, w) into its slot's row pool: once per delivered call and pair.  The band
+// pool is made to hold (k, w) first (record_band_run: a no-op where it does); the frames stay on the device.
+template <class P>
+int record_spectrum_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &hop, const EstimatesWork &work, int64_t frames) {
+    using C = typename stft_types<P>::C;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    if (qs.spec_k == k && qs.spec_w == w) return RT_OK;
+    const size_t n = qs.first_seg.size();
+    if (n == 0) {
+        qs.spec_k = k;
+        qs.spec_w = w;
+        return RT_OK;
+    }
+    if (n > (size_t)INT32_MAX) {  // (the kernel counts records in int32; the grid is a quarter of that)
+        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+        return RT_E_HIP;
+    }
+    const int rs = record_band_run<P>(h, l, entry, k, w, hop, frames);
+    if (rs != RT_OK) return rs;
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    const auto nomem = [&](const char *what, size_t bytes) {
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
+        return RT_E_NOMEM;
+    };
+    // the plan in one piece: frame_first [n + 1], range [n][4], lp [n]
+    const size_t B = (size_t)stft_band_columns(w);
+    const size_t row_bytes = n * sizeof(rt_record_spectrum), col_bytes = n * B * sizeof(double), pool_bytes = spectrum_pool_bytes(n, w);
+    static_assert(sizeof(rt_record_spectrum) == 48, "the row pool's layout: rows of 48 bytes, then the means, then the peaks");
+    const size_t b_first = (n + 1) * sizeof(int64_t), b_range = 4 * n * sizeof(int32_t), b_i32 = n * sizeof(int32_t);
+    const size_t o_range = b_first, o_lp = o_range + b_range, work_bytes = o_lp + b_i32;
+    if (qs.spec_bytes < pool_bytes || qs.spec_work_bytes < work_bytes) qs.spec_k = 0;  // (a pool that grows loses what it held)
+    if (!stft_hop_grow(&qs.d_spec, &qs.spec_bytes, pool_bytes)) return nomem("the call's spectrum rows", pool_bytes);
+    if (!stft_hop_grow(&qs.d_spec_work, &qs.spec_work_bytes, work_bytes)) return nomem("the spectrum's plan", work_bytes);
+    qs.spec_k = 0;  // (whatever the row pool held is gone from here on)
+    std::vector<char> packed(work_bytes);
+    std::memcpy(packed.data(), work.frame_first.data(), b_first);
+    std::memcpy(packed.data() + o_range, work.range.data(), b_range);
+    std::memcpy(packed.data() + o_lp, work.lp.data(), b_i32);
+    SpectrumArgs<P> a{};
+    a.values = reinterpret_cast<const C *>(qs.d_band_vals);
+    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_spec_work);
+    a.range = reinterpret_cast<const int32_t *>(qs.d_spec_work + o_range);
+    a.lp = reinterpret_cast<const int32_t *>(qs.d_spec_work + o_lp);
+    a.n_records = (int32_t)n;
+    a.hop_div = k;
+    a.half_width = w;
+    a.n_frames = frames;
+    a.rows = reinterpret_cast<rt_record_spectrum *>(qs.d_spec);
+    a.mean = reinterpret_cast<double *>(qs.d_spec + row_bytes);
+    a.peak = reinterpret_cast<double *>(qs.d_spec + row_bytes + col_bytes);
+    // (a pageable source: `packed` lives until the stream has been waited for below)
+    hipError_t e = hipMemcpyAsync(qs.d_spec_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        launch_record_spectrum<P>(a, q.s_gather);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
+        (void)hipGetLastError();
+        h->err = std::string(entry) + ": record_spectrum: " + hipGetErrorString(e);
+        return RT_E_HIP;
+    }
+    qs.spec_k = k;
+    qs.spec_w = w;
+    return RT_OK;
+}
+
+int fetch_record_spectrum_impl(rt_handle *h, const char *entry, int32_t hop_div, int32_t half_width, rt_record_spectrum *rows, double *mean, double *peak,
+                               size_t cap, size_t *n_out) {
+    if (!h || !n_out) return RT_E_INVALID;
+    *n_out = 0;
+    const int N = iq_nperseg(h);
+    const std::string why = spectrum_refusal(N, hop_div, half_width);
+    if (!why.empty()) {
+        h->err = std::string(entry) + ": " + why;
+        return RT_E_INVALID;
+    }
+    std::vector<rt_handle *> lanes;
+    size_t records = 0, samples = 0;
+    int bps = 0;
+    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    // every lane's plans, before anything is launched or written
+    std::vector<StftHopWork> hops(lanes.size());
+    std::vector<EstimatesWork> works(lanes.size());
+    std::vector<int64_t> frames(lanes.size());
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
+        const size_t n = qs.first_seg.size();
+        frames[i] = qs.start.size() == n && qs.end.size() == n && qs.fi.size() == n
+                        ? estimates_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.start.data(), qs.end.data(), n, N, hop_div, &works[i])
+                        : -1;
+        if (frames[i] < 0 || stft_band_elems(frames[i], half_width) < 0 ||
+            stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), n, N, hop_div, &hops[i]) != frames[i]) {
+            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
+            return RT_E_HIP;
+        }
+    }
+    *n_out = records;
+    const bool query = !rows || cap == 0;
+    if (query) return RT_OK;
+    if (cap < records) {
+        h->err = std::string(entry) + ": output buffer too small";
+        return RT_E_CAPACITY;
+    }
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const int rs = lanes[i]->f64 ? record_spectrum_run<double>(h, lanes[i], entry, hop_div, half_width, hops[i], works[i], frames[i])
+                                     : record_spectrum_run<float>(h, lanes[i], entry, hop_div, half_width, hops[i], works[i], frames[i]);
+        if (rs != RT_OK) return rs;
+    }
+    const size_t B = (size_t)stft_band_columns(half_width);
+    size_t r0 = 0;
+    for (rt_handle *l : lanes) {
+        const IqSlot &qs = l->riq->slot[l->riq->delivered];
+        const size_t n = qs.first_seg.size();
+        if (n) {
+            const size_t row_bytes = n * sizeof(rt_record_spectrum), col_bytes = n * B * sizeof(double);
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(rows + r0, qs.d_spec, row_bytes, hipMemcpyDeviceToHost));
+            if (mean) RT_HIP(h, hipMemcpy(mean + r0 * B, qs.d_spec + row_bytes, col_bytes, hipMemcpyDeviceToHost));
+            if (peak) RT_HIP(h, hipMemcpy(peak + r0 * B, qs.d_spec + row_bytes + col_bytes, col_bytes, hipMemcpyDeviceToHost));
         }
         r0 += n;
     }
@@ -4215,6 +4365,11 @@ int rt_fetch_record_band_f64(rt_handle *h, int32_t hop_div, int32_t half_width, 
 
 int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out) {
     return fetch_record_estimates_impl(h, "rt_fetch_record_estimates", hop_div, out, cap, n_out);
+}
+
+int rt_fetch_record_spectrum(rt_handle *h, int32_t hop_div, int32_t half_width, rt_record_spectrum *rows, double *mean, double *peak, size_t cap,
+                             size_t *n_out) {
+    return fetch_record_spectrum_impl(h, "rt_fetch_record_spectrum", hop_div, half_width, rows, mean, peak, cap, n_out);
 }
 
 // ---- rt_set_input_stats / rt_fetch_input_stats (include/rt_analyze.h) ----
