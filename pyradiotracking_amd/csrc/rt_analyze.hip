@@ -242,6 +242,26 @@ struct F64State {
 // One per lane-less handle, float32 or float64; a laned handle's lanes each own theirs.
 constexpr int kIqNone = -1, kIqExtract = -2, kIqTruncated = -3, kIqOff = -4;  // RecordIq::delivered without a slot
 constexpr size_t kInitialIqPoolBytes = 1u << 20;  // a slot's byte pool at first need; a call that wants more grows it inside rt_fetch
+// What an entry of the rt_fetch_record_* family leaves in a slot for its delivered call: an output pool, the work list its kernel
+// ran from, and the (hop_div, half_width) key the output was built for.  Nothing of a product is allocated, uploaded or launched
+// unless its entry is called (the estimates entry also makes the hop product, the spectrum entry the band product).
+struct IqProduct {
+    int k = 0, w = 0;       // `out` holds the delivered call's output for (k, w); k 0: it holds nothing
+    char *out = nullptr;
+    size_t out_bytes = 0;
+    char *work = nullptr;
+    size_t work_bytes = 0;
+    bool holds(int k_, int w_) const { return k != 0 && k == k_ && w == w_; }
+    void set(int k_, int w_) { k = k_, w = w_; }
+};
+// out / work of each product (cf: cd on a float64 handle):
+//   kProdStft  rt_fetch_record_stft, key (1, 0): [offsets.back() / N] cf / StftWork: seg_first, fi
+//   kProdHop   rt_fetch_record_stft_hop, key (k, 0): [frames] cf / StftHopWork: frame_first, pool_seg, lp, fi
+//   kProdBand  rt_fetch_record_band: [frames][2 w + 1] cf / StftHopWork, as the hop product's
+//   kProdEst   rt_fetch_record_estimates, key (k, 0): [records] rt_record_estimate / the turn-back table, then EstimatesWork
+//   kProdSpec  rt_fetch_record_spectrum: [records] rt_record_spectrum, then mean and peak [records][2 w + 1] float64 /
+//              EstimatesWork: frame_first, range, lp
+enum { kProdStft, kProdHop, kProdBand, kProdEst, kProdSpec, kProducts };
 struct IqSlot {
     int32_t *h_rows = nullptr, *d_rows = nullptr;    // [S] IqCall::write_buf, pinned / device (iq_tails reads it)
     char *d_pool = nullptr;                          // the snippets of the slot's delivered call, in record order
@@ -253,40 +273,11 @@ struct IqSlot {
     int bps = 0;                                     // bytes per sample of the delivered call
     int state = RT_OK;                               // what the gather left: RT_OK, RT_E_NOMEM, RT_E_HIP
     std::string why;
-    // rt_fetch_record_stft (rt_record_stft.h): what the gather notes for it, and what the entry's first call for this delivered
-    // call leaves -- nothing below is allocated, uploaded or launched unless that entry is called
+    // the rt_fetch_record_* family: what the gather notes for it, and what each entry's first call for this delivered call leaves
     std::vector<int32_t> fi;                         // [records] the records' bins
+    std::vector<int32_t> start, end;                 // [records] the records' cells
     int fmt = kFmtC64;                               // the delivered call's input format (bps does not tell uint8 from int8)
-    bool stft_done = false;                          // d_vals holds the delivered call's values
-    char *d_vals = nullptr;                          // [offsets.back() / N] cf, or cd on a float64 handle
-    size_t vals_bytes = 0;
-    char *d_work = nullptr;                          // StftWork: the prefix, then the bins
-    size_t work_bytes = 0;
-    // rt_fetch_record_stft_hop (rt_record_stft_hop.h): a value pool and a work list of its own, and the hop they were built for
-    int hop_k = 0;                                   // d_hop_vals holds the delivered call's frames at nperseg / hop_k; 0: none
-    char *d_hop_vals = nullptr;                      // [frames] cf, or cd on a float64 handle
-    size_t hop_vals_bytes = 0;
-    char *d_hop_work = nullptr;                      // StftHopWork: frame_first, pool_seg, lp, fi
-    size_t hop_work_bytes = 0;
-    // rt_fetch_record_estimates (rt_record_estimates.h): the records' cells as the gather notes them, the rows and their plan
-    std::vector<int32_t> start, end;                 // [records]
-    int est_k = 0;                                   // d_est holds the delivered call's rows for this hop_div; 0: none
-    char *d_est = nullptr;                           // [records] rt_record_estimate
-    size_t est_bytes = 0;
-    char *d_est_work = nullptr;                      // the turn-back table, then EstimatesWork
-    size_t est_work_bytes = 0;
-    // rt_fetch_record_band (rt_record_band.h): a value pool and a work list of its own, and the (k, w) they were built for
-    int band_k = 0, band_w = 0;                      // d_band_vals holds the delivered call's frames for (band_k, band_w); k 0: none
-    char *d_band_vals = nullptr;                     // [frames][2 w + 1] cf, or cd on a float64 handle
-    size_t band_vals_bytes = 0;
-    char *d_band_work = nullptr;                     // StftHopWork: frame_first, pool_seg, lp, fi
-    size_t band_work_bytes = 0;
-    // rt_fetch_record_spectrum (rt_record_spectrum.h): the rows, means and peaks reduced from the band pool, and their plan
-    int spec_k = 0, spec_w = 0;                      // d_spec holds the delivered call's rows for (spec_k, spec_w); k 0: none
-    char *d_spec = nullptr;                          // [records] rt_record_spectrum, then mean and peak [records][2 w + 1] float64
-    size_t spec_bytes = 0;
-    char *d_spec_work = nullptr;                     // EstimatesWork: frame_first, range, lp
-    size_t spec_work_bytes = 0;
+    IqProduct prod[kProducts];
 };
 struct RecordIq {
     char *d_tails = nullptr;   // [kIqRows][S][row_bytes]
@@ -1451,11 +1442,7 @@ void iq_gather(rt_handle *h, int idx, const IqCall &call, const void *rec, size_
     qs.offsets.assign(n + 1, 0);
     qs.first_seg.assign(n, 0);
     qs.fmt = call.fmt;
-    qs.stft_done = false;
-    qs.hop_k = 0;
-    qs.est_k = 0;
-    qs.band_k = 0;
-    qs.spec_k = 0;
+    for (IqProduct &p : qs.prod) p.k = 0;
     qs.fi.resize(n);
     qs.start.resize(n);
     qs.end.resize(n);
@@ -1534,16 +1521,10 @@ void iq_free(rt_handle *h) {
         (void)hipFree(qs.d_pool);
         (void)hipHostFree(qs.h_descs);
         (void)hipFree(qs.d_descs);
-        (void)hipFree(qs.d_vals);
-        (void)hipFree(qs.d_work);
-        (void)hipFree(qs.d_hop_vals);
-        (void)hipFree(qs.d_hop_work);
-        (void)hipFree(qs.d_est);
-        (void)hipFree(qs.d_est_work);
-        (void)hipFree(qs.d_band_vals);
-        (void)hipFree(qs.d_band_work);
-        (void)hipFree(qs.d_spec);
-        (void)hipFree(qs.d_spec_work);
+        for (IqProduct &p : qs.prod) {
+            (void)hipFree(p.out);
+            (void)hipFree(p.work);
+        }
     }
     (void)hipFree(q->d_stft_tw);
     (void)hipFree(q->d_stft_win);
@@ -1584,184 +1565,56 @@ int iq_delivered_call(rt_handle *h, const char *entry, std::vector<rt_handle *> 
     return RT_OK;
 }
 
-// ---- rt_fetch_record_stft: one complex STFT value per delivered segment (rt_record_stft.h; the work list: rt_record_stft_book.h) ----
-template <class P, int FMT>
-void launch_record_stft(const StftArgs<P> &a, hipStream_t st) {
-    const int64_t blocks = (a.n_segs + kStftWaves - 1) / kStftWaves;
-    hipLaunchKernelGGL((record_stft<P, FMT>), dim3((unsigned)blocks), dim3(kStftBlock), 0, st, a);
+// ---- the rt_fetch_record_* family on the delivered call's byte pool (the plans: rt_record_stft_book.h).  Three entries hand out
+// frames -- rt_fetch_record_stft, _stft_hop, _band -- and two one row per record, reduced on the device from the hop and the band
+// product: rt_fetch_record_estimates, _spectrum.  Each leaves an IqProduct in the slot; what they share stands here once. ----
+// Every message starts with the entry's name and goes to `h`, the handle the caller holds; the work is done on `l`, the lane-less
+// handle that holds the records.
+inline int record_refuse(rt_handle *h, const char *entry, const std::string &why, int code = RT_E_INVALID) {
+    h->err = std::string(entry) + ": " + why;
+    return code;
+}
+inline int record_mismatch(rt_handle *h, const char *entry) {
+    return record_refuse(h, entry, "internal: the delivered call's record list does not match its snippets", RT_E_HIP);
+}
+inline int record_nomem(rt_handle *h, const char *entry, const char *what, size_t bytes) {
+    (void)hipGetLastError();
+    return record_refuse(h, entry, std::string("no device memory for ") + what + " (" + std::to_string(bytes) + " bytes)", RT_E_NOMEM);
 }
 
-// The values of lane-less handle `l`'s delivered call into its slot's value pool, once per delivered call: the twiddle table and
-// (float32) the window go to the device with the first call of the entry on the handle, the value pool grows on demand like the
-// byte pool, the kernel runs on the gather's stream and is waited for.  The error text goes to `h` (the handle the caller holds).
+// The twiddle table and (float32: a float64 handle's is F64State::d_window) the window go to the device with the first call of any
+// entry of the family that has something to compute, and are shared by all of them.
 template <class P>
-int record_stft_run(rt_handle *h, rt_handle *l, const char *entry) {
+int record_tables(rt_handle *h, rt_handle *l, const char *entry) {
     using C = typename stft_types<P>::C;
     RecordIq &q = *l->riq;
-    IqSlot &qs = q.slot[q.delivered];
-    if (qs.stft_done) return RT_OK;
     const int N = iq_nperseg(l);
-    const size_t n = qs.first_seg.size();
-    StftWork work;
-    const int64_t cells = stft_build_work(qs.offsets.data(), qs.fi.data(), n, N, &work);
-    if (cells < 0 || (uint64_t)cells * (uint64_t)N * (uint64_t)qs.bps > qs.pool_bytes || (cells > 0 && !qs.d_pool) ||
-        (cells + kStftWaves - 1) / kStftWaves > 0x7fffffffll) {
-        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-        return RT_E_HIP;
-    }
-    if (cells == 0) {
-        qs.stft_done = true;
-        return RT_OK;
-    }
-    RT_HIP(h, hipSetDevice(l->cfg.device));
-    const auto nomem = [&](const char *what, size_t bytes) {
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
-        return RT_E_NOMEM;
+    const auto upload = [&](const void *src, size_t bytes, const char *what, void **to) {
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes) != hipSuccess) return record_nomem(h, entry, what, bytes);
+        if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            return record_refuse(h, entry, std::string("uploading ") + what + " failed", RT_E_HIP);
+        }
+        *to = d;
+        return (int)RT_OK;
     };
     if (!q.d_stft_tw) {
         const std::vector<C> tw = record_stft_twiddles<C, typename std::conditional<sizeof(P) == 4, double, long double>::type>(N);
-        void *d = nullptr;
-        if (hipMalloc(&d, tw.size() * sizeof(C)) != hipSuccess) return nomem("the twiddle table", tw.size() * sizeof(C));
-        if (hipMemcpy(d, tw.data(), tw.size() * sizeof(C), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            h->err = std::string(entry) + ": uploading the twiddle table failed";
-            return RT_E_HIP;
-        }
-        q.d_stft_tw = d;
+        const int rc = upload(tw.data(), tw.size() * sizeof(C), "the twiddle table", &q.d_stft_tw);
+        if (rc != RT_OK) return rc;
     }
     if (!l->f64 && !q.d_stft_win) {
-        float *d = nullptr;
-        if (hipMalloc(&d, (size_t)N * sizeof(float)) != hipSuccess) return nomem("the window", (size_t)N * sizeof(float));
-        if (hipMemcpy(d, l->h_window.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            h->err = std::string(entry) + ": uploading the window failed";
-            return RT_E_HIP;
-        }
-        q.d_stft_win = d;
-    }
-    const size_t val_bytes = (size_t)cells * sizeof(C);
-    if (qs.vals_bytes < val_bytes) {
-        (void)hipFree(qs.d_vals);
-        qs.d_vals = nullptr;
-        const size_t want = std::max(val_bytes, std::max(qs.vals_bytes * 2, (size_t)1 << 16));
-        qs.vals_bytes = 0;
-        if (hipMalloc(&qs.d_vals, want) != hipSuccess) {
-            (void)hipGetLastError();
-            if (want == val_bytes || hipMalloc(&qs.d_vals, val_bytes) != hipSuccess) return nomem("the call's values", val_bytes);
-            qs.vals_bytes = val_bytes;
-        } else {
-            qs.vals_bytes = want;
-        }
-    }
-    const size_t prefix_bytes = (n + 1) * sizeof(int64_t), work_bytes = prefix_bytes + n * sizeof(int32_t);
-    if (qs.work_bytes < work_bytes) {
-        (void)hipFree(qs.d_work);
-        qs.d_work = nullptr;
-        qs.work_bytes = 0;
-        const size_t want = std::max(work_bytes, (size_t)1 << 16);
-        if (hipMalloc(&qs.d_work, want) != hipSuccess) return nomem("the work list", want);
-        qs.work_bytes = want;
-    }
-    StftArgs<P> a{};
-    a.pool = qs.d_pool;
-    a.seg_first = reinterpret_cast<const int64_t *>(qs.d_work);
-    a.fi = reinterpret_cast<const int32_t *>(qs.d_work + prefix_bytes);
-    a.n_records = (int32_t)n;
-    a.nperseg = N;
-    a.n_segs = cells;
-    a.tw = static_cast<const C *>(q.d_stft_tw);
-    a.values = reinterpret_cast<C *>(qs.d_vals);
-    if constexpr (sizeof(P) == 4) {
-        a.window = q.d_stft_win;
-        a.root = stft_root_f32(l->cfg.scale);
-    } else {
-        a.window = l->f64->d_window;
-        a.root = stft_root_f64(l->f64->c.scale);
-    }
-    // (pageable sources: `work` lives until the stream has been waited for below)
-    hipError_t e = hipMemcpyAsync(qs.d_work, work.seg_first.data(), prefix_bytes, hipMemcpyHostToDevice, q.s_gather);
-    if (e == hipSuccess) e = hipMemcpyAsync(qs.d_work + prefix_bytes, work.fi.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, q.s_gather);
-    if (e == hipSuccess) {
-        if (qs.fmt == kFmtU8) launch_record_stft<P, kFmtU8>(a, q.s_gather);
-        else if (qs.fmt == kFmtI16) launch_record_stft<P, kFmtI16>(a, q.s_gather);
-        else if (qs.fmt == kFmtI8) launch_record_stft<P, kFmtI8>(a, q.s_gather);
-        else launch_record_stft<P, kFmtC64>(a, q.s_gather);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(q.s_gather);  // (`work` must outlive whatever copy did start)
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": record_stft: " + hipGetErrorString(e);
-        return RT_E_HIP;
-    }
-    qs.stft_done = true;
-    return RT_OK;
-}
-
-template <class P>
-int fetch_record_stft_impl(rt_handle *h, const char *entry, const char *twin, int64_t *offsets, size_t n_offsets, int32_t *first_seg,
-                                  size_t n_first, P *values, size_t cap_cells, size_t *n_cells) {
-    using C = typename stft_types<P>::C;
-    if (!h || !n_cells) return RT_E_INVALID;
-    *n_cells = 0;
-    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
-        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
-        return RT_E_INVALID;
-    }
-    std::vector<rt_handle *> lanes;
-    size_t records = 0, samples = 0;
-    int bps = 0;
-    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
-    if (rc != RT_OK) return rc;
-    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
-        h->err = std::string(entry) + ": n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
-        return RT_E_INVALID;
-    }
-    const size_t N = (size_t)iq_nperseg(h);
-    *n_cells = samples / N;
-    const bool query = !values || cap_cells == 0;
-    if (!query && cap_cells < *n_cells) {
-        h->err = std::string(entry) + ": output buffer too small";
-        return RT_E_CAPACITY;
-    }
-    if (!query)
-        for (rt_handle *l : lanes) {
-            const int rs = record_stft_run<P>(h, l, entry);
-            if (rs != RT_OK) return rs;
-        }
-    size_t r0 = 0, c0 = 0;
-    if (offsets) offsets[0] = 0;
-    for (rt_handle *l : lanes) {
-        const IqSlot &qs = l->riq->slot[l->riq->delivered];
-        const size_t n = qs.first_seg.size(), mine = (size_t)qs.offsets.back() / N;
-        if (offsets)
-            for (size_t i = 0; i < n; ++i) offsets[r0 + i + 1] = (int64_t)c0 + qs.offsets[i + 1] / (int64_t)N;
-        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
-        if (!query && mine) {
-            RT_HIP(h, hipSetDevice(l->cfg.device));
-            RT_HIP(h, hipMemcpy(values + 2 * c0, qs.d_vals, mine * sizeof(C), hipMemcpyDeviceToHost));
-        }
-        r0 += n;
-        c0 += mine;
+        void *d = nullptr;
+        const int rc = upload(l->h_window.data(), (size_t)N * sizeof(float), "the window", &d);
+        if (rc != RT_OK) return rc;
+        q.d_stft_win = static_cast<float *>(d);
     }
     return RT_OK;
-}
-
-// ---- rt_fetch_record_stft_hop: the same values for frames every nperseg / k samples (rt_record_stft_hop.h) ----
-template <class P, int FMT>
-void launch_record_stft_hop(const StftHopArgs<P> &a, int group, hipStream_t st) {
-    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
-    const dim3 grid((unsigned)((a.n_frames + per_block - 1) / per_block)), block(kStftBlock);
-    if (group == 8) hipLaunchKernelGGL((record_stft_hop<P, FMT, 8>), grid, block, 0, st, a);
-    else if (group == 16) hipLaunchKernelGGL((record_stft_hop<P, FMT, 16>), grid, block, 0, st, a);
-    else if (group == 32) hipLaunchKernelGGL((record_stft_hop<P, FMT, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((record_stft_hop<P, FMT, 64>), grid, block, 0, st, a);
 }
 
 // a device pool that grows on demand, like the byte pool: at least `need` bytes in *p, doubling
-inline bool stft_hop_grow(char **p, size_t *have, size_t need) {
+inline bool product_grow(char **p, size_t *have, size_t need) {
     if (*have >= need) return true;
     (void)hipFree(*p);
     *p = nullptr;
@@ -1781,79 +1634,58 @@ inline bool stft_hop_grow(char **p, size_t *have, size_t need) {
     return true;
 }
 
-// The frames of lane-less handle `l`'s delivered call at hop nperseg / k into its slot's hop pool: once per delivered call and k
-// (record_stft_run's twin; it shares that entry's twiddle table and window, made by whichever entry is called first, and nothing
-// else -- the value pool, the work list and the k they hold are this entry's own).
-template <class P>
-int record_stft_hop_run(rt_handle *h, rt_handle *l, const char *entry, int k, const StftHopWork &work, int64_t frames) {
-    using C = typename stft_types<P>::C;
-    RecordIq &q = *l->riq;
-    IqSlot &qs = q.slot[q.delivered];
-    if (qs.hop_k == k) return RT_OK;
-    const int N = iq_nperseg(l);
-    const size_t n = qs.first_seg.size();
-    const int group = stft_hop_group(N, qs.bps);
-    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
-    if ((uint64_t)qs.offsets.back() * (uint64_t)qs.bps > qs.pool_bytes || (frames > 0 && !qs.d_pool) || (frames + per_block - 1) / per_block > 0x7fffffffll) {
-        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-        return RT_E_HIP;
+// A product that does not hold the wanted key is built in two steps.  The first makes room: the key goes before either pool is
+// touched -- a pool that grows loses what it held, and whatever it held is gone once the kernel writes -- so a call that fails from
+// here on leaves a product that holds nothing, never one that names values it has lost.
+inline int product_begin(rt_handle *h, const char *entry, IqProduct &p, size_t out_bytes, const char *out_what, size_t work_bytes, const char *work_what) {
+    p.k = 0;
+    if (!product_grow(&p.out, &p.out_bytes, out_bytes)) return record_nomem(h, entry, out_what, out_bytes);
+    if (!product_grow(&p.work, &p.work_bytes, work_bytes)) return record_nomem(h, entry, work_what, work_bytes);
+    return RT_OK;
+}
+// The second uploads the work list `packed` into p.work, runs `launch` behind it on the gather's stream and waits; the product
+// holds (k, w) only where all of that went well.  `packed` is a pageable source: it lives until the stream has been waited for.
+template <class Launch>
+int product_finish(rt_handle *h, RecordIq &q, const char *entry, IqProduct &p, int k, int w, const std::vector<char> &packed, const char *kernel,
+                   Launch launch) {
+    hipError_t e = hipMemcpyAsync(p.work, packed.data(), packed.size(), hipMemcpyHostToDevice, q.s_gather);
+    if (e == hipSuccess) {
+        launch();
+        e = hipGetLastError();
     }
-    if (frames == 0) {
-        qs.hop_k = k;
-        return RT_OK;
-    }
-    RT_HIP(h, hipSetDevice(l->cfg.device));
-    const auto nomem = [&](const char *what, size_t bytes) {
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
         (void)hipGetLastError();
-        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
-        return RT_E_NOMEM;
-    };
-    if (!q.d_stft_tw) {
-        const std::vector<C> tw = record_stft_twiddles<C, typename std::conditional<sizeof(P) == 4, double, long double>::type>(N);
-        void *d = nullptr;
-        if (hipMalloc(&d, tw.size() * sizeof(C)) != hipSuccess) return nomem("the twiddle table", tw.size() * sizeof(C));
-        if (hipMemcpy(d, tw.data(), tw.size() * sizeof(C), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            h->err = std::string(entry) + ": uploading the twiddle table failed";
-            return RT_E_HIP;
-        }
-        q.d_stft_tw = d;
+        return record_refuse(h, entry, std::string(kernel) + ": " + hipGetErrorString(e), RT_E_HIP);
     }
-    if (!l->f64 && !q.d_stft_win) {
-        float *d = nullptr;
-        if (hipMalloc(&d, (size_t)N * sizeof(float)) != hipSuccess) return nomem("the window", (size_t)N * sizeof(float));
-        if (hipMemcpy(d, l->h_window.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            h->err = std::string(entry) + ": uploading the window failed";
-            return RT_E_HIP;
-        }
-        q.d_stft_win = d;
-    }
-    qs.hop_k = 0;  // (whatever the pool held is gone from here on)
-    const size_t val_bytes = (size_t)frames * sizeof(C);
-    if (!stft_hop_grow(&qs.d_hop_vals, &qs.hop_vals_bytes, val_bytes)) return nomem("the call's frames", val_bytes);
-    // the work list in one piece: frame_first [n + 1], pool_seg [n], lp [n], fi [n]
-    const size_t b_first = (n + 1) * sizeof(int64_t), b_seg = n * sizeof(int64_t), b_i32 = n * sizeof(int32_t);
-    const size_t work_bytes = b_first + b_seg + 2 * b_i32;
-    if (!stft_hop_grow(&qs.d_hop_work, &qs.hop_work_bytes, work_bytes)) return nomem("the work list", work_bytes);
-    std::vector<char> packed(work_bytes);
-    std::memcpy(packed.data(), work.frame_first.data(), b_first);
-    std::memcpy(packed.data() + b_first, work.pool_seg.data(), b_seg);
-    std::memcpy(packed.data() + b_first + b_seg, work.lp.data(), b_i32);
-    std::memcpy(packed.data() + b_first + b_seg + b_i32, work.fi.data(), b_i32);
-    StftHopArgs<P> a{};
+    p.set(k, w);
+    return RT_OK;
+}
+
+// `f` with the delivered call's input format as a compile-time constant: f(std::integral_constant<int, kFmt...>)
+template <class F>
+void with_record_format(int fmt, F f) {
+    if (fmt == kFmtU8) f(std::integral_constant<int, kFmtU8>{});
+    else if (fmt == kFmtI16) f(std::integral_constant<int, kFmtI16>{});
+    else if (fmt == kFmtI8) f(std::integral_constant<int, kFmtI8>{});
+    else f(std::integral_constant<int, kFmtC64>{});
+}
+
+// in front of a launch that reads the byte pool: the pool holds what the record list says, and the grid fits an unsigned
+inline bool record_pool_ok(const IqSlot &qs, int64_t frames, int64_t per_block) {
+    return (uint64_t)qs.offsets.back() * (uint64_t)qs.bps <= qs.pool_bytes && (frames == 0 || qs.d_pool) && (frames + per_block - 1) / per_block <= 0x7fffffffll;
+}
+
+// what the arguments of record_stft and record_stft_hop share: the byte pool, the tables and sqrt(scale)
+template <class P, class Args>
+void record_pool_args(rt_handle *l, Args &a) {
+    const RecordIq &q = *l->riq;
+    const IqSlot &qs = q.slot[q.delivered];
     a.pool = qs.d_pool;
-    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_hop_work);
-    a.pool_seg = reinterpret_cast<const int64_t *>(qs.d_hop_work + b_first);
-    a.lp = reinterpret_cast<const int32_t *>(qs.d_hop_work + b_first + b_seg);
-    a.fi = reinterpret_cast<const int32_t *>(qs.d_hop_work + b_first + b_seg + b_i32);
-    a.n_records = (int32_t)n;
-    a.nperseg = N;
-    a.hop_div = k;
-    a.n_frames = frames;
-    a.pool_samples = qs.offsets.back();
-    a.tw = static_cast<const C *>(q.d_stft_tw);
-    a.values = reinterpret_cast<C *>(qs.d_hop_vals);
+    a.n_records = (int32_t)qs.first_seg.size();
+    a.nperseg = iq_nperseg(l);
+    a.tw = static_cast<const typename stft_types<P>::C *>(q.d_stft_tw);
     if constexpr (sizeof(P) == 4) {
         a.window = q.d_stft_win;
         a.root = stft_root_f32(l->cfg.scale);
@@ -1861,92 +1693,114 @@ int record_stft_hop_run(rt_handle *h, rt_handle *l, const char *entry, int k, co
         a.window = l->f64->d_window;
         a.root = stft_root_f64(l->f64->c.scale);
     }
-    // (a pageable source: `packed` lives until the stream has been waited for below)
-    hipError_t e = hipMemcpyAsync(qs.d_hop_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
-    if (e == hipSuccess) {
-        if (qs.fmt == kFmtU8) launch_record_stft_hop<P, kFmtU8>(a, group, q.s_gather);
-        else if (qs.fmt == kFmtI16) launch_record_stft_hop<P, kFmtI16>(a, group, q.s_gather);
-        else if (qs.fmt == kFmtI8) launch_record_stft_hop<P, kFmtI8>(a, group, q.s_gather);
-        else launch_record_stft_hop<P, kFmtC64>(a, group, q.s_gather);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": record_stft_hop: " + hipGetErrorString(e);
-        return RT_E_HIP;
-    }
-    qs.hop_k = k;
-    return RT_OK;
 }
 
+// ---- rt_fetch_record_stft: one complex STFT value per delivered segment (rt_record_stft.h) ----
+template <class P, int FMT>
+void launch_record_stft(const StftArgs<P> &a, hipStream_t st) {
+    const int64_t blocks = (a.n_segs + kStftWaves - 1) / kStftWaves;
+    hipLaunchKernelGGL((record_stft<P, FMT>), dim3((unsigned)blocks), dim3(kStftBlock), 0, st, a);
+}
+
+// The values of lane-less handle `l`'s delivered call into its slot's kProdStft, once per delivered call, under key (1, 0).  A frame
+// is a delivered segment here, so the entry has no frame plan (record_plan): the kernel's list is made where it is needed -- a
+// repeated call, which only copies, pays for none.
 template <class P>
-int fetch_record_stft_hop_impl(rt_handle *h, const char *entry, const char *twin, int32_t hop_div, int64_t *offsets, size_t n_offsets,
-                               int32_t *first_seg, size_t n_first, P *values, size_t cap_frames, size_t *n_frames) {
+int record_stft_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &, int64_t) {
     using C = typename stft_types<P>::C;
-    if (!h || !n_frames) return RT_E_INVALID;
-    *n_frames = 0;
-    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
-        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
-        return RT_E_INVALID;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    IqProduct &p = qs.prod[kProdStft];
+    if (p.holds(k, w)) return RT_OK;
+    const size_t n = qs.first_seg.size();
+    StftWork work;
+    const int64_t cells = stft_build_work(qs.offsets.data(), qs.fi.data(), n, iq_nperseg(l), &work);
+    if (cells < 0 || !record_pool_ok(qs, cells, kStftWaves)) return record_mismatch(h, entry);
+    if (cells == 0) {
+        p.set(k, w);
+        return RT_OK;
     }
-    const int N = iq_nperseg(h);
-    if (!stft_hop_div_ok(N, hop_div)) {
-        h->err = std::string(entry) + ": hop_div k = " + std::to_string(hop_div) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) +
-                 " and divide nperseg N = " + std::to_string(N);
-        return RT_E_INVALID;
-    }
-    std::vector<rt_handle *> lanes;
-    size_t records = 0, samples = 0;
-    int bps = 0;
-    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    int rc = record_tables<P>(h, l, entry);
     if (rc != RT_OK) return rc;
-    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
-        h->err = std::string(entry) + ": n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
-        return RT_E_INVALID;
+    // the work list in one piece: seg_first [n + 1], fi [n]
+    const size_t b_first = (n + 1) * sizeof(int64_t), b_i32 = n * sizeof(int32_t);
+    rc = product_begin(h, entry, p, (size_t)cells * sizeof(C), "the call's values", b_first + b_i32, "the work list");
+    if (rc != RT_OK) return rc;
+    std::vector<char> packed(b_first + b_i32);
+    std::memcpy(packed.data(), work.seg_first.data(), b_first);
+    std::memcpy(packed.data() + b_first, work.fi.data(), b_i32);
+    StftArgs<P> a{};
+    record_pool_args<P>(l, a);
+    a.seg_first = reinterpret_cast<const int64_t *>(p.work);
+    a.fi = reinterpret_cast<const int32_t *>(p.work + b_first);
+    a.n_segs = cells;
+    a.values = reinterpret_cast<C *>(p.out);
+    return product_finish(h, q, entry, p, k, w, packed, "record_stft", [&] {
+        with_record_format(qs.fmt, [&](auto fmt) { launch_record_stft<P, decltype(fmt)::value>(a, q.s_gather); });
+    });
+}
+
+// ---- rt_fetch_record_stft_hop: the same values for frames every nperseg / k samples (rt_record_stft_hop.h) ----
+template <class P, int FMT>
+void launch_record_stft_hop(const StftHopArgs<P> &a, int group, hipStream_t st) {
+    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
+    const dim3 grid((unsigned)((a.n_frames + per_block - 1) / per_block)), block(kStftBlock);
+    if (group == 8) hipLaunchKernelGGL((record_stft_hop<P, FMT, 8>), grid, block, 0, st, a);
+    else if (group == 16) hipLaunchKernelGGL((record_stft_hop<P, FMT, 16>), grid, block, 0, st, a);
+    else if (group == 32) hipLaunchKernelGGL((record_stft_hop<P, FMT, 32>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((record_stft_hop<P, FMT, 64>), grid, block, 0, st, a);
+}
+
+// The hop and the band product run from the same work list, in one piece: frame_first [n + 1], pool_seg [n], lp [n], fi [n].
+inline size_t hop_work_bytes(size_t n) { return (n + 1) * sizeof(int64_t) + n * sizeof(int64_t) + 2 * n * sizeof(int32_t); }
+// `work` packed for the upload, and the kernel's arguments against product `p`, whose pools product_begin has made
+template <class P>
+StftHopArgs<P> hop_args(rt_handle *l, const IqProduct &p, int k, const StftHopWork &work, int64_t frames, std::vector<char> *packed) {
+    const IqSlot &qs = l->riq->slot[l->riq->delivered];
+    const size_t n = qs.first_seg.size(), b_first = (n + 1) * sizeof(int64_t), b_seg = n * sizeof(int64_t), b_i32 = n * sizeof(int32_t);
+    packed->resize(hop_work_bytes(n));
+    std::memcpy(packed->data(), work.frame_first.data(), b_first);
+    std::memcpy(packed->data() + b_first, work.pool_seg.data(), b_seg);
+    std::memcpy(packed->data() + b_first + b_seg, work.lp.data(), b_i32);
+    std::memcpy(packed->data() + b_first + b_seg + b_i32, work.fi.data(), b_i32);
+    StftHopArgs<P> a{};
+    record_pool_args<P>(l, a);
+    a.frame_first = reinterpret_cast<const int64_t *>(p.work);
+    a.pool_seg = reinterpret_cast<const int64_t *>(p.work + b_first);
+    a.lp = reinterpret_cast<const int32_t *>(p.work + b_first + b_seg);
+    a.fi = reinterpret_cast<const int32_t *>(p.work + b_first + b_seg + b_i32);
+    a.hop_div = k;
+    a.n_frames = frames;
+    a.pool_samples = qs.offsets.back();
+    a.values = reinterpret_cast<typename stft_types<P>::C *>(p.out);
+    return a;
+}
+
+// The frames of lane-less handle `l`'s delivered call at hop nperseg / k into its slot's kProdHop: once per delivered call and k.
+template <class P>
+int record_stft_hop_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &work, int64_t frames) {
+    using C = typename stft_types<P>::C;
+    RecordIq &q = *l->riq;
+    IqSlot &qs = q.slot[q.delivered];
+    IqProduct &p = qs.prod[kProdHop];
+    if (p.holds(k, w)) return RT_OK;
+    const int group = stft_hop_group(iq_nperseg(l), qs.bps);
+    if (!record_pool_ok(qs, frames, (int64_t)kStftWaves * (64 / group))) return record_mismatch(h, entry);
+    if (frames == 0) {
+        p.set(k, w);
+        return RT_OK;
     }
-    // every lane's frame plan, before anything is launched or written
-    std::vector<StftHopWork> works(lanes.size());
-    std::vector<int64_t> frames(lanes.size());
-    size_t total = 0;
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
-        frames[i] = stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.first_seg.size(), N, hop_div, &works[i]);
-        if (frames[i] < 0) {
-            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-            return RT_E_HIP;
-        }
-        total += (size_t)frames[i];
-    }
-    *n_frames = total;
-    const bool query = !values || cap_frames == 0;
-    if (!query && cap_frames < total) {
-        h->err = std::string(entry) + ": output buffer too small";
-        return RT_E_CAPACITY;
-    }
-    if (!query)
-        for (size_t i = 0; i < lanes.size(); ++i) {
-            const int rs = record_stft_hop_run<P>(h, lanes[i], entry, hop_div, works[i], frames[i]);
-            if (rs != RT_OK) return rs;
-        }
-    size_t r0 = 0, c0 = 0;
-    if (offsets) offsets[0] = 0;
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        rt_handle *l = lanes[i];
-        const IqSlot &qs = l->riq->slot[l->riq->delivered];
-        const size_t n = qs.first_seg.size(), mine = (size_t)frames[i];
-        if (offsets)
-            for (size_t r = 0; r < n; ++r) offsets[r0 + r + 1] = (int64_t)c0 + works[i].frame_first[r + 1];
-        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
-        if (!query && mine) {
-            RT_HIP(h, hipSetDevice(l->cfg.device));
-            RT_HIP(h, hipMemcpy(values + 2 * c0, qs.d_hop_vals, mine * sizeof(C), hipMemcpyDeviceToHost));
-        }
-        r0 += n;
-        c0 += mine;
-    }
-    return RT_OK;
+    RT_HIP(h, hipSetDevice(l->cfg.device));
+    int rc = record_tables<P>(h, l, entry);
+    if (rc != RT_OK) return rc;
+    rc = product_begin(h, entry, p, (size_t)frames * sizeof(C), "the call's frames", hop_work_bytes(qs.first_seg.size()), "the work list");
+    if (rc != RT_OK) return rc;
+    std::vector<char> packed;
+    const StftHopArgs<P> a = hop_args<P>(l, p, k, work, frames, &packed);
+    return product_finish(h, q, entry, p, k, w, packed, "record_stft_hop", [&] {
+        with_record_format(qs.fmt, [&](auto fmt) { launch_record_stft_hop<P, decltype(fmt)::value>(a, group, q.s_gather); });
+    });
 }
 
 // ---- rt_fetch_record_band: the 2 w + 1 bins around each record's bin, frame by frame (rt_record_band.h) ----
@@ -1968,217 +1822,62 @@ void launch_record_band(const StftBandArgs<P> &a, int group, hipStream_t st) {
     else launch_record_band_hw<P, FMT, 8>(a, group, st);
 }
 
-// The band of lane-less handle `l`'s delivered call for (k, w) into its slot's band pool: once per delivered call and pair
-// (record_stft_hop_run's twin: it shares the twiddle table and the window with the STFT entries, made by whichever is called
-// first, and nothing else -- the value pool, the work list and the pair they hold are this entry's own).
+// The band of lane-less handle `l`'s delivered call for (k, w) into its slot's kProdBand: once per delivered call and pair.  The
+// frames and the work list are the hop entry's; the pools and the pair they hold are this product's own.
 template <class P>
 int record_band_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &work, int64_t frames) {
     using C = typename stft_types<P>::C;
     RecordIq &q = *l->riq;
     IqSlot &qs = q.slot[q.delivered];
-    if (qs.band_k == k && qs.band_w == w) return RT_OK;
-    const int N = iq_nperseg(l);
-    const size_t n = qs.first_seg.size();
-    const int group = stft_hop_group(N, qs.bps);
-    const int64_t per_block = (int64_t)kStftWaves * (64 / group);
+    IqProduct &p = qs.prod[kProdBand];
+    if (p.holds(k, w)) return RT_OK;
+    const int group = stft_hop_group(iq_nperseg(l), qs.bps);
     const int64_t elems = stft_band_elems(frames, w);
-    if ((uint64_t)qs.offsets.back() * (uint64_t)qs.bps > qs.pool_bytes || (frames > 0 && !qs.d_pool) || elems < 0 ||
-        (frames + per_block - 1) / per_block > 0x7fffffffll) {
-        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-        return RT_E_HIP;
-    }
+    if (elems < 0 || !record_pool_ok(qs, frames, (int64_t)kStftWaves * (64 / group))) return record_mismatch(h, entry);
     if (frames == 0) {
-        qs.band_k = k;
-        qs.band_w = w;
+        p.set(k, w);
         return RT_OK;
     }
     RT_HIP(h, hipSetDevice(l->cfg.device));
-    const auto nomem = [&](const char *what, size_t bytes) {
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
-        return RT_E_NOMEM;
-    };
-    if (!q.d_stft_tw) {
-        const std::vector<C> tw = record_stft_twiddles<C, typename std::conditional<sizeof(P) == 4, double, long double>::type>(N);
-        void *d = nullptr;
-        if (hipMalloc(&d, tw.size() * sizeof(C)) != hipSuccess) return nomem("the twiddle table", tw.size() * sizeof(C));
-        if (hipMemcpy(d, tw.data(), tw.size() * sizeof(C), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            h->err = std::string(entry) + ": uploading the twiddle table failed";
-            return RT_E_HIP;
-        }
-        q.d_stft_tw = d;
-    }
-    if (!l->f64 && !q.d_stft_win) {
-        float *d = nullptr;
-        if (hipMalloc(&d, (size_t)N * sizeof(float)) != hipSuccess) return nomem("the window", (size_t)N * sizeof(float));
-        if (hipMemcpy(d, l->h_window.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            h->err = std::string(entry) + ": uploading the window failed";
-            return RT_E_HIP;
-        }
-        q.d_stft_win = d;
-    }
-    // both pools before either is touched: where the second cannot be had, the first still holds what it held
-    const size_t val_bytes = (size_t)((uint64_t)elems * sizeof(C));
-    const size_t b_first = (n + 1) * sizeof(int64_t), b_seg = n * sizeof(int64_t), b_i32 = n * sizeof(int32_t);
-    const size_t work_bytes = b_first + b_seg + 2 * b_i32;
-    if (qs.band_vals_bytes < val_bytes || qs.band_work_bytes < work_bytes) qs.band_k = 0;  // (a pool that grows loses what it held)
-    if (!stft_hop_grow(&qs.d_band_vals, &qs.band_vals_bytes, val_bytes)) return nomem("the call's band", val_bytes);
-    if (!stft_hop_grow(&qs.d_band_work, &qs.band_work_bytes, work_bytes)) return nomem("the work list", work_bytes);
-    qs.band_k = 0;  // (whatever the pool held is gone from here on)
-    std::vector<char> packed(work_bytes);
-    std::memcpy(packed.data(), work.frame_first.data(), b_first);
-    std::memcpy(packed.data() + b_first, work.pool_seg.data(), b_seg);
-    std::memcpy(packed.data() + b_first + b_seg, work.lp.data(), b_i32);
-    std::memcpy(packed.data() + b_first + b_seg + b_i32, work.fi.data(), b_i32);
-    StftBandArgs<P> b{};
-    StftHopArgs<P> &a = b.hop;
-    b.half_width = w;
-    a.pool = qs.d_pool;
-    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_band_work);
-    a.pool_seg = reinterpret_cast<const int64_t *>(qs.d_band_work + b_first);
-    a.lp = reinterpret_cast<const int32_t *>(qs.d_band_work + b_first + b_seg);
-    a.fi = reinterpret_cast<const int32_t *>(qs.d_band_work + b_first + b_seg + b_i32);
-    a.n_records = (int32_t)n;
-    a.nperseg = N;
-    a.hop_div = k;
-    a.n_frames = frames;
-    a.pool_samples = qs.offsets.back();
-    a.tw = static_cast<const C *>(q.d_stft_tw);
-    a.values = reinterpret_cast<C *>(qs.d_band_vals);
-    if constexpr (sizeof(P) == 4) {
-        a.window = q.d_stft_win;
-        a.root = stft_root_f32(l->cfg.scale);
-    } else {
-        a.window = l->f64->d_window;
-        a.root = stft_root_f64(l->f64->c.scale);
-    }
-    // (a pageable source: `packed` lives until the stream has been waited for below)
-    hipError_t e = hipMemcpyAsync(qs.d_band_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
-    if (e == hipSuccess) {
-        if (qs.fmt == kFmtU8) launch_record_band<P, kFmtU8>(b, group, q.s_gather);
-        else if (qs.fmt == kFmtI16) launch_record_band<P, kFmtI16>(b, group, q.s_gather);
-        else if (qs.fmt == kFmtI8) launch_record_band<P, kFmtI8>(b, group, q.s_gather);
-        else launch_record_band<P, kFmtC64>(b, group, q.s_gather);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": record_band: " + hipGetErrorString(e);
-        return RT_E_HIP;
-    }
-    qs.band_k = k;
-    qs.band_w = w;
-    return RT_OK;
-}
-
-template <class P>
-int fetch_record_band_impl(rt_handle *h, const char *entry, const char *twin, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets,
-                           int32_t *first_seg, size_t n_first, P *values, size_t cap_frames, size_t *n_frames) {
-    using C = typename stft_types<P>::C;
-    if (!h || !n_frames) return RT_E_INVALID;
-    *n_frames = 0;
-    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
-        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
-        return RT_E_INVALID;
-    }
-    const int N = iq_nperseg(h);
-    if (!stft_band_ok(N, hop_div, half_width)) {
-        h->err = std::string(entry) + ": hop_div k = " + std::to_string(hop_div) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) +
-                 " and divide nperseg N = " + std::to_string(N) + ", half_width w = " + std::to_string(half_width) + " must be 0 ... " +
-                 std::to_string(kStftBandMaxHalf) + " with 2 w + 1 <= N";
-        return RT_E_INVALID;
-    }
-    std::vector<rt_handle *> lanes;
-    size_t records = 0, samples = 0;
-    int bps = 0;
-    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    int rc = record_tables<P>(h, l, entry);
     if (rc != RT_OK) return rc;
-    if ((offsets && n_offsets != records + 1) || (first_seg && n_first != records)) {
-        h->err = std::string(entry) + ": n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number";
-        return RT_E_INVALID;
-    }
-    // every lane's frame plan, before anything is launched or written
-    const size_t B = (size_t)stft_band_columns(half_width);
-    std::vector<StftHopWork> works(lanes.size());
-    std::vector<int64_t> frames(lanes.size());
-    size_t total = 0;
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
-        frames[i] = stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.first_seg.size(), N, hop_div, &works[i]);
-        if (frames[i] < 0 || stft_band_elems(frames[i], half_width) < 0) {
-            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-            return RT_E_HIP;
-        }
-        total += (size_t)frames[i];
-    }
-    *n_frames = total;
-    const bool query = !values || cap_frames == 0;
-    if (!query && cap_frames < total) {
-        h->err = std::string(entry) + ": output buffer too small";
-        return RT_E_CAPACITY;
-    }
-    if (!query)
-        for (size_t i = 0; i < lanes.size(); ++i) {
-            const int rs = record_band_run<P>(h, lanes[i], entry, hop_div, half_width, works[i], frames[i]);
-            if (rs != RT_OK) return rs;
-        }
-    size_t r0 = 0, c0 = 0;
-    if (offsets) offsets[0] = 0;
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        rt_handle *l = lanes[i];
-        const IqSlot &qs = l->riq->slot[l->riq->delivered];
-        const size_t n = qs.first_seg.size(), mine = (size_t)frames[i];
-        if (offsets)
-            for (size_t r = 0; r < n; ++r) offsets[r0 + r + 1] = (int64_t)c0 + works[i].frame_first[r + 1];
-        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
-        if (!query && mine) {
-            RT_HIP(h, hipSetDevice(l->cfg.device));
-            RT_HIP(h, hipMemcpy(values + 2 * c0 * B, qs.d_band_vals, mine * B * sizeof(C), hipMemcpyDeviceToHost));
-        }
-        r0 += n;
-        c0 += mine;
-    }
-    return RT_OK;
+    rc = product_begin(h, entry, p, (size_t)((uint64_t)elems * sizeof(C)), "the call's band", hop_work_bytes(qs.first_seg.size()), "the work list");
+    if (rc != RT_OK) return rc;
+    std::vector<char> packed;
+    StftBandArgs<P> b{};
+    b.hop = hop_args<P>(l, p, k, work, frames, &packed);
+    b.half_width = w;
+    return product_finish(h, q, entry, p, k, w, packed, "record_band", [&] {
+        with_record_format(qs.fmt, [&](auto fmt) { launch_record_band<P, decltype(fmt)::value>(b, group, q.s_gather); });
+    });
 }
 
-// ---- rt_fetch_record_estimates: one row per record, reduced from the hop pool's frames (rt_record_estimates.h) ----
-// The rows of lane-less handle `l`'s delivered call for hop_div k into its slot's row pool: once per delivered call and k.  The hop
-// pool is made to hold k first (record_stft_hop_run: a no-op where it does); the frames stay on the device.
+// ---- rt_fetch_record_estimates: one row per record, reduced from the hop product's frames (rt_record_estimates.h) ----
+// The rows of lane-less handle `l`'s delivered call for hop_div k into its slot's kProdEst: once per delivered call and k.  The hop
+// product is made to hold k first (record_stft_hop_run: a no-op where it does); the frames stay on the device.  The rows are a
+// product of their own: they stay valid when the hop product moves on to another k.
 template <class P>
-int record_estimates_run(rt_handle *h, rt_handle *l, const char *entry, int k, const StftHopWork &hop, const EstimatesWork &work, int64_t frames) {
+int record_estimates_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &hop, const EstimatesWork &work, int64_t frames) {
     using C = typename stft_types<P>::C;
     RecordIq &q = *l->riq;
     IqSlot &qs = q.slot[q.delivered];
-    if (qs.est_k == k) return RT_OK;
+    IqProduct &p = qs.prod[kProdEst];
+    if (p.holds(k, w)) return RT_OK;
     const size_t n = qs.first_seg.size();
     if (n == 0) {
-        qs.est_k = k;
+        p.set(k, w);
         return RT_OK;
     }
-    if (n > (size_t)INT32_MAX) {  // (the kernel counts records in int32; the grid is a quarter of that)
-        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-        return RT_E_HIP;
-    }
-    const int rs = record_stft_hop_run<P>(h, l, entry, k, hop, frames);
-    if (rs != RT_OK) return rs;
+    if (n > (size_t)INT32_MAX) return record_mismatch(h, entry);  // (the kernel counts records in int32; the grid is a quarter of that)
+    int rc = record_stft_hop_run<P>(h, l, entry, k, w, hop, frames);
+    if (rc != RT_OK) return rc;
     RT_HIP(h, hipSetDevice(l->cfg.device));
-    const auto nomem = [&](const char *what, size_t bytes) {
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
-        return RT_E_NOMEM;
-    };
-    qs.est_k = 0;  // (whatever the row pool held is gone from here on)
-    const size_t row_bytes = n * sizeof(rt_record_estimate);
-    if (!stft_hop_grow(&qs.d_est, &qs.est_bytes, row_bytes)) return nomem("the call's estimates", row_bytes);
     // the plan in one piece: the turn-back table, frame_first [n + 1], base [n][2], range [n][4], lp [n], fmod [n]
     const size_t b_first = (n + 1) * sizeof(int64_t), b_base = 2 * n * sizeof(int64_t), b_range = 4 * n * sizeof(int32_t), b_i32 = n * sizeof(int32_t);
     const size_t o_first = kEstTurnBytes, o_base = o_first + b_first, o_range = o_base + b_base, o_lp = o_range + b_range, o_fmod = o_lp + b_i32;
     const size_t work_bytes = o_fmod + b_i32;
-    if (!stft_hop_grow(&qs.d_est_work, &qs.est_work_bytes, work_bytes)) return nomem("the estimates' plan", work_bytes);
+    rc = product_begin(h, entry, p, n * sizeof(rt_record_estimate), "the call's estimates", work_bytes, "the estimates' plan");
+    if (rc != RT_OK) return rc;
     std::vector<char> packed(work_bytes);
     static_assert(kEstTurnBytes >= 2 * kStftHopMaxDiv * (int)sizeof(double), "the turn-back table holds every hop_div");
     estimates_turn_table(k, reinterpret_cast<double *>(packed.data()));
@@ -2188,90 +1887,24 @@ int record_estimates_run(rt_handle *h, rt_handle *l, const char *entry, int k, c
     std::memcpy(packed.data() + o_lp, work.lp.data(), b_i32);
     std::memcpy(packed.data() + o_fmod, work.fmod.data(), b_i32);
     EstimatesArgs<P> a{};
-    a.values = reinterpret_cast<const C *>(qs.d_hop_vals);
-    a.turn = reinterpret_cast<const double *>(qs.d_est_work);
-    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_est_work + o_first);
-    a.base = reinterpret_cast<const int64_t *>(qs.d_est_work + o_base);
-    a.range = reinterpret_cast<const int32_t *>(qs.d_est_work + o_range);
-    a.lp = reinterpret_cast<const int32_t *>(qs.d_est_work + o_lp);
-    a.fmod = reinterpret_cast<const int32_t *>(qs.d_est_work + o_fmod);
+    a.values = reinterpret_cast<const C *>(qs.prod[kProdHop].out);
+    a.turn = reinterpret_cast<const double *>(p.work);
+    a.frame_first = reinterpret_cast<const int64_t *>(p.work + o_first);
+    a.base = reinterpret_cast<const int64_t *>(p.work + o_base);
+    a.range = reinterpret_cast<const int32_t *>(p.work + o_range);
+    a.lp = reinterpret_cast<const int32_t *>(p.work + o_lp);
+    a.fmod = reinterpret_cast<const int32_t *>(p.work + o_fmod);
     a.n_records = (int32_t)n;
     a.nperseg = iq_nperseg(l);
     a.hop_div = k;
     a.n_frames = frames;
-    a.out = reinterpret_cast<rt_record_estimate *>(qs.d_est);
-    // (a pageable source: `packed` lives until the stream has been waited for below)
-    hipError_t e = hipMemcpyAsync(qs.d_est_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
-    if (e == hipSuccess) {
+    a.out = reinterpret_cast<rt_record_estimate *>(p.out);
+    return product_finish(h, q, entry, p, k, w, packed, "record_estimates", [&] {
         hipLaunchKernelGGL((record_estimates<P>), dim3((unsigned)((n + kStftWaves - 1) / kStftWaves)), dim3(kStftBlock), 0, q.s_gather, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": record_estimates: " + hipGetErrorString(e);
-        return RT_E_HIP;
-    }
-    qs.est_k = k;
-    return RT_OK;
+    });
 }
 
-int fetch_record_estimates_impl(rt_handle *h, const char *entry, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out) {
-    if (!h || !n_out) return RT_E_INVALID;
-    *n_out = 0;
-    const int N = iq_nperseg(h);
-    if (!stft_hop_div_ok(N, hop_div)) {
-        h->err = std::string(entry) + ": hop_div k = " + std::to_string(hop_div) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) +
-                 " and divide nperseg N = " + std::to_string(N);
-        return RT_E_INVALID;
-    }
-    std::vector<rt_handle *> lanes;
-    size_t records = 0, samples = 0;
-    int bps = 0;
-    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
-    if (rc != RT_OK) return rc;
-    // every lane's plans, before anything is launched or written
-    std::vector<StftHopWork> hops(lanes.size());
-    std::vector<EstimatesWork> works(lanes.size());
-    std::vector<int64_t> frames(lanes.size());
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
-        const size_t n = qs.first_seg.size();
-        frames[i] = qs.start.size() == n && qs.end.size() == n && qs.fi.size() == n
-                        ? estimates_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.start.data(), qs.end.data(), n, N, hop_div, &works[i])
-                        : -1;
-        if (frames[i] < 0 || stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), n, N, hop_div, &hops[i]) != frames[i]) {
-            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-            return RT_E_HIP;
-        }
-    }
-    *n_out = records;
-    const bool query = !out || cap == 0;
-    if (query) return RT_OK;
-    if (cap < records) {
-        h->err = std::string(entry) + ": output buffer too small";
-        return RT_E_CAPACITY;
-    }
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        const int rs = lanes[i]->f64 ? record_estimates_run<double>(h, lanes[i], entry, hop_div, hops[i], works[i], frames[i])
-                                     : record_estimates_run<float>(h, lanes[i], entry, hop_div, hops[i], works[i], frames[i]);
-        if (rs != RT_OK) return rs;
-    }
-    size_t r0 = 0;
-    for (rt_handle *l : lanes) {
-        const IqSlot &qs = l->riq->slot[l->riq->delivered];
-        const size_t n = qs.first_seg.size();
-        if (n) {
-            RT_HIP(h, hipSetDevice(l->cfg.device));
-            RT_HIP(h, hipMemcpy(out + r0, qs.d_est, n * sizeof(rt_record_estimate), hipMemcpyDeviceToHost));
-        }
-        r0 += n;
-    }
-    return RT_OK;
-}
-
-// ---- rt_fetch_record_spectrum: one row per record and its column means and peaks, reduced from the band pool (rt_record_spectrum.h) ----
+// ---- rt_fetch_record_spectrum: one row per record and its column means and peaks, reduced from the band product (rt_record_spectrum.h) ----
 template <class P>
 void launch_record_spectrum(const SpectrumArgs<P> &a, hipStream_t st) {
     const dim3 grid((unsigned)(((size_t)a.n_records + kStftWaves - 1) / kStftWaves)), block(kStftBlock);
@@ -2281,130 +1914,172 @@ void launch_record_spectrum(const SpectrumArgs<P> &a, hipStream_t st) {
     else hipLaunchKernelGGL((record_spectrum<P, 8>), grid, block, 0, st, a);
 }
 
-// The rows of lane-less handle `l`'s delivered call for (k, w) into its slot's row pool: once per delivered call and pair.  The band
-// pool is made to hold (k, w) first (record_band_run: a no-op where it does); the frames stay on the device.
+// The rows of lane-less handle `l`'s delivered call for (k, w) into its slot's kProdSpec: once per delivered call and pair.  The
+// band product is made to hold (k, w) first (record_band_run: a no-op where it does); the frames stay on the device, and the rows
+// stay valid when the band product moves on to another pair.
 template <class P>
 int record_spectrum_run(rt_handle *h, rt_handle *l, const char *entry, int k, int w, const StftHopWork &hop, const EstimatesWork &work, int64_t frames) {
     using C = typename stft_types<P>::C;
     RecordIq &q = *l->riq;
     IqSlot &qs = q.slot[q.delivered];
-    if (qs.spec_k == k && qs.spec_w == w) return RT_OK;
+    IqProduct &p = qs.prod[kProdSpec];
+    if (p.holds(k, w)) return RT_OK;
     const size_t n = qs.first_seg.size();
     if (n == 0) {
-        qs.spec_k = k;
-        qs.spec_w = w;
+        p.set(k, w);
         return RT_OK;
     }
-    if (n > (size_t)INT32_MAX) {  // (the kernel counts records in int32; the grid is a quarter of that)
-        h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-        return RT_E_HIP;
-    }
-    const int rs = record_band_run<P>(h, l, entry, k, w, hop, frames);
-    if (rs != RT_OK) return rs;
+    if (n > (size_t)INT32_MAX) return record_mismatch(h, entry);  // (the kernel counts records in int32; the grid is a quarter of that)
+    int rc = record_band_run<P>(h, l, entry, k, w, hop, frames);
+    if (rc != RT_OK) return rc;
     RT_HIP(h, hipSetDevice(l->cfg.device));
-    const auto nomem = [&](const char *what, size_t bytes) {
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": no device memory for " + what + " (" + std::to_string(bytes) + " bytes)";
-        return RT_E_NOMEM;
-    };
     // the plan in one piece: frame_first [n + 1], range [n][4], lp [n]
-    const size_t B = (size_t)stft_band_columns(w);
-    const size_t row_bytes = n * sizeof(rt_record_spectrum), col_bytes = n * B * sizeof(double), pool_bytes = spectrum_pool_bytes(n, w);
+    const size_t row_bytes = n * sizeof(rt_record_spectrum), col_bytes = n * (size_t)stft_band_columns(w) * sizeof(double);
     static_assert(sizeof(rt_record_spectrum) == 48, "the row pool's layout: rows of 48 bytes, then the means, then the peaks");
     const size_t b_first = (n + 1) * sizeof(int64_t), b_range = 4 * n * sizeof(int32_t), b_i32 = n * sizeof(int32_t);
     const size_t o_range = b_first, o_lp = o_range + b_range, work_bytes = o_lp + b_i32;
-    if (qs.spec_bytes < pool_bytes || qs.spec_work_bytes < work_bytes) qs.spec_k = 0;  // (a pool that grows loses what it held)
-    if (!stft_hop_grow(&qs.d_spec, &qs.spec_bytes, pool_bytes)) return nomem("the call's spectrum rows", pool_bytes);
-    if (!stft_hop_grow(&qs.d_spec_work, &qs.spec_work_bytes, work_bytes)) return nomem("the spectrum's plan", work_bytes);
-    qs.spec_k = 0;  // (whatever the row pool held is gone from here on)
+    rc = product_begin(h, entry, p, spectrum_pool_bytes(n, w), "the call's spectrum rows", work_bytes, "the spectrum's plan");
+    if (rc != RT_OK) return rc;
     std::vector<char> packed(work_bytes);
     std::memcpy(packed.data(), work.frame_first.data(), b_first);
     std::memcpy(packed.data() + o_range, work.range.data(), b_range);
     std::memcpy(packed.data() + o_lp, work.lp.data(), b_i32);
     SpectrumArgs<P> a{};
-    a.values = reinterpret_cast<const C *>(qs.d_band_vals);
-    a.frame_first = reinterpret_cast<const int64_t *>(qs.d_spec_work);
-    a.range = reinterpret_cast<const int32_t *>(qs.d_spec_work + o_range);
-    a.lp = reinterpret_cast<const int32_t *>(qs.d_spec_work + o_lp);
+    a.values = reinterpret_cast<const C *>(qs.prod[kProdBand].out);
+    a.frame_first = reinterpret_cast<const int64_t *>(p.work);
+    a.range = reinterpret_cast<const int32_t *>(p.work + o_range);
+    a.lp = reinterpret_cast<const int32_t *>(p.work + o_lp);
     a.n_records = (int32_t)n;
     a.hop_div = k;
     a.half_width = w;
     a.n_frames = frames;
-    a.rows = reinterpret_cast<rt_record_spectrum *>(qs.d_spec);
-    a.mean = reinterpret_cast<double *>(qs.d_spec + row_bytes);
-    a.peak = reinterpret_cast<double *>(qs.d_spec + row_bytes + col_bytes);
-    // (a pageable source: `packed` lives until the stream has been waited for below)
-    hipError_t e = hipMemcpyAsync(qs.d_spec_work, packed.data(), work_bytes, hipMemcpyHostToDevice, q.s_gather);
-    if (e == hipSuccess) {
-        launch_record_spectrum<P>(a, q.s_gather);
-        e = hipGetLastError();
+    a.rows = reinterpret_cast<rt_record_spectrum *>(p.out);
+    a.mean = reinterpret_cast<double *>(p.out + row_bytes);
+    a.peak = reinterpret_cast<double *>(p.out + row_bytes + col_bytes);
+    return product_finish(h, q, entry, p, k, w, packed, "record_spectrum", [&] { launch_record_spectrum<P>(a, q.s_gather); });
+}
+
+// ---- the entries: refusals, the plan, the products, the delivery ----
+// The plan of the delivered call for hop_div k: the lanes that hold it and each lane's frame list, before anything is launched or
+// written.  kPlanRows: each lane's EstimatesWork too.  kPlanSegments: the k = 1 entry, whose frames are the delivered segments --
+// they are counted and no list is made (record_stft_run).  `band_w` >= 0: the frames are a band's, 2 band_w + 1 values each.
+enum { kPlanSegments, kPlanFrames, kPlanRows };
+struct RecordPlan {
+    std::vector<rt_handle *> lanes;
+    std::vector<StftHopWork> hops;    // [lanes]
+    std::vector<EstimatesWork> rows;  // [lanes] where wanted
+    std::vector<int64_t> frames;      // [lanes]
+    size_t records = 0, total = 0;    // records and frames over all lanes
+    IqSlot &slot(size_t i) const { return lanes[i]->riq->slot[lanes[i]->riq->delivered]; }
+};
+int record_plan(rt_handle *h, const char *entry, int what, int k, int band_w, const int64_t *offsets, size_t n_offsets, const int32_t *first_seg,
+                size_t n_first, RecordPlan *p) {
+    const bool want_rows = what == kPlanRows;
+    size_t samples = 0;
+    int bps = 0;
+    const int rc = iq_delivered_call(h, entry, &p->lanes, &p->records, &samples, &bps);
+    if (rc != RT_OK) return rc;
+    if ((offsets && n_offsets != p->records + 1) || (first_seg && n_first != p->records))
+        return record_refuse(h, entry, "n_offsets must be the number of records the last rt_fetch delivered plus one, n_first that number");
+    const int N = iq_nperseg(h);
+    p->hops.resize(p->lanes.size());
+    p->rows.resize(want_rows ? p->lanes.size() : 0);
+    p->frames.resize(p->lanes.size());
+    for (size_t i = 0; i < p->lanes.size(); ++i) {
+        const IqSlot &qs = p->slot(i);
+        const size_t n = qs.first_seg.size();
+        const bool sized = qs.fi.size() == n && (!want_rows || (qs.start.size() == n && qs.end.size() == n));
+        int64_t f = what == kPlanSegments ? qs.offsets.back() / N
+                    : sized               ? stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), n, N, k, &p->hops[i])
+                                          : -1;
+        // (both builders agree on the frame count)
+        if (want_rows && f >= 0 &&
+            estimates_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.start.data(), qs.end.data(), n, N, k, &p->rows[i]) != f)
+            f = -1;
+        if (f < 0 || (band_w >= 0 && stft_band_elems(f, band_w) < 0)) return record_mismatch(h, entry);
+        p->frames[i] = f;
+        p->total += (size_t)f;
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(q.s_gather);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(q.s_gather);  // (`packed` must outlive whatever copy did start)
-        (void)hipGetLastError();
-        h->err = std::string(entry) + ": record_spectrum: " + hipGetErrorString(e);
-        return RT_E_HIP;
+    return RT_OK;
+}
+// the (k, w) rule of an entry: the band and spectrum entries', or the hop's alone
+inline std::string record_rule(rt_handle *h, bool band, int k, int w) {
+    return band ? spectrum_refusal(iq_nperseg(h), k, w) : stft_hop_refusal(iq_nperseg(h), k);
+}
+
+// rt_fetch_record_stft (k = 1), _stft_hop and _band (`band`; w = 0 otherwise) and their _f64 twins: `run` makes product `prod` of a
+// lane hold (k, w), and a frame is 2 w + 1 values.
+using RecordFramesRun = int (*)(rt_handle *, rt_handle *, const char *, int, int, const StftHopWork &, int64_t);
+template <class P>
+int fetch_record_frames(rt_handle *h, const char *entry, const char *twin, int prod, RecordFramesRun run, bool band, int k, int w, int64_t *offsets,
+                        size_t n_offsets, int32_t *first_seg, size_t n_first, P *values, size_t cap_frames, size_t *n_frames) {
+    if (!h || !n_frames) return RT_E_INVALID;
+    *n_frames = 0;
+    if ((h->f64 != nullptr) != (sizeof(P) == 8)) {
+        h->err = std::string(entry) + (h->f64 ? " on a float64 handle (rt_create_f64): use " : " on a float32 handle (rt_create): use ") + twin;
+        return RT_E_INVALID;
     }
-    qs.spec_k = k;
-    qs.spec_w = w;
+    const std::string why = record_rule(h, band, k, w);
+    if (!why.empty()) return record_refuse(h, entry, why);
+    RecordPlan plan;
+    const bool segments = prod == kProdStft;
+    const int N = iq_nperseg(h);
+    const int rc = record_plan(h, entry, segments ? kPlanSegments : kPlanFrames, k, band ? w : -1, offsets, n_offsets, first_seg, n_first, &plan);
+    if (rc != RT_OK) return rc;
+    *n_frames = plan.total;
+    const bool query = !values || cap_frames == 0;
+    if (!query && cap_frames < plan.total) return record_refuse(h, entry, "output buffer too small", RT_E_CAPACITY);
+    if (!query)
+        for (size_t i = 0; i < plan.lanes.size(); ++i) {
+            const int rs = run(h, plan.lanes[i], entry, k, w, plan.hops[i], plan.frames[i]);
+            if (rs != RT_OK) return rs;
+        }
+    const size_t frame_bytes = (size_t)stft_band_columns(w) * sizeof(typename stft_types<P>::C);
+    size_t r0 = 0, c0 = 0;
+    if (offsets) offsets[0] = 0;
+    for (size_t i = 0; i < plan.lanes.size(); ++i) {
+        rt_handle *l = plan.lanes[i];
+        const IqSlot &qs = plan.slot(i);
+        const size_t n = qs.first_seg.size(), mine = (size_t)plan.frames[i];
+        if (offsets)
+            for (size_t r = 0; r < n; ++r) offsets[r0 + r + 1] = (int64_t)c0 + (segments ? qs.offsets[r + 1] / N : plan.hops[i].frame_first[r + 1]);
+        if (first_seg && n) std::memcpy(first_seg + r0, qs.first_seg.data(), n * sizeof(int32_t));
+        if (!query && mine) {
+            RT_HIP(h, hipSetDevice(l->cfg.device));
+            RT_HIP(h, hipMemcpy(reinterpret_cast<char *>(values) + c0 * frame_bytes, qs.prod[prod].out, mine * frame_bytes, hipMemcpyDeviceToHost));
+        }
+        r0 += n;
+        c0 += mine;
+    }
     return RT_OK;
 }
 
-int fetch_record_spectrum_impl(rt_handle *h, const char *entry, int32_t hop_div, int32_t half_width, rt_record_spectrum *rows, double *mean, double *peak,
-                               size_t cap, size_t *n_out) {
+// rt_fetch_record_estimates and _spectrum (`band`; w = 0 otherwise): `run32` / `run64` makes product `prod` of a float32 / float64
+// lane hold (k, w); copy(pool, r0, n) hands out a lane's n rows, the caller's rows r0 on, from the product's output pool.
+using RecordRowsRun = int (*)(rt_handle *, rt_handle *, const char *, int, int, const StftHopWork &, const EstimatesWork &, int64_t);
+template <class Copy>
+int fetch_record_rows(rt_handle *h, const char *entry, int prod, RecordRowsRun run32, RecordRowsRun run64, bool band, int k, int w, bool query, size_t cap,
+                      size_t *n_out, Copy copy) {
     if (!h || !n_out) return RT_E_INVALID;
     *n_out = 0;
-    const int N = iq_nperseg(h);
-    const std::string why = spectrum_refusal(N, hop_div, half_width);
-    if (!why.empty()) {
-        h->err = std::string(entry) + ": " + why;
-        return RT_E_INVALID;
-    }
-    std::vector<rt_handle *> lanes;
-    size_t records = 0, samples = 0;
-    int bps = 0;
-    const int rc = iq_delivered_call(h, entry, &lanes, &records, &samples, &bps);
+    const std::string why = record_rule(h, band, k, w);
+    if (!why.empty()) return record_refuse(h, entry, why);
+    RecordPlan plan;
+    const int rc = record_plan(h, entry, kPlanRows, k, band ? w : -1, nullptr, 0, nullptr, 0, &plan);
     if (rc != RT_OK) return rc;
-    // every lane's plans, before anything is launched or written
-    std::vector<StftHopWork> hops(lanes.size());
-    std::vector<EstimatesWork> works(lanes.size());
-    std::vector<int64_t> frames(lanes.size());
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        const IqSlot &qs = lanes[i]->riq->slot[lanes[i]->riq->delivered];
-        const size_t n = qs.first_seg.size();
-        frames[i] = qs.start.size() == n && qs.end.size() == n && qs.fi.size() == n
-                        ? estimates_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), qs.start.data(), qs.end.data(), n, N, hop_div, &works[i])
-                        : -1;
-        if (frames[i] < 0 || stft_band_elems(frames[i], half_width) < 0 ||
-            stft_hop_build_work(qs.offsets.data(), qs.first_seg.data(), qs.fi.data(), n, N, hop_div, &hops[i]) != frames[i]) {
-            h->err = std::string(entry) + ": internal: the delivered call's record list does not match its snippets";
-            return RT_E_HIP;
-        }
-    }
-    *n_out = records;
-    const bool query = !rows || cap == 0;
+    *n_out = plan.records;
     if (query) return RT_OK;
-    if (cap < records) {
-        h->err = std::string(entry) + ": output buffer too small";
-        return RT_E_CAPACITY;
-    }
-    for (size_t i = 0; i < lanes.size(); ++i) {
-        const int rs = lanes[i]->f64 ? record_spectrum_run<double>(h, lanes[i], entry, hop_div, half_width, hops[i], works[i], frames[i])
-                                     : record_spectrum_run<float>(h, lanes[i], entry, hop_div, half_width, hops[i], works[i], frames[i]);
+    if (cap < plan.records) return record_refuse(h, entry, "output buffer too small", RT_E_CAPACITY);
+    for (size_t i = 0; i < plan.lanes.size(); ++i) {
+        const int rs = (plan.lanes[i]->f64 ? run64 : run32)(h, plan.lanes[i], entry, k, w, plan.hops[i], plan.rows[i], plan.frames[i]);
         if (rs != RT_OK) return rs;
     }
-    const size_t B = (size_t)stft_band_columns(half_width);
     size_t r0 = 0;
-    for (rt_handle *l : lanes) {
-        const IqSlot &qs = l->riq->slot[l->riq->delivered];
-        const size_t n = qs.first_seg.size();
+    for (size_t i = 0; i < plan.lanes.size(); ++i) {
+        const size_t n = plan.slot(i).first_seg.size();
         if (n) {
-            const size_t row_bytes = n * sizeof(rt_record_spectrum), col_bytes = n * B * sizeof(double);
-            RT_HIP(h, hipSetDevice(l->cfg.device));
-            RT_HIP(h, hipMemcpy(rows + r0, qs.d_spec, row_bytes, hipMemcpyDeviceToHost));
-            if (mean) RT_HIP(h, hipMemcpy(mean + r0 * B, qs.d_spec + row_bytes, col_bytes, hipMemcpyDeviceToHost));
-            if (peak) RT_HIP(h, hipMemcpy(peak + r0 * B, qs.d_spec + row_bytes + col_bytes, col_bytes, hipMemcpyDeviceToHost));
+            RT_HIP(h, hipSetDevice(plan.lanes[i]->cfg.device));
+            RT_HIP(h, copy(plan.slot(i).prod[prod].out, r0, n));
         }
         r0 += n;
     }
@@ -4331,45 +4006,59 @@ int rt_fetch_record_iq(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t
 
 int rt_fetch_record_stft(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, float *values, size_t cap_cells,
                          size_t *n_cells) {
-    return fetch_record_stft_impl<float>(h, "rt_fetch_record_stft", "rt_fetch_record_stft_f64", offsets, n_offsets, first_seg, n_first, values, cap_cells, n_cells);
+    return fetch_record_frames<float>(h, "rt_fetch_record_stft", "rt_fetch_record_stft_f64", kProdStft, record_stft_run<float>, false, 1, 0, offsets,
+                                      n_offsets, first_seg, n_first, values, cap_cells, n_cells);
 }
 
 int rt_fetch_record_stft_f64(rt_handle *h, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, double *values,
                              size_t cap_cells, size_t *n_cells) {
-    return fetch_record_stft_impl<double>(h, "rt_fetch_record_stft_f64", "rt_fetch_record_stft", offsets, n_offsets, first_seg, n_first, values, cap_cells, n_cells);
+    return fetch_record_frames<double>(h, "rt_fetch_record_stft_f64", "rt_fetch_record_stft", kProdStft, record_stft_run<double>, false, 1, 0, offsets,
+                                       n_offsets, first_seg, n_first, values, cap_cells, n_cells);
 }
 
 int rt_fetch_record_stft_hop(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, float *values,
                              size_t cap_frames, size_t *n_frames) {
-    return fetch_record_stft_hop_impl<float>(h, "rt_fetch_record_stft_hop", "rt_fetch_record_stft_hop_f64", hop_div, offsets, n_offsets, first_seg, n_first,
-                                             values, cap_frames, n_frames);
+    return fetch_record_frames<float>(h, "rt_fetch_record_stft_hop", "rt_fetch_record_stft_hop_f64", kProdHop, record_stft_hop_run<float>, false, hop_div, 0,
+                                      offsets, n_offsets, first_seg, n_first, values, cap_frames, n_frames);
 }
 
 int rt_fetch_record_stft_hop_f64(rt_handle *h, int32_t hop_div, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first, double *values,
                                  size_t cap_frames, size_t *n_frames) {
-    return fetch_record_stft_hop_impl<double>(h, "rt_fetch_record_stft_hop_f64", "rt_fetch_record_stft_hop", hop_div, offsets, n_offsets, first_seg, n_first,
-                                              values, cap_frames, n_frames);
+    return fetch_record_frames<double>(h, "rt_fetch_record_stft_hop_f64", "rt_fetch_record_stft_hop", kProdHop, record_stft_hop_run<double>, false, hop_div, 0,
+                                       offsets, n_offsets, first_seg, n_first, values, cap_frames, n_frames);
 }
 
 int rt_fetch_record_band(rt_handle *h, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
                          float *values, size_t cap_frames, size_t *n_frames) {
-    return fetch_record_band_impl<float>(h, "rt_fetch_record_band", "rt_fetch_record_band_f64", hop_div, half_width, offsets, n_offsets, first_seg, n_first,
-                                         values, cap_frames, n_frames);
+    return fetch_record_frames<float>(h, "rt_fetch_record_band", "rt_fetch_record_band_f64", kProdBand, record_band_run<float>, true, hop_div, half_width,
+                                      offsets, n_offsets, first_seg, n_first, values, cap_frames, n_frames);
 }
 
 int rt_fetch_record_band_f64(rt_handle *h, int32_t hop_div, int32_t half_width, int64_t *offsets, size_t n_offsets, int32_t *first_seg, size_t n_first,
                              double *values, size_t cap_frames, size_t *n_frames) {
-    return fetch_record_band_impl<double>(h, "rt_fetch_record_band_f64", "rt_fetch_record_band", hop_div, half_width, offsets, n_offsets, first_seg, n_first,
-                                          values, cap_frames, n_frames);
+    return fetch_record_frames<double>(h, "rt_fetch_record_band_f64", "rt_fetch_record_band", kProdBand, record_band_run<double>, true, hop_div, half_width,
+                                       offsets, n_offsets, first_seg, n_first, values, cap_frames, n_frames);
 }
 
 int rt_fetch_record_estimates(rt_handle *h, int32_t hop_div, rt_record_estimate *out, size_t cap, size_t *n_out) {
-    return fetch_record_estimates_impl(h, "rt_fetch_record_estimates", hop_div, out, cap, n_out);
+    return fetch_record_rows(h, "rt_fetch_record_estimates", kProdEst, record_estimates_run<float>, record_estimates_run<double>, false, hop_div, 0,
+                             !out || cap == 0, cap, n_out, [&](const char *pool, size_t r0, size_t n) {
+                                 return hipMemcpy(out + r0, pool, n * sizeof(rt_record_estimate), hipMemcpyDeviceToHost);
+                             });
 }
 
 int rt_fetch_record_spectrum(rt_handle *h, int32_t hop_div, int32_t half_width, rt_record_spectrum *rows, double *mean, double *peak, size_t cap,
                              size_t *n_out) {
-    return fetch_record_spectrum_impl(h, "rt_fetch_record_spectrum", hop_div, half_width, rows, mean, peak, cap, n_out);
+    // (a lane's pool: its rows, then its means, then its peaks -- spectrum_pool_bytes)
+    return fetch_record_rows(h, "rt_fetch_record_spectrum", kProdSpec, record_spectrum_run<float>, record_spectrum_run<double>, true, hop_div, half_width,
+                             !rows || cap == 0, cap, n_out, [&](const char *pool, size_t r0, size_t n) {
+                                 const size_t B = (size_t)stft_band_columns(half_width);
+                                 const size_t row_bytes = n * sizeof(rt_record_spectrum), col_bytes = n * B * sizeof(double);
+                                 hipError_t e = hipMemcpy(rows + r0, pool, row_bytes, hipMemcpyDeviceToHost);
+                                 if (e == hipSuccess && mean) e = hipMemcpy(mean + r0 * B, pool + row_bytes, col_bytes, hipMemcpyDeviceToHost);
+                                 if (e == hipSuccess && peak) e = hipMemcpy(peak + r0 * B, pool + row_bytes + col_bytes, col_bytes, hipMemcpyDeviceToHost);
+                                 return e;
+                             });
 }
 
 // ---- rt_set_input_stats / rt_fetch_input_stats (include/rt_analyze.h) ----

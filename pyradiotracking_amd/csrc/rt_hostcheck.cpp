@@ -792,9 +792,9 @@ long long hc_estimates_work(const int64_t *offsets, const int32_t *first_seg, co
     if (turn) estimates_turn_table(k, turn);
     return (long long)frames;
 }
-// rt_fetch_record_spectrum's argument rule: the refusal's text into `out` (cut to cap - 1 characters), its length; 0: accepted
-int hc_spectrum_refusal(int nperseg, int k, int w, char *out, int cap) {
-    const std::string why = spectrum_refusal(nperseg, k, w);
+// The argument rules of rt_fetch_record_band and _spectrum (k, w) and of rt_fetch_record_stft_hop and _estimates (k): the refusal's
+// text into `out` (cut to cap - 1 characters), its length; 0: accepted
+static int refusal_out(const std::string &why, char *out, int cap) {
     if (out && cap > 0) {
         const size_t n = std::min(why.size(), (size_t)cap - 1);
         std::memcpy(out, why.data(), n);
@@ -802,6 +802,8 @@ int hc_spectrum_refusal(int nperseg, int k, int w, char *out, int cap) {
     }
     return (int)why.size();
 }
+int hc_spectrum_refusal(int nperseg, int k, int w, char *out, int cap) { return refusal_out(spectrum_refusal(nperseg, k, w), out, cap); }
+int hc_stft_hop_refusal(int nperseg, int k, char *out, int cap) { return refusal_out(stft_hop_refusal(nperseg, k), out, cap); }
 long long hc_spectrum_pool_bytes(long long n, int w) { return (long long)spectrum_pool_bytes((size_t)n, w); }
 float hc_stft_root_f32(float scale) { return stft_root_f32(scale); }
 double hc_stft_root_f64(double scale) { return stft_root_f64(scale); }

@@ -220,12 +220,15 @@ inline void estimates_turn_table(int k, double *cs /* [2 k] */) {
 
 // ---- rt_fetch_record_spectrum: one row per record from the band's frames (record_spectrum, rt_record_spectrum.h) ----
 // The frames are the band entry's and the inside runs the estimates entry's: the plan is EstimatesWork (estimates_build_work) and
-// the argument rule stft_band_ok.  What the entry says where the rule refuses (k, w, N), before anything is launched or copied;
-// empty where it accepts.
+// the argument rule stft_band_ok.  What an entry says where its rule refuses, before anything is launched or copied; empty where
+// it accepts: the hop and estimates entries of (k, N), the band and spectrum entries of (k, w, N).
+inline std::string stft_hop_rule(int N, int k) {
+    return "hop_div k = " + std::to_string(k) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) + " and divide nperseg N = " + std::to_string(N);
+}
+inline std::string stft_hop_refusal(int N, int k) { return stft_hop_div_ok(N, k) ? std::string() : stft_hop_rule(N, k); }
 inline std::string spectrum_refusal(int N, int k, int w) {
     if (stft_band_ok(N, k, w)) return std::string();
-    return "hop_div k = " + std::to_string(k) + " must be 1 ... " + std::to_string(kStftHopMaxDiv) + " and divide nperseg N = " + std::to_string(N) +
-           ", half_width w = " + std::to_string(w) + " must be 0 ... " + std::to_string(kStftBandMaxHalf) + " with 2 w + 1 <= N";
+    return stft_hop_rule(N, k) + ", half_width w = " + std::to_string(w) + " must be 0 ... " + std::to_string(kStftBandMaxHalf) + " with 2 w + 1 <= N";
 }
 // bytes of a slot's row pool for n records: the 48-byte rows, then the means and the peaks, [n][2 w + 1] float64 each
 inline size_t spectrum_pool_bytes(size_t n, int w) { return n * (48 + 2 * sizeof(double) * (size_t)stft_band_columns(w)); }

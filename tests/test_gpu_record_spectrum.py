@@ -290,6 +290,57 @@ def test_the_order_of_calls_does_not_change_the_bytes_and_another_pair_rebuilds(
     assert n[0] > 20
 
 
+def test_products_that_grow_between_two_calls_of_a_slot_give_a_fresh_handles_bytes():
+    """A call slot's hop and band pools start at 65536 bytes.  A small call leaves all five entries' products in the slot, at
+    different keys for the hop and the band entry; a later call through the same slot (two calls on: a handle has two slots) needs
+    more than that floor, so both pools are freed and made again under products that still carry the small call's sizes.  Every
+    entry, asked in another order, gives the bytes of a handle that has only ever seen the large call."""
+    from tests import detect_order_cases as doc
+
+    N, T, margin, n_streams = 32, 400, 2, 12
+    small = [[(3, 10, 5)], [(N - 1, 20, 9)], [(1, 30, 3)], [(N // 2, 40, 12)]] + [[]] * 8  # per stream: (bin, first segment, segments)
+    # (clear of the buffer's start: no look-back; an eighth of the buffer: the row means stay the noise's)
+    large = [[(3 + s, 5 + s, 48)] for s in range(n_streams)]
+
+    def feed(pulses, seed):
+        return np.stack([doc.plant(N, T, [(f, t0, r, doc.TONE_DBW) for f, t0, r in p], seed=1000 * seed + s) for s, p in enumerate(pulses)])
+
+    def handle():
+        return BatchSignalAnalyzer([str(i) for i in range(n_streams)], sdr_callback_length=T * N, lanes=1, record_iq=True, record_iq_margin=margin,
+                                   **sc.small_settings(N))
+
+    def flat(got):
+        return b"".join(np.ascontiguousarray(a).tobytes() for a in (got if isinstance(got, tuple) else (got,)))
+
+    entries = dict(stft=lambda b: b.fetch_record_stft(), hop=lambda b: b.fetch_record_stft(hop_div=16), band=lambda b: b.fetch_record_band(4, 2),
+                   est=lambda b: b.fetch_record_estimates(hop_div=16), spec=lambda b: b.fetch_record_spectrum(4, 2))
+    key = ("stream", "fi", "start", "end")
+    b, twin = handle(), handle()
+    try:
+        b.enqueue(feed(small, 0))
+        assert len(b.fetch_records()) >= 4
+        got ={name: entries[name](b) for name in ("stft", "hop", "band", "est", "spec")}
+        assert 0 < got["hop"][2].nbytes <= 65536 and 0 < got["band"][2].nbytes <= 65536, (got["hop"][2].shape, got["band"][2].shape)
+        b.enqueue(feed(small, 1))  # the handle's other slot
+        b.fetch_records()
+        b.enqueue(feed(large, 2))  # ... and the first one again
+        rec = b.fetch_records()
+        got = {name: entries[name](b) for name in ("spec", "est", "band", "hop", "stft")}
+        twin.enqueue(feed(large, 2))
+        rec_twin = twin.fetch_records()
+        want = {name: entries[name](twin) for name in ("stft", "hop", "band", "est", "spec")}
+        assert len(rec) >= n_streams and all(rec[f].tolist() == rec_twin[f].tolist() for f in key)
+        # frames x 8 bytes (complex64) of the hop entry, x 5 columns of the band entry: past the floor, so both pools grew
+        assert want["hop"][2].dtype == want["band"][2].dtype == np.complex64
+        assert want["hop"][2].nbytes > 65536 and want["band"][2].nbytes > 65536 and want["band"][2].shape[1] == 5
+        for name in want:
+            assert flat(got[name]) == flat(want[name]), name
+        assert len(got["est"]) == len(got["spec"][0]) == len(rec)
+    finally:
+        b.close()
+        twin.close()
+
+
 # ---- 5: a constant segment, a NaN sample ---------------------------------------------------------------------------------------------
 CONST_VALUE = np.complex64(complex(np.float32(0.3), np.float32(-0.7)))  # a full-mantissa constant
 

@@ -28,6 +28,7 @@ def hc():
     lib.hc_estimates_work.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.hc_estimates_work.restype = C.c_longlong
     lib.hc_spectrum_refusal.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    lib.hc_stft_hop_refusal.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.hc_spectrum_pool_bytes.argtypes = [C.c_longlong, C.c_int]
     lib.hc_spectrum_pool_bytes.restype = C.c_longlong
     return lib
@@ -70,6 +71,12 @@ def test_the_entry_exists_and_refuses_bad_arguments_first(hc):
         assert why and f"k = {k}" in why and f"w = {w}" in why and f"N = {N}" in why, (N, k, w, why)
     for N, k, w in ((8, 1, 3), (8, 8, 0), (256, 16, 8), (300, 15, 8), (17, 1, 8), (1, 1, 0)):
         assert _refusal(hc, N, k, w) == "", (N, k, w)
+    # the hop and estimates entries' rule has no w (stft_hop_refusal): its words are the front of the band rule's
+    for N, k, ok in ((256, 3, False), (256, 0, False), (256, 17, False), (300, 8, False), (256, 16, True), (300, 15, True), (1, 1, True)):
+        buf = C.create_string_buffer(512)
+        assert hc.hc_stft_hop_refusal(N, k, buf, 512) == len(buf.value)
+        assert buf.value.decode() == ("" if ok else f"hop_div k = {k} must be 1 ... 16 and divide nperseg N = {N}"), (N, k)
+        assert _refusal(hc, N, k, 9).startswith(f"hop_div k = {k} must be 1 ... 16 and divide nperseg N = {N}, half_width w = 9 must be 0 ... 8")
     for n_rec, w in ((0, 0), (1, 0), (7, 8), (79000, 2)):
         assert hc.hc_spectrum_pool_bytes(n_rec, w) == n_rec * (48 + 16 * (2 * w + 1))
 
